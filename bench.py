@@ -2,6 +2,7 @@
 """Contract benchmark of the GraphNet forward hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--scaling strong|weak]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one synthetic batch that is already resident in
 HBM: destination-CSR build for the batch's edge_index (topology cache cleared, so it is paid
@@ -15,10 +16,17 @@ configs[3] "c4": the SAME c3 batch split by graph id into N contiguous ranges ba
 ("strong": total work fixed; `--scaling weak` gives every rank its own full-size batch instead).
 Graphs are independent, so the timed forward has no data-path collective.
 
-After the timed region the same JSON line gets a `train` object: a few training steps (forward + CE
-loss + backward on the K8 kernels + ONE flat-gradient all-reduce over RCCL when N > 1 + fused Adam,
-reference utils/train_model.py:37-42 with the collective inserted at :41-42), with the all-reduce timed
-separately (`allreduce_ms`).  `--mode train` makes that step the timed metric instead.
+`--mode train` makes the training step the timed metric instead: forward + CE loss + backward on
+the K8 kernels + ONE flat-gradient all-reduce over RCCL when N > 1 + fused Adam (reference
+utils/train_model.py:37-42 with the collective inserted at :41-42), the all-reduce timed separately
+(`allreduce_ms` of the `train` object).
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else runs on
+the device.  `--full` adds, after the timed region, everything else the benchmark measures: the
+per-kernel table and the roofline objects (HIP events around launches), the step with the
+topology cached and with per-step validation, K1 in isolation, the `train` leg of a forward run
+(`--train-steps`), and the CPU baseline with its parity check against the oracle.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32).
 
 Prints ONE JSON line on rank 0.  value = edges aggregated per second over the whole job
 (= sum over ranks of E_rank * n_blocks * steps / max-over-ranks wall time).
@@ -29,6 +37,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -43,6 +52,20 @@ from graphnet_classifier_amd.topology import clear_topology_cache  # noqa: E402
 
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 MFMA peak
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of one run together
+
+
+def dump_outputs(directory, arrays, limit_bytes):
+    """Writes every tensor of ``arrays`` as ``directory/<name>.npy`` in float32.  An array above its share of
+    ``limit_bytes`` keeps evenly spaced rows only (the same rows in every run of the same arguments)."""
+    os.makedirs(directory, exist_ok=True)
+    share = limit_bytes // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            rows = max(1, share // max(1, a.nbytes // a.shape[0]))
+            a = a[np.linspace(0, a.shape[0] - 1, rows).astype(np.int64)]
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def usable_cpus() -> int:
@@ -115,9 +138,17 @@ def main():
                     help="how the step reports an out-of-range edge_index: deferred (default) = the flags the topology build "
                          "computes stay on the device and are read once after the timed region (no host sync inside a step, the "
                          "host enqueues ahead of the GPU); sync = read back in every step, as the module API does by default")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline figure does not need: per-kernel table and "
+                         "roofline objects, the step with the topology cached and with per-step validation, K1 in isolation, "
+                         "the `train` leg of a forward run and the CPU baseline with its parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all): the "
+                         "forward's `output`, or the training step's `parameters` / `gradients` (+ `logits` of an eager step); "
+                         "with N > 1 every rank writes its own, suffixed _rank<r>")
     ap.add_argument("--train-steps", type=int, default=5,
-                    help="training steps of the extra `train` leg after the timed forward region (0 = skip it)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: training steps of the extra `train` leg after the timed forward region (0 = skip it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
     ap.add_argument("--scale", type=float, default=1.0,
                     help="fraction of the workload's graphs (tests / rehearsals only; the contract number is --scale 1)")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
@@ -133,6 +164,8 @@ def main():
                     help="train: the timed step is forward + cross-entropy + backward (HIP K8 kernels) + one flat gradient "
                          "all-reduce (RCCL, world > 1) + fused Adam, graphs batched block-diagonally")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -259,10 +292,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warm-up steps run exactly like timed ones (per-launch HIP events included), so that nothing - event pools,
-    # allocator blocks, lazily loaded code objects - is created for the first time inside the timed region
-    warm_timers = native.KernelTimers()
-    native.set_kernel_timers(warm_timers)
+    # warm-up steps run exactly like timed ones (with --full: per-launch HIP events included), so that nothing - event
+    # pools, allocator blocks, lazily loaded code objects - is created for the first time inside the timed region
+    if a.full:
+        warm_timers = native.KernelTimers()
+        native.set_kernel_timers(warm_timers)
     # device pre-heat (untimed, before the W warm-up steps): clocks and caches settle, and the HIP runtime's
     # event / signal pools grow here instead of inside the K timed steps
     if a.preheat_ms > 0:
@@ -278,21 +312,24 @@ def main():
         torch.cuda.synchronize()
     for _ in range(a.warmup):
         y = step()
-        torch.cuda.Event(enable_timing=True).record()
-    # Inside the timed region HIP events bracket ONLY the dominant fused-MLP launch (roofline_mlp) - an event pair costs
-    # 5-10 us of GPU time per launch, 0.2 ms per c3 step when every launch carries one (kernel trace of the step) - the
-    # full per-kernel table comes from a few eager steps directly after the region.
-    wsum = warm_timers.summary()
-    wmlp = [k for k in wsum if k.startswith("mlp_fused")]
-    dominant = max(wmlp, key=lambda k: wsum[k]["avg_ms"] * wsum[k]["launches"]) if wmlp else None
-    timers = native.KernelTimers(only=dominant or "<no launch is timed inside the region>")
-    all_timers = native.KernelTimers()
-    # every HIP event of the timed region exists before it starts (see KernelTimers.reserve)
-    steps_seen = max(1, a.warmup + (int(n_heat.item()) + 1 if a.preheat_ms > 0 else 0))
-    per_step_launches = warm_timers.num_launches() / steps_seen
-    timers.reserve(int((wsum[dominant]["launches"] / steps_seen if dominant else 0) * (a.steps + 1) * 1.1) + 64)
-    all_timers.reserve(int(per_step_launches * 12 * 1.1) + 64)
-    del warm_timers
+        if a.full:
+            torch.cuda.Event(enable_timing=True).record()
+    timers = all_timers = None  # a plain run records no HIP event at all
+    if a.full:
+        # Inside the timed region HIP events bracket ONLY the dominant fused-MLP launch (roofline_mlp) - an event pair costs
+        # 5-10 us of GPU time per launch, 0.2 ms per c3 step when every launch carries one (kernel trace of the step) - the
+        # full per-kernel table comes from a few eager steps directly after the region.
+        wsum = warm_timers.summary()
+        wmlp = [k for k in wsum if k.startswith("mlp_fused")]
+        dominant = max(wmlp, key=lambda k: wsum[k]["avg_ms"] * wsum[k]["launches"]) if wmlp else None
+        timers = native.KernelTimers(only=dominant or "<no launch is timed inside the region>")
+        all_timers = native.KernelTimers()
+        # every HIP event of the timed region exists before it starts (see KernelTimers.reserve)
+        steps_seen = max(1, a.warmup + (int(n_heat.item()) + 1 if a.preheat_ms > 0 else 0))
+        per_step_launches = warm_timers.num_launches() / steps_seen
+        timers.reserve(int((wsum[dominant]["launches"] / steps_seen if dominant else 0) * (a.steps + 1) * 1.1) + 64)
+        all_timers.reserve(int(per_step_launches * 12 * 1.1) + 64)
+        del warm_timers
     # hipGraph replay of the step (see --graph): captured once, after the warm-up; any failure falls back to eager launches
     graph, graph_out, graph_note = None, None, None
     if a.mode == "forward" and (a.graph == "on" or (a.graph == "auto" and world > 1)):
@@ -317,82 +354,99 @@ def main():
     else:
         native.set_kernel_timers(timers)
     fence()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]  # per-step spread (diagnostic only)
-    for ev in marks:
-        ev.record()  # allocate them now (re-recorded below)
-    allocs0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)  # hipMalloc calls of the caching allocator so far
+    if a.full:
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]  # per-step spread (diagnostic only)
+        for ev in marks:
+            ev.record()  # allocate them now (re-recorded below)
+        allocs0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)  # hipMalloc calls of the caching allocator so far
     coll0 = train_ctx[0].reducer.collectives if train_ctx else 0
     t0 = time.perf_counter()
-    marks[0].record()
-    for k in range(a.steps):
-        y = run_step()
-        marks[k + 1].record()
+    if a.full:
+        marks[0].record()
+        for k in range(a.steps):
+            y = run_step()
+            marks[k + 1].record()
+    else:
+        for _ in range(a.steps):
+            y = run_step()
     fence()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:  # before anything after the region can change what the last timed step left
+        if a.mode == "forward":
+            outputs = {"output": y}
+        else:
+            outputs = {"parameters": train_ctx[0].flat, "gradients": train_ctx[0].grad}
+            if y is not None:  # the eager step returns its logits; a replayed one returns nothing
+                outputs["logits"] = y
+        if world > 1:
+            outputs = {f"{k}_rank{rank}": v for k, v in outputs.items()}
+        dump_outputs(a.dump_outputs, outputs, DUMP_LIMIT_BYTES // world)
     coll_timed = (train_ctx[0].reducer.collectives - coll0) if train_ctx else 0
     ar_timed = list(train_ctx[1]["events"][-a.steps:]) if train_ctx else []
-    # the per-kernel table: the same step, eagerly, with HIP events around every launch, right after the timed region
-    ksteps = min(a.steps, 10)  # steps behind the per-kernel HIP events
-    native.set_kernel_timers(all_timers)
-    for _ in range(ksteps):
-        step()
-    fence()
-    native.set_kernel_timers(timers)
-    topology.check_deferred()  # the out-of-range flags of every timed step, read with one sync (raises IndexError if set)
-    y_fwd = y
-    device_allocs_timed = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0
-    per_step_order = [marks[k].elapsed_time(marks[k + 1]) for k in range(a.steps)]
-    per_step = sorted(per_step_order)
-    # (not part of `value`) the same step with the topology cached: SURVEY 8d asks for the throughput with and
-    # without the CSR build
-    cached_ms = sync_ms = None
-    if a.mode == "forward" and a.validation == "deferred":  # the same step with the flags read back in every step
-        native.set_kernel_timers(None)
-        topology.set_validation("sync")
-        step()
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(a.steps):
+    if a.full:
+        # the per-kernel table: the same step, eagerly, with HIP events around every launch, right after the timed region
+        ksteps = min(a.steps, 10)  # steps behind the per-kernel HIP events
+        native.set_kernel_timers(all_timers)
+        for _ in range(ksteps):
             step()
         fence()
-        sync_ms = (time.perf_counter() - t1) / a.steps * 1e3
-        topology.set_validation("deferred")
         native.set_kernel_timers(timers)
-    if a.mode == "forward":
-        native.set_kernel_timers(None)
-        with torch.no_grad():
-            model(x, pos, ei)
-        fence()
-        t1 = time.perf_counter()
-        for _ in range(a.steps):
+    topology.check_deferred()  # the out-of-range flags of every timed step, read with one sync (raises IndexError if set)
+    y_fwd = y
+    cached_ms = sync_ms = None
+    if a.full:
+        device_allocs_timed = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0
+        per_step_order = [marks[k].elapsed_time(marks[k + 1]) for k in range(a.steps)]
+        per_step = sorted(per_step_order)
+        # (not part of `value`) the same step with the topology cached: SURVEY 8d asks for the throughput with and
+        # without the CSR build
+        if a.mode == "forward" and a.validation == "deferred":  # the same step with the flags read back in every step
+            native.set_kernel_timers(None)
+            topology.set_validation("sync")
+            step()
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(a.steps):
+                step()
+            fence()
+            sync_ms = (time.perf_counter() - t1) / a.steps * 1e3
+            topology.set_validation("deferred")
+            native.set_kernel_timers(timers)
+        if a.mode == "forward":
+            native.set_kernel_timers(None)
             with torch.no_grad():
                 model(x, pos, ei)
-        fence()
-        cached_ms = (time.perf_counter() - t1) / a.steps * 1e3
-        native.set_kernel_timers(timers)
-    # K1 is the kernel north_star grades.  When the step's aggregation ran inside the edge kernel's epilogue
-    # (fused) no K1 launch exists in the timed region: time it in isolation as SURVEY 8d prescribes
-    # (N(0,1) messages [E, D] in CSR order, the batch's own row pointers), HIP events on the launch stream.
-    k1_isolated = False
-    if not any(k.startswith("scatter_sum_csr") for k in all_timers.summary()):
-        from graphnet_classifier_amd.topology import get_topology
-        topo = get_topology(ei, batch.num_nodes, dev)
-        msgs = torch.randn(batch.num_edges, w["width"], device=dev, generator=torch.Generator(device=dev).manual_seed(7))
-        agg_buf = torch.empty(batch.num_nodes, w["width"], device=dev)
+            fence()
+            t1 = time.perf_counter()
+            for _ in range(a.steps):
+                with torch.no_grad():
+                    model(x, pos, ei)
+            fence()
+            cached_ms = (time.perf_counter() - t1) / a.steps * 1e3
+            native.set_kernel_timers(timers)
+        # K1 is the kernel north_star grades.  When the step's aggregation ran inside the edge kernel's epilogue
+        # (fused) no K1 launch exists in the timed region: time it in isolation as SURVEY 8d prescribes
+        # (N(0,1) messages [E, D] in CSR order, the batch's own row pointers), HIP events on the launch stream.
+        k1_isolated = False
+        if not any(k.startswith("scatter_sum_csr") for k in all_timers.summary()):
+            from graphnet_classifier_amd.topology import get_topology
+            topo = get_topology(ei, batch.num_nodes, dev)
+            msgs = torch.randn(batch.num_edges, w["width"], device=dev, generator=torch.Generator(device=dev).manual_seed(7))
+            agg_buf = torch.empty(batch.num_nodes, w["width"], device=dev)
+            native.set_kernel_timers(None)
+            for _ in range(3):
+                native.scatter_sum_csr(msgs, topo.rowptr, None, batch.num_nodes, out=agg_buf)
+            native.set_kernel_timers(all_timers)
+            for _ in range(20):
+                native.scatter_sum_csr(msgs, topo.rowptr, None, batch.num_nodes, out=agg_buf)
+            torch.cuda.synchronize()
+            del msgs, agg_buf
+            k1_isolated = True
         native.set_kernel_timers(None)
-        for _ in range(3):
-            native.scatter_sum_csr(msgs, topo.rowptr, None, batch.num_nodes, out=agg_buf)
-        native.set_kernel_timers(all_timers)
-        for _ in range(20):
-            native.scatter_sum_csr(msgs, topo.rowptr, None, batch.num_nodes, out=agg_buf)
-        torch.cuda.synchronize()
-        del msgs, agg_buf
-        k1_isolated = True
-    native.set_kernel_timers(None)
-    ksum = all_timers.summary()
-    for k, v in timers.summary().items():  # the dominant MLP launch as timed INSIDE the region; K1's isolated launches
-        ksum[k] = v
-    timed_inside = set(timers.summary())
+        ksum = all_timers.summary()
+        for k, v in timers.summary().items():  # the dominant MLP launch as timed INSIDE the region; K1's isolated launches
+            ksum[k] = v
+        timed_inside = set(timers.summary())
 
     # ---- training leg (not part of `value` unless --mode train): BASELINE config c4's "RCCL grad all-reduce" lives here
     t_train, ar_ms, train_steps, collectives = 0.0, 0.0, 0, 0
@@ -403,7 +457,7 @@ def main():
         t_train, train_steps = elapsed, a.steps
         ar_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / max(1, len(evs)) if evs else 0.0
         collectives = coll_timed
-    elif a.train_steps > 0:
+    elif a.full and a.train_steps > 0:
         tstep, flat_params, ar_events = make_train_step()
         for _ in range(2):
             tstep()
@@ -435,21 +489,6 @@ def main():
                                                                                     if a.mode == "train" else ""))
         else:
             wl_name = f"{a.workload}: {w['desc']}" + (f", one such batch per rank x {world}" if world > 1 else "")
-        k1 = ksum.get("scatter_sum_csr_sorted") or ksum.get("scatter_sum_csr_perm")
-        k1_gbps = k1["avg_work"] / (k1["avg_ms"] * 1e-3) / 1e9
-        # HBM bytes per launch from PMC counters (FETCH_SIZE doubled + WRITE_SIZE, separate passes) of an EARLIER profiled
-        # run of this workload, condensed by tools/pmc_summary.py into profiles/pmc_<workload>.json
-        traffic = mlp_traffic = None
-        pmc_file = os.path.join("profiles", f"pmc_{a.workload}.json")
-        if a.scale == 1.0 and world == 1 and os.path.exists(os.path.join(ROOT, pmc_file)):
-            with open(os.path.join(ROOT, pmc_file)) as f:
-                pmc = json.load(f)
-            traffic = pmc["kernels"].get(pmc.get("k1", ""), {}).get("hbm_bytes_per_launch")
-            mlp_traffic = pmc["kernels"].get(pmc.get("dominant_mlp", ""), {}).get("hbm_bytes_per_launch")
-        mlp_names = [k for k in ksum if k.startswith("mlp_fused")]  # none when the timed step was a hipGraph replay
-        mlp_name = max(mlp_names, key=lambda k: ksum[k]["avg_ms"] * ksum[k]["launches"]) if mlp_names else None
-        mlp = ksum[mlp_name] if mlp_name else None
-        mlp_tflops = mlp["avg_work"] / (mlp["avg_ms"] * 1e-3) / 1e12 if mlp else None
         result = {
             "metric": "edges aggregated/sec (GraphNet forward)" if a.mode == "forward" else
                       "edges aggregated/sec (GraphNet+classifier training step: fwd+bwd+allreduce+Adam)",
@@ -462,51 +501,70 @@ def main():
                        "step": "CSR build + GraphNet.forward, inputs resident in HBM" if a.mode == "forward" else
                                "CSR build + forward + CE loss + backward + flat grad all-reduce + Adam, inputs resident in HBM"},
             "graphs_per_sec": tot_graphs * a.steps / elapsed,
-            "roofline": {"kernel": "scatter_sum_csr_vec4 (K1 scatter-sum aggregation, CSR-ordered messages)",
-                         "measured": ("isolated: 20 launches on N(0,1) messages [E, D] with the batch's row pointers, after the "
-                                      "timed region (in the step the aggregation runs in the edge kernel's epilogue)")
-                         if k1_isolated else "every K1 launch of the timed region",
-                         "bound": "hbm", "achieved": k1_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": k1_gbps / HBM_PEAK_GBPS, "traffic": traffic,
-                         "traffic_source": f"{pmc_file}: PMC counters of an earlier profiled run of this workload "
-                                           "(not measured in this run)" if traffic is not None else None,
-                         "avg_launch_ms": k1["avg_ms"], "launches": k1["launches"],
-                         "algorithmic_bytes_per_launch": k1["avg_work"]},
-            "roofline_mlp": None if mlp is None else {"kernel": f"mlp_fused_kernel ({mlp_name}: fused gather+concat+MLP+LayerNorm+residual)",
-                             "bound": "mfma", "achieved": mlp_tflops, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                             "frac": mlp_tflops / MFMA_F32_PEAK_TFLOPS, "avg_launch_ms": mlp["avg_ms"],
-                             "launches": mlp["launches"], "executed_flops_per_launch": mlp["avg_work"],
-                             # HBM side of the same launch: rows in (4 D E), rows out (4 D E), and for the W-split edge launch the
-                             # two gathered projections priced as if every gathered row came from memory (2 x 4 D E; the tables
-                             # are 4 D N each and mostly L2 / MALL resident), three int32 ids per edge and the aggregate (4 D N)
-                             "algorithmic_bytes_per_launch": (4.0 * w["width"] * (4 * batch.num_edges + batch.num_nodes) + 12.0 * batch.num_edges)
-                             if "+2add" in mlp_name else None,
-                             "traffic": mlp_traffic if "+2add" in mlp_name else None,
-                             "traffic_over_algorithmic": (mlp_traffic / (4.0 * w["width"] * (4 * batch.num_edges + batch.num_nodes) + 12.0 * batch.num_edges))
-                             if (mlp_traffic and "+2add" in mlp_name) else None,
-                             "traffic_source": (f"{pmc_file} (earlier profiled run, not this one)" if mlp_traffic else None),
-                             # the reference's concat form of the same launch (W-split removes 2 of the 3 first-Linear blocks)
-                             "reference_form_flops_per_launch": mlp["avg_work"] + (4.0 * batch.num_edges * w["width"] ** 2
-                                                                                    if "+2add" in mlp_name else 0.0)},
-            "step_ms_spread": {"min": per_step[0], "median": per_step[len(per_step) // 2], "max": per_step[-1],
-                               "slowest_step": per_step_order.index(per_step[-1]),
-                               "device_allocs_in_timed_region": device_allocs_timed},
-            "kernel_ms_per_step": {k: v["avg_ms"] * v["launches"] / (a.steps if (k in timed_inside and graph is None) else ksteps)
-                                   for k, v in ksum.items() if not (k1_isolated and k.startswith("scatter_sum_csr"))},
-            "kernel_ms_per_step_source": f"HIP events around every launch of {ksteps} eager steps directly after the timed region "
-                                         "(inside it only the dominant fused-MLP launch carries events)",
         }
-        if mlp_names and a.mode == "forward":  # the whole step against the same roof: every MLP launch's executed FLOPs over the step's wall time
-            step_flops = sum(all_timers.summary()[k]["avg_work"] * all_timers.summary()[k]["launches"] for k in mlp_names
-                             if k in all_timers.summary()) / ksteps
-            result["whole_step"] = {"executed_flops_per_step": step_flops, "achieved": step_flops / (elapsed / a.steps) / 1e12,
-                                    "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                    "frac": step_flops / (elapsed / a.steps) / 1e12 / MFMA_F32_PEAK_TFLOPS,
-                                    "note": "all fused-MLP launches of one step (this rank) / ms_per_step; includes the CSR build and "
-                                            "every non-MFMA launch in the denominator"}
+        if a.full:
+            k1 = ksum.get("scatter_sum_csr_sorted") or ksum.get("scatter_sum_csr_perm")
+            k1_gbps = k1["avg_work"] / (k1["avg_ms"] * 1e-3) / 1e9
+            # HBM bytes per launch from PMC counters (FETCH_SIZE doubled + WRITE_SIZE, separate passes) of an EARLIER profiled
+            # run of this workload, condensed by tools/pmc_summary.py into profiles/pmc_<workload>.json
+            traffic = mlp_traffic = None
+            pmc_file = os.path.join("profiles", f"pmc_{a.workload}.json")
+            if a.scale == 1.0 and world == 1 and os.path.exists(os.path.join(ROOT, pmc_file)):
+                with open(os.path.join(ROOT, pmc_file)) as f:
+                    pmc = json.load(f)
+                traffic = pmc["kernels"].get(pmc.get("k1", ""), {}).get("hbm_bytes_per_launch")
+                mlp_traffic = pmc["kernels"].get(pmc.get("dominant_mlp", ""), {}).get("hbm_bytes_per_launch")
+            mlp_names = [k for k in ksum if k.startswith("mlp_fused")]  # none when the timed step was a hipGraph replay
+            mlp_name = max(mlp_names, key=lambda k: ksum[k]["avg_ms"] * ksum[k]["launches"]) if mlp_names else None
+            mlp = ksum[mlp_name] if mlp_name else None
+            mlp_tflops = mlp["avg_work"] / (mlp["avg_ms"] * 1e-3) / 1e12 if mlp else None
+            result.update({
+                "roofline": {"kernel": "scatter_sum_csr_vec4 (K1 scatter-sum aggregation, CSR-ordered messages)",
+                             "measured": ("isolated: 20 launches on N(0,1) messages [E, D] with the batch's row pointers, after the "
+                                          "timed region (in the step the aggregation runs in the edge kernel's epilogue)")
+                             if k1_isolated else "every K1 launch of the timed region",
+                             "bound": "hbm", "achieved": k1_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": k1_gbps / HBM_PEAK_GBPS, "traffic": traffic,
+                             "traffic_source": f"{pmc_file}: PMC counters of an earlier profiled run of this workload "
+                                               "(not measured in this run)" if traffic is not None else None,
+                             "avg_launch_ms": k1["avg_ms"], "launches": k1["launches"],
+                             "algorithmic_bytes_per_launch": k1["avg_work"]},
+                "roofline_mlp": None if mlp is None else {"kernel": f"mlp_fused_kernel ({mlp_name}: fused gather+concat+MLP+LayerNorm+residual)",
+                                 "bound": "mfma", "achieved": mlp_tflops, "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                 "frac": mlp_tflops / MFMA_F32_PEAK_TFLOPS, "avg_launch_ms": mlp["avg_ms"],
+                                 "launches": mlp["launches"], "executed_flops_per_launch": mlp["avg_work"],
+                                 # HBM side of the same launch: rows in (4 D E), rows out (4 D E), and for the W-split edge launch the
+                                 # two gathered projections priced as if every gathered row came from memory (2 x 4 D E; the tables
+                                 # are 4 D N each and mostly L2 / MALL resident), three int32 ids per edge and the aggregate (4 D N)
+                                 "algorithmic_bytes_per_launch": (4.0 * w["width"] * (4 * batch.num_edges + batch.num_nodes) + 12.0 * batch.num_edges)
+                                 if "+2add" in mlp_name else None,
+                                 "traffic": mlp_traffic if "+2add" in mlp_name else None,
+                                 "traffic_over_algorithmic": (mlp_traffic / (4.0 * w["width"] * (4 * batch.num_edges + batch.num_nodes) + 12.0 * batch.num_edges))
+                                 if (mlp_traffic and "+2add" in mlp_name) else None,
+                                 "traffic_source": (f"{pmc_file} (earlier profiled run, not this one)" if mlp_traffic else None),
+                                 # the reference's concat form of the same launch (W-split removes 2 of the 3 first-Linear blocks)
+                                 "reference_form_flops_per_launch": mlp["avg_work"] + (4.0 * batch.num_edges * w["width"] ** 2
+                                                                                        if "+2add" in mlp_name else 0.0)},
+                "step_ms_spread": {"min": per_step[0], "median": per_step[len(per_step) // 2], "max": per_step[-1],
+                                   "slowest_step": per_step_order.index(per_step[-1]),
+                                   "device_allocs_in_timed_region": device_allocs_timed},
+                "kernel_ms_per_step": {k: v["avg_ms"] * v["launches"] / (a.steps if (k in timed_inside and graph is None) else ksteps)
+                                       for k, v in ksum.items() if not (k1_isolated and k.startswith("scatter_sum_csr"))},
+                "kernel_ms_per_step_source": f"HIP events around every launch of {ksteps} eager steps directly after the timed region "
+                                             "(inside it only the dominant fused-MLP launch carries events)",
+            })
+            if mlp_names and a.mode == "forward":  # the whole step against the same roof: every MLP launch's executed FLOPs over the step's wall time
+                step_flops = sum(all_timers.summary()[k]["avg_work"] * all_timers.summary()[k]["launches"] for k in mlp_names
+                                 if k in all_timers.summary()) / ksteps
+                result["whole_step"] = {"executed_flops_per_step": step_flops, "achieved": step_flops / (elapsed / a.steps) / 1e12,
+                                        "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                        "frac": step_flops / (elapsed / a.steps) / 1e12 / MFMA_F32_PEAK_TFLOPS,
+                                        "note": "all fused-MLP launches of one step (this rank) / ms_per_step; includes the CSR build and "
+                                                "every non-MFMA launch in the denominator"}
         if a.mode == "forward":
-            result["step_launch"] = (f"one hipGraph replay per step (captured after the warm-up; per-kernel HIP events from {ksteps} eager "
-                                     "steps after the timed region)") if graph is not None else \
+            result["step_launch"] = ("one hipGraph replay per step (captured after the warm-up" +
+                                     (f"; per-kernel HIP events from {ksteps} eager steps after the timed region)" if a.full else ")")) \
+                                    if graph is not None else \
                                     ("eager launches from Python" + (f" ({graph_note})" if graph_note else ""))
         if train_steps:
             result["train"] = {
@@ -527,7 +585,7 @@ def main():
         if cached_ms is not None:
             result["topology_cached"] = {"ms_per_step": cached_ms, "value": tot_edges * n_blocks / (cached_ms * 1e-3),
                                          "note": "same step without the CSR build (rank 0's clock)"}
-        if world == 1 and not a.no_cpu_baseline and a.mode == "forward":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.mode == "forward":
             base, (s, yref), sd = cpu_baseline(batch, kw, n_blocks)
             result["cpu_baseline"] = base
             # parity in the same run: the timed sample (a prefix of the batch) AND the first / middle / last graphs, so that

@@ -512,7 +512,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
     for extra, graphs, scaling in (([], 62, "strong"), (["--scaling", "weak"], 2 * 62, "weak"), (["--mode", "train"], 62, "strong")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", "29531", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup",
-               "1", "--scale", "0.01", "--no-cpu-baseline", "--train-steps", "2"] + extra
+               "1", "--scale", "0.01", "--full", "--no-cpu-baseline", "--train-steps", "2"] + extra
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
@@ -528,6 +528,35 @@ def test_bench_two_ranks_rehearsal_on_one_gpu(tmp_path):
         assert tr["step_launch"].startswith("one hipGraph replay"), tr["step_launch"]
         assert tr["collectives_per_step"] == 1.0 and tr["allreduce_ms"] > 0 and tr["value"] > 0
         assert tr["allreduce_bytes"] >= 4 * 60_000
+
+
+def test_bench_plain_run_dumps_the_last_timed_output(G, tmp_path):
+    """A plain bench.py run measures the headline figure only, and --dump-outputs holds the forward of the timed step:
+    the oracle's result for the same seeded batch and weights."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from graphnet_classifier_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.01",
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+    assert not {"roofline", "kernel_ms_per_step", "train", "topology_cached", "cpu_baseline"} & set(d)
+    assert os.listdir(tmp_path) == ["output.npy"]
+    y = np.load(tmp_path / "output.npy")
+    batch, kw = synthetic.make_workload("c3", 0.01)
+    assert y.dtype == np.float32 and y.shape == (batch.num_nodes, 1) == (d["config"]["nodes"], 1)
+    torch.manual_seed(0)  # bench.py's weights
+    sd = {k: v.detach().cpu() for k, v in G.GraphNet(**kw).state_dict().items()}
+    s = batch.slice_graphs(0, 3)
+    with torch.no_grad():
+        ref = O.graphnet_forward(sd, s.x, s.pos, s.edge_index)
+    assert max_abs(torch.from_numpy(y[: s.num_nodes]), ref) < TOL
 
 
 def test_forward_on_cpu_module_fails_loudly(G):

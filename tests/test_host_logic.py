@@ -138,3 +138,14 @@ def test_topology_cache_keys_host_tensors_by_content():
     k2 = TopologyCache._key(ei.clone(), 3, "cuda:0")
     k3 = TopologyCache._key(torch.tensor([[0, 1, 2], [1, 2, 1]]), 3, "cuda:0")
     assert k1 == k2 and k1 != k3 and k1 != TopologyCache._key(ei, 4, "cuda:0")
+
+
+def test_bench_dump_outputs_float32_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per array; an array above its share of the limit keeps evenly spaced
+    rows, first and last included."""
+    import bench
+    big = torch.arange(4000, dtype=torch.float64).reshape(1000, 4)
+    bench.dump_outputs(str(tmp_path), {"big": big, "small": torch.ones(3)}, limit_bytes=8000)
+    b, s = np.load(tmp_path / "big.npy"), np.load(tmp_path / "small.npy")
+    assert b.dtype == s.dtype == np.float32 and s.tolist() == [1, 1, 1]
+    assert b.shape == (250, 4) and b.nbytes <= 4000 and b[0, 0] == 0 and b[-1, 0] == 3996
