@@ -181,6 +181,119 @@ __device__ __forceinline__ void mma_chunk_from_regs(f32x16 (&dst)[TO], const f32
   }
 }
 
+// ---- fp32-accurate products on the bf16 matrix pipe (3-way split) ----------------------------------------------
+// x = x0 + x1 + x2 with x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1) (round to nearest even; the residuals
+// are exact in fp32, |x - x0 - x1 - x2| <= 2^-27 |x|).  With the weights split the same way, the six products with
+// i + j <= 2 (each bf16 x bf16 product is exact in fp32) give W x to about 2^-26 |W| |x| per product: below the
+// rounding of the fp32 accumulation itself.  One v_mfma_f32_32x32x16_bf16 (32 cycles) covers 16 k, where the fp32
+// form needs 8 x v_mfma_f32_32x32x2_f32 (64 cycles each): 6 of them per 16 k are 2.7x fewer matrix cycles.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+constexpr int SLDW = 72;               // bf16 per padded row of a split weight plane (36 dwords = 4 * odd)
+constexpr int SPLANE = 64 * SLDW;      // bf16 per plane: 64 weight rows (two 32-row output tiles)
+constexpr int SCH = 3 * SPLANE / 2;    // floats per resident split chunk (three planes)
+
+struct bf16x8x3 {
+  bf16x8 p0, p1, p2;  // most significant first
+};
+
+__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ bf16x8x3 split3_bf16(f32x8 x) {
+  const bf16x8 a = __builtin_convertvector(x, bf16x8);  // v_cvt_pk_bf16_f32 (RNE)
+  const f32x8 r1 = x - __builtin_convertvector(a, f32x8);
+  const bf16x8 b = __builtin_convertvector(r1, bf16x8);
+  const f32x8 r2 = r1 - __builtin_convertvector(b, f32x8);
+  return {a, b, __builtin_convertvector(r2, bf16x8)};
+}
+
+// K-group layout of a split chunk: slot j (0..7) of lane half h in K-group kg (16 k) is feature
+//   16 kg + (j & 3) + 8 (j >> 2) + 4 h,
+// which is what accumulator registers 8 (kg & 1) + j of tile kg >> 1 hold on lane half h (feat_of), so the previous
+// layer's accumulators are the next layer's B operand as they stand; a staged fp32 row gives the same 8 features with
+// two 16-B reads.  The permutation is folded into the weight planes here, once per launch.
+// Workgroup-wide (NT >= 512): plane q row n = split q of W[n][kbase + feature] for n < 64, zero outside the matrix.
+template <int NT>
+__device__ __forceinline__ void stage_weights_split(__bf16* wsp, const float* __restrict__ W, int ldw, int out_dim, int kbase,
+                                                    int klimit, bool vec_ok, int tid) {
+  static_assert(NT >= 512, "one pass: 64 rows x 8 groups of 8 features");
+  if (tid < 512) {
+    const int n = tid >> 3, kg = (tid >> 1) & 3, hh = tid & 1;
+    const int c0 = kbase + 16 * kg + 4 * hh;
+    f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+    if (n < out_dim) {
+      lo = load4_guarded(W + (int64_t)n * ldw + c0, c0, klimit, vec_ok);
+      hi = load4_guarded(W + (int64_t)n * ldw + c0 + 8, c0 + 8, klimit, vec_ok);
+    }
+    const bf16x8x3 s = split3_bf16(f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w});
+    __bf16* p = wsp + n * SLDW + 16 * kg + 8 * hh;
+    *reinterpret_cast<bf16x8*>(p) = s.p0;
+    *reinterpret_cast<bf16x8*>(p + SPLANE) = s.p1;
+    *reinterpret_cast<bf16x8*>(p + 2 * SPLANE) = s.p2;
+  }
+}
+
+// acc[t] += W[32t + i][K-group kg] * x for one K-group: 6 MFMAs per output tile, small products first, the tiles'
+// chains interleaved.
+template <int TO>
+__device__ __forceinline__ void mma_group_split(f32x16 (&acc)[TO], const bf16x8x3& x, const __bf16* wsp, int kg, int i, int h) {
+  bf16x8 w0[TO], w1[TO], w2[TO];
+#pragma unroll
+  for (int t = 0; t < TO; ++t) {
+    const __bf16* p = wsp + (32 * t + i) * SLDW + 16 * kg + 8 * h;
+    w0[t] = *reinterpret_cast<const bf16x8*>(p);
+    w1[t] = *reinterpret_cast<const bf16x8*>(p + SPLANE);
+    w2[t] = *reinterpret_cast<const bf16x8*>(p + 2 * SPLANE);
+  }
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w0[t], x.p2, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w1[t], x.p1, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w2[t], x.p0, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w0[t], x.p1, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w1[t], x.p0, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w0[t], x.p0, acc[t]);
+}
+
+// the 8 features of K-group kg of row i from the wave's fp32 LDS tile, split
+__device__ __forceinline__ bf16x8x3 split_lds_group(const float* abuf, int kg, int i, int h) {
+  const f32x4 lo = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * kg + 4 * h);
+  const f32x4 hi = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * kg + 8 + 4 * h);
+  return split3_bf16(f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w});
+}
+
+// split form of mma_chunk_from_lds: kc16 K-groups of the staged tile (columns beyond the segment width are zeros)
+template <int T>
+__device__ __forceinline__ void mma_chunk_from_lds_split(f32x16 (&acc)[T], const float* abuf, const __bf16* wsp, int kc16,
+                                                         int i, int h) {
+#pragma unroll
+  for (int kg = 0; kg < 4; ++kg)
+    if (kg < kc16) mma_group_split<T>(acc, split_lds_group(abuf, kg, i, h), wsp, kg, i, h);
+}
+
+// split form of mma_chunk_from_regs (one 64-column chunk, the input being the previous layer's accumulators)
+template <int TI, int TO>
+__device__ __forceinline__ void mma_chunk_from_regs_split(f32x16 (&dst)[TO], const f32x16 (&src)[TI], const __bf16* wsp,
+                                                          int in_dim, int i, int h) {
+#pragma unroll
+  for (int kg = 0; kg < 4; ++kg) {
+    const int ts = kg >> 1;
+    if (ts < TI && kg * 16 < in_dim) {
+      const f32x16& s = src[ts < TI ? ts : 0];
+      const int r0 = 8 * (kg & 1);
+      const f32x8 x = {s[r0 + 0], s[r0 + 1], s[r0 + 2], s[r0 + 3], s[r0 + 4], s[r0 + 5], s[r0 + 6], s[r0 + 7]};
+      mma_group_split<TO>(dst, split3_bf16(x), wsp, kg, i, h);
+    }
+  }
+}
+
 // x(lane) + x(lane ^ 32) in every lane, on the VALU: gfx950's v_permlane32_swap exchanges the upper half of
 // one register with the lower half of another (no LDS round trip like ds_bpermute / __shfl_xor).
 __device__ __forceinline__ float add_halves(float x) {

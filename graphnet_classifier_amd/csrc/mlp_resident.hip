@@ -91,12 +91,23 @@ constexpr int RNT = RWAVES * 64;
 // d.weight[1] / d.save_act[0] (a description built by gnc_mlp_dual_projection_f32, never by a caller).  No bias, no LayerNorm.
 // EF = 2: the only segment is a contiguous [rows, 3] table (the reference's node features, models/GNN.py:305): one 12-B load
 // per row and tile (lane & 31 = tile row) where it lies - no zero-padded [rows, 4] copy in front of the launch.
-template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0, bool DUAL = false>
+// SPLIT (chosen by the launcher from the launch's shape, never by another template flag): which Linears run on the bf16
+// matrix pipe in the fp32-accurate 3-way split form (mlp_device.h) - 1: all of them (the W-split edge processor: one
+// row-ordered MATMUL step, two ADD segments, residual in registers), 2: all but the first (the encoders: first Linear
+// K <= 4, one fp32 MFMA k-group).  Their weights are resident as three bf16 planes (SCH floats per chunk, after the
+// fp32 chunks).  0: every Linear in fp32 MFMA (GNC_MLP_F32_EXACT=1 keeps every launch there).
+template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0, bool DUAL = false,
+          int SPLIT = 0>
 __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t d, const int num_wtiles,
                                                            const int total_chunks) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int WT = HT > OT ? HT : OT;
   constexpr int CH = WT * 32 * LDSW;  // floats per resident weight chunk
+  static_assert(SPLIT == 0 || (WT == 2 && NMM == 1 && !DUAL && (SPLIT == 1 || NADD == 0)), "split shapes");
+  // split instances: chunks [0, nf32) fp32, the rest split
+  constexpr int nf32 = SPLIT == 1 ? 0 : NMM;
+  __bf16* const wsp = reinterpret_cast<__bf16*>(lds + nf32 * CH);
+  auto wsplit = [&](int chunk) -> const __bf16* { return wsp + (chunk - nf32) * 3 * SPLANE; };
   constexpr int PSTRIDE = WT * 32;
   constexpr int NS = NMM + NADD;
   const int tid = threadIdx.x;
@@ -110,12 +121,24 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   const int out_dim = FULL ? KC : d.out_dim[L - 1];
   const int rows = (int)d.rows;
   float* wres = lds;
-  float* pbuf = lds + total_chunks * CH;
+  float* pbuf = SPLIT == 0 ? lds + total_chunks * CH : lds + nf32 * CH + (total_chunks - nf32) * SCH;
   float* abuf = pbuf + (L + 2) * PSTRIDE + wave * RPW * LDSW;
 
   // ---- one-time: parameters and every weight chunk into LDS ---------------------------------
   stage_params<RNT>(pbuf, d, PSTRIDE, tid);
-  {
+  if constexpr (SPLIT != 0) {  // split chunks: three bf16 planes each (mlp_device.h)
+    const int ldw0 = ldw_of(d, 0);
+    const bool w0v = (ldw0 % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[0]) & 15u) == 0) && (d.seg[0].wcol % 4 == 0);
+    if constexpr (SPLIT == 1)
+      stage_weights_split<RNT>(wsp, d.weight[0], ldw0, d.out_dim[0], d.seg[0].wcol, d.seg[0].wcol + d.seg[0].width, w0v, tid);
+    else
+      stage_weights<WT * 32, RNT>(wres, d.weight[0], ldw0, d.out_dim[0], d.seg[0].wcol, d.seg[0].wcol + d.seg[0].width, 16, w0v, tid);
+    for (int l = 1; l < L; ++l) {
+      const int ldw = ldw_of(d, l);
+      const bool wv = (ldw % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[l]) & 15u) == 0);
+      stage_weights_split<RNT>(wsp + (NMM + l - 1 - nf32) * 3 * SPLANE, d.weight[l], ldw, d.out_dim[l], 0, d.in_dim[l], wv, tid);
+    }
+  } else {
     int chunk = 0;
     const int ldw0 = ldw_of(d, 0);
     const bool w0v = (ldw0 % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[0]) & 15u) == 0);
@@ -315,6 +338,23 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
             const uint32_t cola = (uint32_t)(c4 * 4 < sa.ld ? c4 * 16 : 0), colb = (uint32_t)(c4 * 4 < sb.ld ? c4 * 16 : 0);
             const int rba = (int)(offs[NMM] * (uint32_t)(sa.ld * 4)), rbb = (int)(offs[NMM + 1] * (uint32_t)(sb.ld * 4));
             int na = __shfl(rba, rs, 64), nb = __shfl(rbb, rs, 64);
+            if constexpr (SPLIT == 1) {  // two pieces of each table per 16-k group
+              const __bf16* wch = wsplit(s);
+#pragma unroll
+              for (int kg = 0; kg < 4; ++kg) {
+                mma_group_split<HT>(hid, split_lds_group(abuf, kg, i, h), wch, kg, i, h);
+#pragma unroll
+                for (int g = 2 * kg; g < 2 * kg + 2; ++g) {
+                  const uint32_t oa = (uint32_t)na + cola, ob = (uint32_t)nb + colb;
+                  if (g + 1 < 8) {
+                    na = __shfl(rba, (g + 1) * 4 + rs, 64);
+                    nb = __shfl(rbb, (g + 1) * 4 + rs, 64);
+                  }
+                  addA[g] = window_load(wa, oa);
+                  addB[g] = window_load(wb, ob);
+                }
+              }
+            } else {
             const float* wch = wres + s * CH;
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
@@ -334,6 +374,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
               }
               addA[g] = window_load(wa, oa);
               addB[g] = window_load(wb, ob);
+            }
             }
             offs[NMM] = row_offset(nwt, sv[NMM]);
             offs[NMM + 1] = row_offset(nwt, sv[NMM + 1]);
@@ -355,7 +396,10 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
         }
       }
       PROBE(7);  // issue of the next rows' loads
-      if (!interleaved) mma_chunk_from_lds<HT>(hid, abuf, wres + s * CH, (sv[s].width + 7) >> 3, i, h);
+      if (!interleaved) {
+        if constexpr (SPLIT == 1) mma_chunk_from_lds_split<HT>(hid, abuf, wsplit(s), (sv[s].width + 15) >> 4, i, h);
+        else mma_chunk_from_lds<HT>(hid, abuf, wres + s * CH, (sv[s].width + 7) >> 3, i, h);
+      }
       if constexpr (RESREG) if (s == NMM - 1) {
 #pragma unroll
         for (int t = 0; t < HT; ++t)
@@ -409,7 +453,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       for (int l = 1; l < L - 1; ++l) {
         f32x16 nxt[HT];
         init_bias<HT>(nxt, pbuf + l * PSTRIDE, h);
-        mma_chunk_from_regs<HT, HT>(nxt, hid, wres + (NMM + l - 1) * CH, 0, FULL ? KC : d.in_dim[l], i, h);
+        if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, HT>(nxt, hid, wsplit(NMM + l - 1), FULL ? KC : d.in_dim[l], i, h);
+        else mma_chunk_from_regs<HT, HT>(nxt, hid, wres + (NMM + l - 1) * CH, 0, FULL ? KC : d.in_dim[l], i, h);
         relu_tiles<HT>(nxt);
         if constexpr (SAVE) save_rows(nxt, l);
 #pragma unroll
@@ -419,7 +464,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       // ---------------------------------------------------------------- last Linear, LayerNorm
       f32x16 o[OT];
       init_bias<OT>(o, pbuf + (L - 1) * PSTRIDE, h);
-      mma_chunk_from_regs<HT, OT>(o, hid, wres + (NMM + L - 2) * CH, 0, FULL ? KC : d.in_dim[L - 1], i, h);
+      if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, OT>(o, hid, wsplit(NMM + L - 2), FULL ? KC : d.in_dim[L - 1], i, h);
+      else mma_chunk_from_regs<HT, OT>(o, hid, wres + (NMM + L - 2) * CH, 0, FULL ? KC : d.in_dim[L - 1], i, h);
       PROBE(4);  // last Linear
       if (FULL || d.ln_gamma) layer_norm_tiles<OT>(o, pbuf + L * PSTRIDE, pbuf + (L + 1) * PSTRIDE, out_dim, d.ln_eps, h);
       if constexpr (RESREG) {
@@ -557,14 +603,14 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   PROBE_END();
 }
 
-template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0, bool DUAL = false>
+template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0, bool DUAL = false,
+          int SPLIT = 0>
 int launch(const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t stream) {
+  void (*const kernel)(const gnc_mlp_desc_t, const int, const int) = &mlp_resident_kernel<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, DUAL, SPLIT>;
   static bool attr_set = false;
   if (!attr_set) {
-    int rc = gnc::check_hip(
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_resident_kernel<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, DUAL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-        "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    int rc = gnc::check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+                            "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     if (rc) return rc;
     attr_set = true;
   }
@@ -572,9 +618,21 @@ int launch(const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t s
   int64_t grid = gnc::ceil_div(num_wtiles, RWAVES);
   if (grid > gnc::num_cu()) grid = gnc::num_cu();  // one persistent workgroup per CU
   if constexpr (AGG) grid = gnc::num_cu();        // agg_fix has two entries for every wave of the full grid
-  mlp_resident_kernel<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, DUAL>
-      <<<dim3((unsigned)grid), dim3(RNT), smem, stream>>>(d, (int)num_wtiles, total_chunks);
+  kernel<<<dim3((unsigned)grid), dim3(RNT), smem, stream>>>(d, (int)num_wtiles, total_chunks);
   return gnc::check_launch("mlp_resident_kernel");
+}
+
+// the launch in its split class (see SPLIT at mlp_resident_kernel): 1 = the W-split edge processor, 2 = the encoders
+template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0>
+int launch_cls(int split, const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t stream) {
+  if constexpr (HT == 2 && OT == 2 && NMM == 1 && NADD == 2 && RESREG) {
+    if (split == 1) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 1>(d, total_chunks, smem, stream);
+  }
+  if constexpr (HT == 2 && OT == 2 && NMM == 1 && NADD == 0 && !RESREG && !AGG && !FULL) {
+    if (split == 2) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 2>(d, total_chunks, smem, stream);
+  }
+  if (split) return GNC_ERR_UNSUPPORTED;  // a class without its instance: never taken (the launcher's tests below)
+  return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF>(d, total_chunks, smem, stream);
 }
 
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -668,12 +726,31 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
   }
 
   const int total_chunks = nmm + (L - 1);
-  const size_t floats = (size_t)total_chunks * T * 32 * LDSW + (size_t)(L + 2) * T * 32 + (size_t)RWAVES * RPW * LDSW;
-  const size_t smem = floats * sizeof(float);
-  if (smem > 160 * 1024) return GNC_OK;
-
   const gnc_mlp_segment_t& lm = d.seg[nmm - 1];
   const bool resreg = d.residual && d.residual == lm.ptr && !lm.index && lm.ld == d.ld_residual && lm.width == od;
+
+  // Split class (bf16 matrix pipe, fp32-accurate 3-way split; mlp_resident_kernel): decided by the shape alone, so that
+  // every instance of a shape (AGG / SAVE / FULL / EF variants, fused or separate K1) computes the same bits.
+  //   1: the W-split edge processor - one MATMUL segment, two ADD segments, residual = the MATMUL rows;
+  //   2: the encoders - first Linear K <= 4 (computed K6 rows, the [rows, 3] node features, or a [rows, <= 4] table),
+  //      hidden width 64.
+  // Everything else (node processors, projections, decoder, 64-wide plain shapes) stays in fp32 MFMA.
+  static const bool f32_exact = getenv("GNC_MLP_F32_EXACT") != nullptr;  // A/B switch: the fp32 path everywhere
+  int split = 0;
+  if (!f32_exact && T == 2 && L >= 2 && !narrow_out && nmm == 1) {
+    bool hidden64 = true;
+    for (int l = 0; l < L - 1; ++l) hidden64 = hidden64 && d.out_dim[l] == KC;
+    if (nadd == 2 && resreg) split = 1;
+    else if (nadd == 0 && !resreg && hidden64 && d.seg[0].width <= 4) split = 2;
+  }
+  auto smem_of = [&](int nsplit) {  // bytes of LDS: fp32 chunks, split chunks (1.6x), parameters, the waves' row tiles
+    return ((size_t)(total_chunks - nsplit) * T * 32 * LDSW + (size_t)nsplit * SCH + (size_t)(L + 2) * T * 32 +
+            (size_t)RWAVES * RPW * LDSW) * sizeof(float);
+  };
+  // c3: 150.3 KB for the edge processor (3 split chunks), 140.3 KB for a 3-Linear encoder; deeper stacks keep fp32
+  if (split && smem_of(split == 1 ? total_chunks : total_chunks - nmm) > 160 * 1024) split = 0;
+  const size_t smem = smem_of(split == 1 ? total_chunks : (split == 2 ? total_chunks - nmm : 0));
+  if (smem > 160 * 1024) return GNC_OK;
 
   if (narrow_out && (resreg || nadd || nmm != 1)) return GNC_OK;  // out width <= 32 (the decoder): plain shapes only
   // every width exactly 64, three Linear layers, LayerNorm, whole 16-B output rows: the FULL instances (c3's edge processor)
@@ -684,12 +761,12 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
   if (d.ef_pos) {
     *launched = true;
     if (probe_only) return GNC_OK;
-    return launch<2, 2, 1, 0, false, false, false, false, 1>(d, total_chunks, smem, stream);
+    return launch_cls<2, 2, 1, 0, false, false, false, false, 1>(split, d, total_chunks, smem, stream);
   }
   if (n3) {
     *launched = true;
     if (probe_only) return GNC_OK;
-    return launch<2, 2, 1, 0, false, false, false, false, 2>(d, total_chunks, smem, stream);
+    return launch_cls<2, 2, 1, 0, false, false, false, false, 2>(split, d, total_chunks, smem, stream);
   }
   if (d.save_act[0]) {
     // training forward: SAVE instances exist for the shapes whose K8 kernel reads the saved tensors (the fused data +
@@ -703,18 +780,18 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
     if (nmm == 2)
       return resreg ? launch<2, 2, 2, 0, true, false, true>(d, total_chunks, smem, stream)
                     : launch<2, 2, 2, 0, false, false, true>(d, total_chunks, smem, stream);
-    if (d.agg_out) return full64 ? launch<2, 2, 1, 2, true, true, true, true>(d, total_chunks, smem, stream)
-                                 : launch<2, 2, 1, 2, true, true, true>(d, total_chunks, smem, stream);
-    if (nadd == 2) return launch<2, 2, 1, 2, true, false, true>(d, total_chunks, smem, stream);
+    if (d.agg_out) return full64 ? launch_cls<2, 2, 1, 2, true, true, true, true>(split, d, total_chunks, smem, stream)
+                                 : launch_cls<2, 2, 1, 2, true, true, true>(split, d, total_chunks, smem, stream);
+    if (nadd == 2) return launch_cls<2, 2, 1, 2, true, false, true>(split, d, total_chunks, smem, stream);
     return resreg ? launch<2, 2, 1, 0, true, false, true>(d, total_chunks, smem, stream)
-                  : launch<2, 2, 1, 0, false, false, true>(d, total_chunks, smem, stream);
+                  : launch_cls<2, 2, 1, 0, false, false, true>(split, d, total_chunks, smem, stream);
   }
   if (d.agg_out) {  // fused aggregation epilogue: the W-split edge processor shape only
     if (!(nadd == 2 && nmm == 1 && resreg && !narrow_out && d.agg_index && d.agg_fix && d.ld_agg >= od)) return GNC_OK;
     *launched = true;
     if (probe_only) return GNC_OK;
-    if (T == 2 && full64) return launch<2, 2, 1, 2, true, true, false, true>(d, total_chunks, smem, stream);
-    return T == 2 ? launch<2, 2, 1, 2, true, true>(d, total_chunks, smem, stream)
+    if (T == 2 && full64) return launch_cls<2, 2, 1, 2, true, true, false, true>(split, d, total_chunks, smem, stream);
+    return T == 2 ? launch_cls<2, 2, 1, 2, true, true>(split, d, total_chunks, smem, stream)
                   : launch<1, 1, 1, 2, true, true>(d, total_chunks, smem, stream);
   }
   if (probe_only) {
@@ -733,8 +810,11 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
                   : launch<1, 1, 1, 0, false>(d, total_chunks, smem, stream);
   }
   if (T == 2) {
-    if (nadd == 2) GNC_RES(2, 1, 2);
-    if (nmm == 1) GNC_RES(2, 1, 0);
+    *launched = true;
+    if (nadd == 2) return resreg ? launch_cls<2, 2, 1, 2, true>(split, d, total_chunks, smem, stream)
+                                 : launch<2, 2, 1, 2, false>(d, total_chunks, smem, stream);
+    if (nmm == 1) return resreg ? launch<2, 2, 1, 0, true>(d, total_chunks, smem, stream)
+                                : launch_cls<2, 2, 1, 0, false>(split, d, total_chunks, smem, stream);
     if (nmm == 2) GNC_RES(2, 2, 0);
     GNC_RES(2, 3, 0);
   }
