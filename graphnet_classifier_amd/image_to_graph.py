@@ -3,7 +3,8 @@
 Same function names and arguments as the reference
 (``image_to_graph_optimized.py:7,42,50``, ``image_to_graph_patch.py:6``, ``image_to_graph_superpixel.py:8``);
 the image is decoded / resized on the host with PIL exactly as the reference does, then everything else
-(node features, positions, edges) is produced in HBM by the kernels of ``csrc/graph_build.hip``.  Results
+(SLIC segmentation, node features, positions, edges) is produced in HBM by the kernels of ``csrc/superpixel.hip``
+and ``csrc/graph_build.hip``.  Results
 are the tensors ``utils/dataloader.py:49-51`` would build: ``x`` float32, ``pos`` float32, ``edge_index``
 int64, already on the GPU, in the reference's node and edge order.
 """
@@ -95,12 +96,19 @@ def image_to_graph_patch(image_or_path, resize_value: int = 128, patch_size: int
 def superpixel_graph_from_labels(img_u8: np.ndarray, segments: np.ndarray):
     """Everything of superpixel.py after the SLIC call (:33-71) for a given label image: per-segment mean
     colour (of img/255) and centroid, region adjacency, edges [i,j],[j,i] in lexicographic order."""
-    lib = native.load_library()
     img = _to_device_u8(img_u8)
     H, W, C = img.shape
     if C != 3 or segments.shape != (H, W):
         raise ValueError("expected an RGB image and a label image of the same size")
     labels = torch.from_numpy(np.ascontiguousarray(segments.astype(np.int32))).to(img.device)
+    return _superpixel_graph_from_device_labels(img, labels)
+
+
+def _superpixel_graph_from_device_labels(img_u8, labels: torch.Tensor):
+    lib = native.load_library()
+    img = img_u8 if isinstance(img_u8, torch.Tensor) else _to_device_u8(img_u8)
+    H, W, C = img.shape
+    labels = labels.to(device=img.device, dtype=torch.int32).contiguous()
     n = H * W
     x = torch.empty(n, 3, dtype=torch.float32, device=img.device)
     pos = torch.empty(n, 2, dtype=torch.float32, device=img.device)
@@ -120,15 +128,50 @@ def superpixel_graph_from_labels(img_u8: np.ndarray, segments: np.ndarray):
     return x[:s], pos[:s], ei[:, :e]
 
 
-def image_to_graph_superpixel(image_or_path, resize_value: int = 128, n_segments: int = 100, compactness: int = 10):
-    """superpixel.py:8-73.  The SLIC segmentation itself is scikit-image's (superpixel.py:31) and stays on the
-    host; it is imported lazily because that package is optional."""
-    try:
-        from skimage.segmentation import slic
-        from skimage.util import img_as_float
-    except ImportError as exc:  # same dependency the reference has
-        raise ImportError("image_to_graph_superpixel needs scikit-image for SLIC (reference superpixel.py:4-5); "
-                          "use superpixel_graph_from_labels with your own label image") from exc
-    img = _load_resized(image_or_path, resize_value)
-    segments = slic(img_as_float(img), n_segments=n_segments, compactness=compactness, start_label=0)
-    return superpixel_graph_from_labels(img, segments)
+def slic(image_u8, n_segments: int = 100, compactness: float = 10, max_iter: int = 10,
+         enforce_connectivity: bool = True, min_size_factor: float = 0.5, max_size_factor: float = 3,
+         start_label: int = 0, return_counts: bool = False):
+    """scikit-image 0.18.3 ``slic(img_as_float(img), ...)`` on the GPU (csrc/superpixel.hip) for uint8 RGB images
+    ``[H, W, 3]`` or a batch ``[B, H, W, 3]`` (NumPy array or tensor).  Returns int32 labels ``[H, W]`` / ``[B, H, W]``
+    on the device, and with ``return_counts`` also the int32 ``[B]`` number of labels per image.  sigma = 0, no mask,
+    unit spacing, Lab conversion, SLIC (not SLIC-zero): the options the reference uses (superpixel.py:31)."""
+    lib = native.load_library()
+    img = image_u8 if isinstance(image_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image_u8))
+    if img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError("slic: expected a uint8 RGB image [H, W, 3] or batch [B, H, W, 3]")
+    single = img.dim() == 3
+    img = (img.unsqueeze(0) if single else img).to(_device()).contiguous()
+    B, H, W, _ = img.shape
+    if B == 0 or H == 0 or W == 0:
+        raise ValueError("slic: empty image or batch")
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=img.device)
+    counts = torch.empty(B, dtype=torch.int32, device=img.device)
+    with torch.cuda.device(img.device):
+        nbytes = lib.gnc_slic_workspace_bytes(B, H, W, int(n_segments))
+        if nbytes == 0:
+            raise NotImplementedError(f"slic: {H} x {W} with n_segments={n_segments} is outside the supported set")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        native._check(lib.gnc_slic_rgb_u8(img.data_ptr(), B, H, W, int(n_segments), float(compactness), int(max_iter),
+                                          int(bool(enforce_connectivity)), float(min_size_factor),
+                                          float(max_size_factor), int(start_label), labels.data_ptr(),
+                                          counts.data_ptr(), ws.data_ptr(), nbytes,
+                                          torch.cuda.current_stream(img.device).cuda_stream), "gnc_slic_rgb_u8")
+    if single:
+        labels, counts = labels[0], counts[:1]
+    return (labels, counts) if return_counts else labels
+
+
+def superpixel_graph_from_array(img_u8: np.ndarray, n_segments: int = 100, compactness: float = 10):
+    """superpixel.py:29-71 for an already resized uint8 RGB array: device SLIC, then the region graph."""
+    labels = slic(img_u8, n_segments=n_segments, compactness=compactness, start_label=0)
+    return _superpixel_graph_from_device_labels(img_u8, labels)
+
+
+def image_to_graph_superpixel(image_or_path, resize_value: int = 128, n_segments: int = 100, compactness: int = 10,
+                              **slic_options):
+    """superpixel.py:8-73, SLIC included, on the device.  Options of scikit-image's ``slic`` that the reference never
+    passes (mask, sigma, spacing, slic_zero, ...) are not implemented and raise."""
+    if slic_options:
+        raise NotImplementedError(f"image_to_graph_superpixel: SLIC options {sorted(slic_options)} are not implemented "
+                                  "(the reference passes only n_segments and compactness)")
+    return superpixel_graph_from_array(_load_resized(image_or_path, resize_value), n_segments, compactness)

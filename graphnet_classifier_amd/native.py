@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 GNC_MAX_SEGMENTS = 4
 GNC_MAX_LINEAR = 8
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 ACTIVATIONS = {  # nn.<Name> accepted by the reference's MLP(activation=...) (models/MLP.py:21)
     "ReLU": 0, "Identity": 1, "Tanh": 2, "Sigmoid": 3, "SiLU": 4, "GELU": 5, "LeakyReLU": 6, "ELU": 7,
@@ -85,6 +85,9 @@ _SIGNATURES = {
     "gnc_rag_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "gnc_rag_build": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
+    "gnc_slic_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "gnc_slic_rgb_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32, c_int32, c_double, c_double,
+                                  c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gnc_colsum_pair_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
     "gnc_reduce_partials_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnc_activation_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_float, c_void_p, c_int64, c_void_p]),

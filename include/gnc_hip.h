@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNC_ABI_VERSION 19
+#define GNC_ABI_VERSION 20
 
 enum {
   GNC_OK = 0,
@@ -476,6 +476,23 @@ size_t gnc_rag_workspace_bytes(int32_t H, int32_t W);
 int gnc_rag_build(const int32_t* labels, const uint8_t* img, int32_t H, int32_t W, float* x, float* pos,
                   int64_t* edge_index, int64_t ld_edges, int32_t* counts, void* workspace, size_t workspace_bytes,
                   void* stream);
+
+/* ---- SLIC superpixels on the device (ABI 20; image_to_graph_superpixel.py:31) ------------------
+ * gnc_slic_rgb_u8      scikit-image 0.18.3 `slic(img_as_float(img), n_segments, compactness, max_iter,
+ *                      enforce_connectivity, min_size_factor, max_size_factor, start_label)` with sigma = 0, no
+ *                      mask, unit spacing, slic_zero off and Lab conversion, for B images `img` [B, H, W, 3] uint8
+ *                      at once.  `labels` [B, H, W] int32; counts[b] = labels handed out (connectivity on:
+ *                      new labels of the connectivity pass; off: number of grid centres).  Workspace of
+ *                      gnc_slic_workspace_bytes(B, H, W, n_segments) bytes (0 = shape not supported).
+ *                      GNC_ERR_UNSUPPORTED for H or W > 4096, n_segments < 1, compactness <= 0, max_iter outside
+ *                      1..1000, start_label other than 0 or 1, negative size factors.  Stream-ordered, no host
+ *                      synchronisation.
+ */
+size_t gnc_slic_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t n_segments);
+int gnc_slic_rgb_u8(const uint8_t* img, int32_t B, int32_t H, int32_t W, int32_t n_segments, double compactness,
+                    int32_t max_iter, int32_t enforce_connectivity, double min_size_factor, double max_size_factor,
+                    int32_t start_label, int32_t* labels, int32_t* counts, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 /* ---- fused Adam over flat buffers -------------------------------
  * Replaces `optimizer.step()` of utils/train_model.py:42 for `optim.Adam(model.parameters(), lr=1e-3)` (:9):
