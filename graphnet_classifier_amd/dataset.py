@@ -1,0 +1,160 @@
+"""Image-folder training data without torchvision: the reference's ``utils/dataloader.py`` (``OptimizedDatasetLoader``
+over ``torchvision.datasets.ImageFolder``) on the device path.
+
+``GraphImageFolder(dataset_path, resize_value, diagonals, method, n_segments, patch_size, use_cache)`` finds images
+by torchvision's ``ImageFolder`` rules and yields ``((x, pos, edge_index), label)`` as the reference's
+``__getitem__`` does, with the tensors already on the GPU.  It is a ``torch.utils.data.Dataset``, so ``main.py``'s
+``DataLoader(ds, batch_size=1, shuffle=True, collate_fn=lambda b: b[0])`` works unchanged.
+
+``GraphImageFolder.loader()`` is the fast way through an epoch: the same samples in the same order as that
+``DataLoader`` (and the same draws from the global RNG), with decoding on a host thread pool and the resize and the
+graph builds of a chunk of images run as batched launches (``image_to_graph.graphs_from_images``).
+"""
+from __future__ import annotations
+
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+from torch.utils.data import Dataset
+
+from . import image_to_graph as I2G
+
+# torchvision.datasets.folder.IMG_EXTENSIONS
+IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
+MAX_WORKERS = 16
+
+
+def find_classes(directory: str):
+    """Sorted sub-directory names and their indices (torchvision ``find_classes``)."""
+    classes = sorted(entry.name for entry in os.scandir(directory) if entry.is_dir())
+    if not classes:
+        raise FileNotFoundError(f"Couldn't find any class folder in {directory}.")
+    return classes, {name: i for i, name in enumerate(classes)}
+
+
+def make_dataset(directory: str, class_to_idx, extensions=IMG_EXTENSIONS):
+    """``(path, class_index)`` pairs in torchvision ``make_dataset`` order: classes sorted, then
+    ``sorted(os.walk(class_dir, followlinks=True))`` with sorted file names, extensions matched case-insensitively.
+    A class without images raises ``FileNotFoundError``."""
+    directory = os.path.expanduser(directory)
+    instances, empty = [], []
+    for target_class in sorted(class_to_idx):
+        class_index = class_to_idx[target_class]
+        target_dir = os.path.join(directory, target_class)
+        if not os.path.isdir(target_dir):
+            continue
+        found = False
+        for root, _, fnames in sorted(os.walk(target_dir, followlinks=True)):
+            for fname in sorted(fnames):
+                path = os.path.join(root, fname)
+                if path.lower().endswith(extensions):
+                    instances.append((path, class_index))
+                    found = True
+        if not found:
+            empty.append(target_class)
+    if empty:
+        raise FileNotFoundError(f"Found no valid file for the classes {', '.join(sorted(empty))}. "
+                                f"Supported extensions are: {', '.join(extensions)}")
+    return instances
+
+
+def load_rgb(path: str) -> np.ndarray:
+    """torchvision's ``pil_loader``: ``Image.open(f).convert("RGB")``, as a uint8 [H, W, 3] array."""
+    from PIL import Image
+    with open(path, "rb") as f:
+        img = Image.open(f)
+        return np.array(img.convert("RGB"))
+
+
+def default_workers() -> int:
+    """``OMP_NUM_THREADS`` capped at 16 (never the machine's CPU count: a job is given a share of it)."""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", ""))
+    except ValueError:
+        n = 0
+    return max(1, min(n if n > 0 else MAX_WORKERS, MAX_WORKERS))
+
+
+class GraphImageFolder(Dataset):
+    """``utils/dataloader.py``'s ``OptimizedDatasetLoader`` (same parameters and defaults) over an image folder laid
+    out as ``torchvision.datasets.ImageFolder`` expects (``root/<class>/.../<image>``)."""
+
+    def __init__(self, dataset_path='dataset', resize_value=128, diagonals=False, method='pixel', n_segments=100,
+                 patch_size=8, use_cache=True):
+        if method not in I2G.METHODS:
+            raise ValueError(f"Unknown method: {method}")
+        self.dataset_path = dataset_path
+        self.classes, self.class_to_idx = find_classes(dataset_path)
+        self.samples = make_dataset(dataset_path, self.class_to_idx)
+        self.targets = [t for _, t in self.samples]
+        self.resize_value = resize_value
+        self.diagonals = diagonals
+        self.method = method
+        self.n_segments = n_segments
+        self.patch_size = patch_size
+        self.use_cache = use_cache
+
+    def __len__(self):
+        return len(self.samples)
+
+    def _graphs(self, images):
+        return I2G.graphs_from_images(images, self.method, resize_value=self.resize_value, diagonals=self.diagonals,
+                                      use_cache=self.use_cache, n_segments=self.n_segments,
+                                      patch_size=self.patch_size)
+
+    def __getitem__(self, idx):
+        path, label = self.samples[idx]
+        return self._graphs([load_rgb(path)])[0], torch.tensor(label, dtype=torch.long)
+
+    def loader(self, shuffle: bool = True, chunk: int = 64, workers: int | None = None):
+        """Iterable over ``((x, pos, edge_index), label)`` for ``train(model, ds.loader(), epochs, ...)``; every
+        iteration is one epoch, in the order ``DataLoader(self, batch_size=1, shuffle=shuffle)`` would give under the
+        same global RNG state."""
+        return GraphFolderLoader(self, shuffle, chunk, workers)
+
+
+class GraphFolderLoader:
+    """Epochs over a ``GraphImageFolder``: decode on a thread pool (the next chunk's decode is in flight while the
+    current chunk is consumed), then resize and graph builds per chunk in batched launches."""
+
+    def __init__(self, dataset: GraphImageFolder, shuffle: bool = True, chunk: int = 64, workers: int | None = None):
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        self.dataset = dataset
+        self.shuffle = shuffle
+        self.chunk = int(chunk)
+        self.workers = default_workers() if workers is None else max(1, min(int(workers), MAX_WORKERS))
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def order(self):
+        """The epoch's sample indices, drawing from the global RNG exactly as a single-process ``DataLoader`` does:
+        its iterator's base seed, then (shuffle only) ``RandomSampler``'s seed for a private generator."""
+        torch.empty((), dtype=torch.int64).random_()  # _BaseDataLoaderIter._base_seed
+        n = len(self.dataset)
+        if not self.shuffle:
+            return list(range(n))
+        seed = int(torch.empty((), dtype=torch.int64).random_().item())
+        generator = torch.Generator()
+        generator.manual_seed(seed)
+        return torch.randperm(n, generator=generator).tolist()
+
+    def __iter__(self):
+        order = self.order()
+        samples = self.dataset.samples
+        chunks = [order[i:i + self.chunk] for i in range(0, len(order), self.chunk)]
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            def decode(idx):
+                return [pool.submit(load_rgb, samples[i][0]) for i in idx]
+
+            pending = decode(chunks[0]) if chunks else []
+            for c, idx in enumerate(chunks):
+                images = [f.result() for f in pending]
+                pending = decode(chunks[c + 1]) if c + 1 < len(chunks) else []
+                graphs = self.dataset._graphs(images)
+                del images
+                for i, g in zip(idx, graphs):
+                    yield g, torch.tensor(samples[i][1], dtype=torch.long)

@@ -2,11 +2,15 @@
 
 Same function names and arguments as the reference
 (``image_to_graph_optimized.py:7,42,50``, ``image_to_graph_patch.py:6``, ``image_to_graph_superpixel.py:8``);
-the image is decoded / resized on the host with PIL exactly as the reference does, then everything else
+the single-image builders decode and resize on the host with PIL exactly as the reference does, then everything else
 (SLIC segmentation, node features, positions, edges) is produced in HBM by the kernels of ``csrc/superpixel.hip``
 and ``csrc/graph_build.hip``.  Results
 are the tensors ``utils/dataloader.py:49-51`` would build: ``x`` float32, ``pos`` float32, ``edge_index``
 int64, already on the GPU, in the reference's node and edge order.
+
+``resize`` is Pillow's ``Image.resize`` on the device (csrc/resize.hip) for a batch of decoded images of any sizes, and
+``graphs_from_images`` builds the graphs of such a batch from it: the same tensors as the single-image builders, with
+the resize and SLIC run as batched launches.
 """
 from __future__ import annotations
 
@@ -58,8 +62,12 @@ def _to_device_u8(img: np.ndarray) -> torch.Tensor:
 
 
 def pixel_graph_from_array(img_u8: np.ndarray, diagonals: bool = False, use_cache: bool = True):
+    return _pixel_graph(_to_device_u8(img_u8), diagonals, use_cache)
+
+
+def _pixel_graph(img: torch.Tensor, diagonals: bool, use_cache: bool):
+    """pixel graph of a device uint8 [H, W, C] image"""
     lib = native.load_library()
-    img = _to_device_u8(img_u8)
     H, W, C = img.shape
     x = torch.empty(H * W, C, dtype=torch.float32, device=img.device)
     pos = torch.empty(H * W, 2, dtype=torch.float32, device=img.device)
@@ -76,8 +84,12 @@ def image_to_graph_pixel_optimized(image_or_path, resize_value: int = 128, diago
 
 
 def patch_graph_from_array(img_u8: np.ndarray, patch_size: int = 8):
+    return _patch_graph(_to_device_u8(img_u8), patch_size)
+
+
+def _patch_graph(img: torch.Tensor, patch_size: int):
+    """patch graph of a device uint8 [H, W, C] image"""
     lib = native.load_library()
-    img = _to_device_u8(img_u8)
     H, W, C = img.shape
     nh, nw = H // patch_size, W // patch_size
     x = torch.empty(nh * nw, C, dtype=torch.float32, device=img.device)
@@ -175,3 +187,127 @@ def image_to_graph_superpixel(image_or_path, resize_value: int = 128, n_segments
         raise NotImplementedError(f"image_to_graph_superpixel: SLIC options {sorted(slic_options)} are not implemented "
                                   "(the reference passes only n_segments and compactness)")
     return superpixel_graph_from_array(_load_resized(image_or_path, resize_value), n_segments, compactness)
+
+
+# PIL.Image.Resampling values; the device resize implements the three whose weights need no sin / cos
+_RESAMPLE = {"bilinear": 2, "bicubic": 3, "box": 4}
+_UNSUPPORTED_RESAMPLE = {"nearest": 0, "lanczos": 1, "antialias": 1, "hamming": 5}
+
+
+def _resample_code(resample) -> int:
+    if isinstance(resample, str):
+        name = resample.lower()
+        if name in _RESAMPLE:
+            return _RESAMPLE[name]
+        if name in _UNSUPPORTED_RESAMPLE:
+            raise NotImplementedError(f"resize: resample={resample!r} is not implemented (bicubic, bilinear, box)")
+        raise ValueError(f"resize: unknown resample {resample!r}")
+    code = int(resample)
+    if code in _RESAMPLE.values():
+        return code
+    if code in _UNSUPPORTED_RESAMPLE.values():
+        raise NotImplementedError(f"resize: resample={resample!r} is not implemented (bicubic, bilinear, box)")
+    raise ValueError(f"resize: unknown resample {resample!r}")
+
+
+def _as_u8_tensor(img) -> torch.Tensor:
+    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if t.dtype != torch.uint8:
+        raise TypeError(f"resize: expected uint8 images, got {t.dtype}")
+    return t
+
+
+def _upload(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
+    """host -> device through pinned memory, stream-ordered (no host wait); device tensors pass through"""
+    if t.is_cuda:
+        return t.to(dev)
+    return t.contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def resize(images, size, resample="bicubic", box=None, reducing_gap=None) -> torch.Tensor:
+    """``PIL.Image.fromarray(img).resize(size, resample)`` on the GPU, byte for byte, for a batch of RGB images.
+
+    ``images``: one uint8 ``[H, W, 3]`` array or tensor, a ``[B, H, W, 3]`` batch, or a list of ``[H_i, W_i, 3]``
+    images of different sizes (NumPy arrays or tensors, on the host or the device).  ``size`` is ``(W, H)`` as in
+    PIL.  Returns a device uint8 ``[B, H, W, 3]`` tensor, or ``[H, W, 3]`` for a single image.  Host images are
+    uploaded through pinned memory; the whole batch is one stream-ordered enqueue with no host synchronisation, and a
+    dense device batch can be resized under ``torch.cuda.graph`` capture.
+
+    ``resample``: ``"bicubic"`` (Pillow's default), ``"bilinear"`` or ``"box"``, or the matching
+    ``PIL.Image.Resampling`` values.  ``NEAREST``, ``HAMMING`` and ``LANCZOS`` raise ``NotImplementedError``
+    (Hamming and Lanczos weights need ``sin`` / ``cos``, and the device libm is not promised to match glibc's last
+    bit), as do the ``box`` and ``reducing_gap`` arguments of ``Image.resize``."""
+    if box is not None or reducing_gap is not None:
+        raise NotImplementedError("resize: the box and reducing_gap arguments of Image.resize are not implemented")
+    code = _resample_code(resample)
+    out_w, out_h = (int(v) for v in size)
+    if out_w < 1 or out_h < 1:
+        raise ValueError(f"resize: output size must be positive, got {tuple(size)}")
+    dev = _device()
+    lib = native.load_library()
+    single = False
+    table = None
+    if isinstance(images, (list, tuple)):
+        if not images:
+            raise ValueError("resize: empty list of images")
+        imgs = [_as_u8_tensor(im) for im in images]
+        for im in imgs:
+            if im.dim() != 3 or im.shape[-1] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError(f"resize: expected RGB images [H, W, 3], got {tuple(im.shape)}")
+        if all(im.shape == imgs[0].shape for im in imgs):
+            src = torch.stack([_upload(im, dev) for im in imgs]) if imgs[0].is_cuda else _upload(torch.stack(imgs), dev)
+        else:
+            sizes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+            offs = np.cumsum([0] + [h * w * 3 for h, w in sizes])
+            tab = torch.tensor([[int(o), h, w] for o, (h, w) in zip(offs[:-1], sizes)], dtype=torch.int64)
+            if all(im.is_cuda for im in imgs):
+                src = torch.cat([im.to(dev).reshape(-1) for im in imgs])
+            else:
+                src = _upload(torch.cat([im.cpu().reshape(-1) for im in imgs]), dev)
+            table = _upload(tab, dev)
+            in_h, in_w = max(h for h, _ in sizes), max(w for _, w in sizes)
+            B = len(imgs)
+    else:
+        t = _as_u8_tensor(images)
+        if t.dim() not in (3, 4) or t.shape[-1] != 3:
+            raise ValueError(f"resize: expected an RGB image [H, W, 3] or batch [B, H, W, 3], got {tuple(t.shape)}")
+        single = t.dim() == 3
+        src = _upload(t.unsqueeze(0) if single else t, dev).contiguous()
+    if table is None:
+        B, in_h, in_w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    if B == 0 or in_h == 0 or in_w == 0:
+        raise ValueError("resize: empty image or batch")
+    out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = lib.gnc_resize_workspace_bytes(B, in_h, in_w, out_h, out_w, code)
+        if nbytes == 0:
+            raise NotImplementedError(f"resize: {B} images of up to {in_h} x {in_w} -> {out_h} x {out_w} is outside "
+                                      "the supported set (batch and sides up to 65535)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        native._check(lib.gnc_resize_rgb_u8(src.data_ptr(), table.data_ptr() if table is not None else None, B, in_h,
+                                            in_w, out_h, out_w, code, out.data_ptr(), ws.data_ptr(), nbytes,
+                                            torch.cuda.current_stream(dev).cuda_stream), "gnc_resize_rgb_u8")
+    return out[0] if single else out
+
+
+METHODS = ("pixel", "patch", "superpixel")
+
+
+def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128, diagonals: bool = False,
+                       use_cache: bool = True, n_segments: int = 100, patch_size: int = 8, compactness: float = 10):
+    """Graphs of a batch of decoded uint8 RGB images ``[H_i, W_i, 3]`` (any sizes): a list of ``(x, pos, edge_index)``
+    equal to ``image_to_graph_pixel_optimized`` / ``image_to_graph_patch`` / ``image_to_graph_superpixel`` of each
+    image, with arguments named as ``utils/dataloader.py``'s ``OptimizedDatasetLoader``.  The resize of the whole
+    batch is one launch (``resize``), superpixel runs one batched ``slic``; pixel and patch nodes are one launch per
+    image, and every superpixel region graph costs one host synchronisation (its sizes depend on the data)."""
+    if method not in METHODS:
+        raise ValueError(f"Unknown method: {method}")
+    if len(images_u8) == 0:
+        return []
+    imgs = resize(list(images_u8), (resize_value, resize_value))
+    if method == "pixel":
+        return [_pixel_graph(im, diagonals, use_cache) for im in imgs]
+    if method == "patch":
+        return [_patch_graph(im, patch_size) for im in imgs]
+    labels = slic(imgs, n_segments=n_segments, compactness=compactness, start_label=0)
+    return [_superpixel_graph_from_device_labels(im, lab) for im, lab in zip(imgs, labels)]

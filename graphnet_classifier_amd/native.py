@@ -88,6 +88,9 @@ _SIGNATURES = {
     "gnc_slic_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "gnc_slic_rgb_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32, c_int32, c_double, c_double,
                                   c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gnc_resize_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "gnc_resize_rgb_u8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     "gnc_colsum_pair_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
     "gnc_reduce_partials_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnc_activation_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_float, c_void_p, c_int64, c_void_p]),

@@ -494,6 +494,21 @@ int gnc_slic_rgb_u8(const uint8_t* img, int32_t B, int32_t H, int32_t W, int32_t
                     int32_t start_label, int32_t* labels, int32_t* counts, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* ---- batched RGB resize on the device (the `Image.resize((R, R))` of every image_to_graph builder) --
+ * gnc_resize_rgb_u8    Pillow's `Image.fromarray(img).resize((out_w, out_h), filter)` byte for byte for B uint8 RGB images
+ *                      of any sizes at once; filter = PIL.Image.Resampling value: BILINEAR 2, BICUBIC 3 (Pillow's
+ *                      default), BOX 4 (anything else: GNC_ERR_UNSUPPORTED).  `table` NULL: `src` is a dense
+ *                      [B, in_h, in_w, 3] batch.  Otherwise `table` is DEVICE int64 [B, 3] = (byte offset of image b in
+ *                      `src`, h_b, w_b) with 1 <= h_b <= in_h and 1 <= w_b <= in_w (an entry outside that is skipped).
+ *                      `out` [B, out_h, out_w, 3] uint8.  Workspace of gnc_resize_workspace_bytes(B, in_h, in_w, out_h,
+ *                      out_w, filter) bytes (0 = not supported: B or a side outside 1..65535, unknown filter).
+ *                      Stream-ordered, no host synchronisation, safe under stream capture.  Added without an ABI bump:
+ *                      a library without these symbols fails the symbol lookup of the binding.
+ */
+size_t gnc_resize_workspace_bytes(int32_t B, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, int32_t filter);
+int gnc_resize_rgb_u8(const uint8_t* src, const int64_t* table, int32_t B, int32_t in_h, int32_t in_w, int32_t out_h,
+                      int32_t out_w, int32_t filter, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- fused Adam over flat buffers -------------------------------
  * Replaces `optimizer.step()` of utils/train_model.py:42 for `optim.Adam(model.parameters(), lr=1e-3)` (:9):
  * every parameter is a view of `param` [n], every gradient a view of `grad` [n]; one launch updates all of them
