@@ -31,6 +31,9 @@ READOUT_HIP = os.environ.get("GNC_NO_READOUT_KERNEL") is None
 # Inference: the edge processor's launch also forms the node model's per-destination sums (fused aggregation
 # epilogue); GNC_NO_FUSED_AGG=1 keeps K1 as a separate launch for A/B measurements.
 FUSED_AGG = os.environ.get("GNC_NO_FUSED_AGG") is None
+# Inference: GraphNet.forward_device drops the last GN block's edge output, so that block's edge launch forms only the
+# aggregate and stores no e' rows (gnc_mlp_forward_agg_only_f32); GNC_NO_DEAD_EDGE_STORE=1 keeps the storing launch for A/B.
+DROP_DEAD_EDGE_STORE = os.environ.get("GNC_NO_DEAD_EDGE_STORE") is None
 
 
 # --------------------------------------------------------------------------- a1 scatter_sum
@@ -84,11 +87,13 @@ class EdgeProcessor(nn.Module):
         out = self.edge_processor.forward_segments([(src, None), (dest, None), (edge_attr, None)], residual=edge_attr)
         return out if back == dev else out.to(back)
 
-    def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor, aggregate: bool = False):
+    def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor, aggregate: bool = False,
+                       need_edges: bool = True):
         """Same math with the two row gathers fused into the kernel; ``edge_attr`` and the
         result are in destination-sorted edge order.  ``aggregate=True`` returns ``(e', agg)`` where ``agg`` is the
         per-destination sum of ``e'`` formed in the same launch, or None when this path cannot provide it (the
-        caller then runs K1)."""
+        caller then runs K1).  ``need_edges=False`` (with ``aggregate``, autograd off): ``e'`` may come back as None
+        when the launch can form ``agg`` without storing it."""
         mlp = self.edge_processor
         norm = mlp.model[-1] if mlp.norm_type is not None else None
         lin = mlp._linears()
@@ -101,7 +106,7 @@ class EdgeProcessor(nn.Module):
             ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
             if aggregate and not torch.is_grad_enabled():
                 return Fn.edge_processor_wsplit_aggregated(x, edge_attr, topo, [m.weight for m in lin], [m.bias for m in lin],
-                                                           ln, mlp.activation_name, mlp._act_param())
+                                                           ln, mlp.activation_name, mlp._act_param(), store_edges=need_edges)
             if aggregate:  # training: same launch, both outputs differentiable
                 return Fn.edge_processor_wsplit(x, edge_attr, topo, [m.weight for m in lin], [m.bias for m in lin], ln,
                                                 mlp.activation_name, mlp._act_param(), with_agg=True)
@@ -166,14 +171,15 @@ class MetaLayer(nn.Module):
             x, edge_attr = x.to(back), edge_attr.to(back)
         return x, edge_attr, u
 
-    def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor):
+    def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor, need_edges: bool = True):
+        """``need_edges=False``: the caller drops the edge output, which may then come back as None (inference)."""
         agg = None
         if self.edge_model is not None:
             # let the edge launch form the node model's aggregate in its epilogue (SURVEY 8-f1); with autograd on the
             # W-split Function returns both outputs and folds the aggregate's gradient (a gather) into e''s
             if (FUSED_AGG and self.node_model is not None
                     and isinstance(self.edge_model, EdgeProcessor) and isinstance(self.node_model, NodeProcessor)):
-                edge_attr, agg = self.edge_model.forward_sorted(x, topo, edge_attr, aggregate=True)
+                edge_attr, agg = self.edge_model.forward_sorted(x, topo, edge_attr, aggregate=True, need_edges=need_edges)
             else:
                 edge_attr = self.edge_model.forward_sorted(x, topo, edge_attr)
         if self.node_model is not None:
@@ -225,9 +231,11 @@ class GraphProcessor(nn.Module):
             x, edge_attr = x.to(back), edge_attr.to(back)
         return x, edge_attr
 
-    def forward_sorted(self, x, topo: GraphTopology, edge_attr):
-        for block in self.blocks:
-            x, edge_attr = block.forward_sorted(x, topo, edge_attr)
+    def forward_sorted(self, x, topo: GraphTopology, edge_attr, need_edges: bool = True):
+        """``need_edges=False``: the caller drops the edge output; the last block may then return None for it."""
+        last = len(self.blocks) - 1
+        for k, block in enumerate(self.blocks):
+            x, edge_attr = block.forward_sorted(x, topo, edge_attr, need_edges=need_edges or k < last)
         return x, edge_attr
 
 
@@ -281,7 +289,7 @@ class GraphNet(nn.Module):
         if edge_attr is None:
             edge_attr = Fn.edge_features(pos, topo.src_sorted, topo.dst_sorted)           # :299-302 (K6)
             edge_attr = self.edge_encoder.forward_segments([(edge_attr, None)])           # :306
-        out, _ = self.graph_processor.forward_sorted(out, topo, edge_attr)                # :307
+        out, _ = self.graph_processor.forward_sorted(out, topo, edge_attr, need_edges=not DROP_DEAD_EDGE_STORE)  # :307
         out = self.node_decoder.forward_segments([(out, None)])                           # :308
         return _poison_if_deferred(topo, out)  # validation not read back yet: a bad edge_index must not yield a plausible result
 

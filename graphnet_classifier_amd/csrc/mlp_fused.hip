@@ -301,6 +301,58 @@ extern "C" int gnc_mlp_agg_supported(const gnc_mlp_desc_t* desc) {
   return GNC_OK;
 }
 
+// shape-only answer for the aggregate-only launch (gnc_mlp_forward_agg_only_f32): the FULL W-split edge processor instance of
+// the weights-resident kernel (every width 64, three Linear layers, LayerNorm), inference
+extern "C" int gnc_mlp_agg_only_supported(const gnc_mlp_desc_t* desc) {
+  int rc = gnc_mlp_agg_supported(desc);
+  if (rc) return rc;
+  const int L = desc->num_linear;
+  int T = tiles_for(desc->out_dim[0]);
+  const int od = desc->out_dim[L - 1];
+  const bool narrow_out = od <= 32;
+  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
+  gnc_mlp_desc_t probe = *desc;
+  int32_t dummy_i = 0;
+  float dummy_f = 0.f;
+  if (!probe.agg_out) probe.agg_out = &dummy_f;
+  if (!probe.agg_index) probe.agg_index = &dummy_i;
+  if (!probe.agg_fix) probe.agg_fix = &dummy_i;
+  if (probe.ld_agg < od) probe.ld_agg = od;
+  bool ok = false;
+  rc = launch_resident(probe, T, narrow_out, nullptr, &ok, true, true);
+  if (rc) return rc;
+  if (!ok) {
+    gnc::set_error("gnc_mlp_agg_only_supported: needs the 64-wide W-split edge processor (1 MATMUL + 2 ADD segments, residual = "
+                   "the MATMUL segment, three Linear layers, LayerNorm) without save_act");
+    return GNC_ERR_UNSUPPORTED;
+  }
+  return GNC_OK;
+}
+
+extern "C" int gnc_mlp_forward_agg_only_f32(const gnc_mlp_desc_t* desc, void* stream) {
+  int rc = validate_desc(desc, true);
+  if (rc) return rc;
+  if (!desc->agg_out || !desc->agg_index || !desc->agg_fix) {
+    gnc::set_error("gnc_mlp_forward_agg_only_f32: agg_out, agg_index and agg_fix are required");
+    return GNC_ERR_INVALID_ARGUMENT;
+  }
+  rc = gnc_mlp_agg_only_supported(desc);
+  if (rc) return rc;
+  if (desc->rows == 0) return GNC_OK;
+  const int L = desc->num_linear;
+  int T = tiles_for(desc->out_dim[0]);
+  const int od = desc->out_dim[L - 1];
+  const bool narrow_out = od <= 32;
+  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
+  bool launched = false;
+  rc = launch_resident(*desc, T, narrow_out, (hipStream_t)stream, &launched, false, true);
+  if (!rc && !launched) {
+    gnc::set_error("gnc_mlp_forward_agg_only_f32: the weights-resident kernel did not take the launch");
+    rc = GNC_ERR_UNSUPPORTED;
+  }
+  return rc;
+}
+
 // shape-only answer for the training forward's saved post-activations: the weights-resident kernel writes them
 namespace {
 // Small batches at 65..128 features (one ~1000-node graph per call, main.py:60): a 32-row wave tile is 768 dependent

@@ -96,8 +96,12 @@ constexpr int RNT = RWAVES * 64;
 // row-ordered MATMUL step, two ADD segments, residual in registers), 2: all but the first (the encoders: first Linear
 // K <= 4, one fp32 MFMA k-group).  Their weights are resident as three bf16 planes (SCH floats per chunk, after the
 // fp32 chunks).  0: every Linear in fp32 MFMA (GNC_MLP_F32_EXACT=1 keeps every launch there).
+// AGGONLY (with AGG; gnc_mlp_forward_agg_only_f32): only the aggregate is wanted - the output rows are stored only where
+// gnc_agg_fixup_f32 reads them, i.e. the rows of the wave range's first and last destination; every other row is dropped.
+// A destination cut by range boundaries is the first or the last destination of EVERY range that holds rows of it, so the
+// fix-up finds all of its rows.  The aggregate itself is formed from the same staged rows as in the storing instance.
 template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0, bool DUAL = false,
-          int SPLIT = 0>
+          int SPLIT = 0, bool AGGONLY = false>
 __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t d, const int num_wtiles,
                                                            const int total_chunks) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -301,6 +305,17 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   int agg_cur = -1, agg_first_dst = -1;  // wave-uniform
   bool agg_first = true;
   if constexpr (AGG) aid = agg_ids(wt < last_wt ? wt : last_wt);
+  static_assert(!AGGONLY || (AGG && FULL && !SAVE && !DUAL), "aggregate-only: the FULL AGG inference instance");
+  // AGGONLY: the first and the last destination of this wave's range (wave-uniform; -1 for an idle wave)
+  int keep_lo = -1, keep_hi = -1;
+  if constexpr (AGGONLY) {
+    if (wt < wt_end) {
+      const int last_row = wt_end * RPW < rows ? wt_end * RPW - 1 : rows - 1;
+      keep_lo = d.agg_index[wt * RPW];
+      keep_hi = d.agg_index[last_row];
+    }
+  }
+  uint32_t keep_rows = 0;  // AGGONLY: bit r = row r of the current tile is stored
 
   PROBE_BEGIN();
   while (wt < wt_end) {
@@ -485,6 +500,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       prv = lane == 0 ? agg_cur : prv;
       const unsigned long long vmask = valid >= 32 ? 0xffffffffull : ((1ull << valid) - 1ull);
       const unsigned long long bnd = __ballot(aid != prv) & vmask;
+      if constexpr (AGGONLY) keep_rows = (uint32_t)(__ballot(aid == keep_lo || aid == keep_hi) & vmask);
       // all 32 row values first (one batch of LDS reads): the walk below has a scalar branch per row, and a
       // read inside it would cost a full LDS round trip every time
       float rowv[RPW];
@@ -540,7 +556,15 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
     if constexpr (AGG) asm volatile("" ::"v"(aid_next));
 
     // ------------------------------------------------------------------ epilogue: whole rows out
-    {
+    if constexpr (AGGONLY) {  // only the rows the fix-up reads (none in most tiles); rows past the end are never kept
+      if (keep_rows) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(abuf + (p * 4 + rs) * LDSW + col_out);
+          if ((keep_rows >> (p * 4 + rs)) & 1u) hidden_window_store<true>(v, out_lane_off, row_window(d.out, row0 + 4 * p, rows, d.ld_out));
+        }
+      }
+    } else {
       f32x4 outv[NP];
 #pragma unroll
       for (int p = 0; p < NP; ++p) outv[p] = *reinterpret_cast<const f32x4*>(abuf + (p * 4 + rs) * LDSW + col_out);
@@ -604,9 +628,9 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
 }
 
 template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0, bool DUAL = false,
-          int SPLIT = 0>
+          int SPLIT = 0, bool AGGONLY = false>
 int launch(const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t stream) {
-  void (*const kernel)(const gnc_mlp_desc_t, const int, const int) = &mlp_resident_kernel<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, DUAL, SPLIT>;
+  void (*const kernel)(const gnc_mlp_desc_t, const int, const int) = &mlp_resident_kernel<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, DUAL, SPLIT, AGGONLY>;
   static bool attr_set = false;
   if (!attr_set) {
     int rc = gnc::check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
@@ -623,16 +647,17 @@ int launch(const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t s
 }
 
 // the launch in its split class (see SPLIT at mlp_resident_kernel): 1 = the W-split edge processor, 2 = the encoders
-template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0>
+template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0,
+          bool AGGONLY = false>
 int launch_cls(int split, const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t stream) {
   if constexpr (HT == 2 && OT == 2 && NMM == 1 && NADD == 2 && RESREG) {
-    if (split == 1) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 1>(d, total_chunks, smem, stream);
+    if (split == 1) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 1, AGGONLY>(d, total_chunks, smem, stream);
   }
   if constexpr (HT == 2 && OT == 2 && NMM == 1 && NADD == 0 && !RESREG && !AGG && !FULL) {
     if (split == 2) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 2>(d, total_chunks, smem, stream);
   }
   if (split) return GNC_ERR_UNSUPPORTED;  // a class without its instance: never taken (the launcher's tests below)
-  return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF>(d, total_chunks, smem, stream);
+  return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 0, AGGONLY>(d, total_chunks, smem, stream);
 }
 
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -677,8 +702,9 @@ int gnc_mlp::launch_resident_dual(const float* x, int64_t ld_x, int64_t rows, co
 }
 
 int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hipStream_t stream, bool* launched,
-                             bool probe_only) {
+                             bool probe_only, bool agg_only) {
   *launched = false;
+  if (agg_only && (!d.agg_out || d.save_act[0])) return GNC_OK;  // aggregate-only: an inference launch with the epilogue
   static const bool disabled = getenv("GNC_MLP_NO_RESIDENT") != nullptr;  // A/B switch for benchmarking
   if (disabled) return GNC_OK;
   if (T > 2 || d.rows >= INT32_MAX) return GNC_OK;
@@ -788,8 +814,11 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
   }
   if (d.agg_out) {  // fused aggregation epilogue: the W-split edge processor shape only
     if (!(nadd == 2 && nmm == 1 && resreg && !narrow_out && d.agg_index && d.agg_fix && d.ld_agg >= od)) return GNC_OK;
+    // aggregate-only (gnc_mlp_forward_agg_only_f32): the FULL instance only (c3's edge processor, either class)
+    if (agg_only && !(T == 2 && full64)) return GNC_OK;
     *launched = true;
     if (probe_only) return GNC_OK;
+    if (agg_only) return launch_cls<2, 2, 1, 2, true, true, false, true, 0, true>(split, d, total_chunks, smem, stream);
     if (T == 2 && full64) return launch_cls<2, 2, 1, 2, true, true, false, true>(split, d, total_chunks, smem, stream);
     return T == 2 ? launch_cls<2, 2, 1, 2, true, true>(split, d, total_chunks, smem, stream)
                   : launch<1, 1, 1, 2, true, true>(d, total_chunks, smem, stream);

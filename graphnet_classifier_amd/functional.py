@@ -483,18 +483,19 @@ def edge_processor_wsplit(x, e, topo, weights, biases, ln, activation="ReLU", ac
     return _EdgeProcessorWSplit.apply(meta, topo, x, e, *args)
 
 
-def edge_processor_wsplit_aggregated(x, e, topo, weights, biases, ln, activation="ReLU", act_param=0.0):
+def edge_processor_wsplit_aggregated(x, e, topo, weights, biases, ln, activation="ReLU", act_param=0.0, store_edges=True):
     """Inference form of ``edge_processor_wsplit`` (no autograd graph): the edge launch also forms the
     per-destination sums of its output rows in its epilogue (include/gnc_hip.h, ``agg_out``).
     Returns ``(e', agg)``; ``agg`` is None when the launch shape cannot carry the epilogue (the caller then
-    runs K1).  ``agg`` is bit-identical to ``scatter_sum_csr(e', topo.rowptr)``."""
+    runs K1).  ``agg`` is bit-identical to ``scatter_sum_csr(e', topo.rowptr)``.  ``store_edges=False``: ``e'`` is not
+    wanted, and where the aggregate-only launch serves the shape it is not stored either: ``(None, agg)``."""
     dn = x.size(1)
     w0 = weights[0]
     ps, pd = _node_projections(x, w0, dn)
     return native.mlp_forward([(ps, topo.src_sorted), (pd, topo.dst_sorted), (e, None)], [w0[:, 2 * dn:]] + list(weights[1:]),
                               list(biases), ln=ln, activation=activation, act_param=act_param, residual=e, rows=e.size(0),
                               modes=[native.SEG_ADD, native.SEG_ADD, native.SEG_MATMUL],
-                              aggregate=(topo.dst_sorted, topo.rowptr, topo.num_nodes))
+                              aggregate=(topo.dst_sorted, topo.rowptr, topo.num_nodes), agg_only=not store_edges)
 
 
 class _Readout(torch.autograd.Function):

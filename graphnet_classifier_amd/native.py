@@ -30,6 +30,8 @@ _SIGNATURES = {
     "gnc_last_error_string": (c_char_p, []),
     "gnc_target_arch": (c_char_p, []),
     "gnc_mlp_agg_supported": (c_int32, [c_void_p]),
+    "gnc_mlp_agg_only_supported": (c_int32, [c_void_p]),
+    "gnc_mlp_forward_agg_only_f32": (c_int32, [c_void_p, c_void_p]),
     "gnc_mlp_edge_features_supported": (c_int32, [c_void_p]),
     "gnc_mlp_operands_in_place_supported": (c_int32, [c_void_p]),
     "gnc_mlp_save_act_supported": (c_int32, [c_void_p]),
@@ -550,7 +552,7 @@ def _backward_reads_saved_act(lib, desc, any_tensor, need_dx: bool = True) -> bo
 
 def mlp_forward(segments, weights, biases, ln=None, activation: str = "ReLU", act_param: float = 0.0,
                 residual: torch.Tensor | None = None, rows: int | None = None, modes=None, aggregate=None,
-                save_act: list | None = None, save_need_dx: bool = True):
+                save_act: list | None = None, save_need_dx: bool = True, agg_only: bool = False):
     """Fused MLP.  segments (in CONCAT order): list of (table [*, w] fp32, index int32 [rows] | None);
     ``modes[s]`` is SEG_MATMUL (default) or SEG_ADD.  Weights may be column slices of a larger
     matrix.  The segment that is also the residual is listed last for the kernel (its weight
@@ -559,7 +561,9 @@ def mlp_forward(segments, weights, biases, ln=None, activation: str = "ReLU", ac
     ``aggregate=(dst_of_row int32 [rows] non-decreasing, rowptr int32 [N+1], N)`` asks for the fused aggregation
     epilogue: returns ``(out, agg)`` with ``agg[v] = sum of out rows with dst v`` in row order,
     bit-identical to ``scatter_sum_csr(out, rowptr)``; returns ``(out, None)`` when the launch shape cannot
-    carry it (the caller then runs K1).
+    carry it (the caller then runs K1).  With ``agg_only`` as well, the output rows are not wanted: where
+    gnc_mlp_agg_only_supported says so the launch stores only the rows the fix-up reads and ``(None, agg)`` comes back
+    (``agg`` bit-identical to the storing launch's); otherwise the storing launch runs and ``(out, agg)`` comes back.
 
     ``save_act`` (training forward): an empty list; when the kernel that serves the call can write the post-activation
     outputs of its hidden layers (gnc_mlp_save_act_supported) they are appended to it ([rows, H] each) for
@@ -600,18 +604,20 @@ def mlp_forward(segments, weights, biases, ln=None, activation: str = "ReLU", ac
             fix = torch.empty(lib.gnc_mlp_agg_fix_len(), dtype=torch.int32, device=dev)
             desc.agg_out, desc.ld_agg = agg.data_ptr(), _ld(agg)
             desc.agg_index, desc.agg_fix = dst_of_row.contiguous().data_ptr(), fix.data_ptr()
+    agg_only = agg_only and agg is not None and lib.gnc_mlp_agg_only_supported(ctypes.byref(desc)) == 0
+    forward = lib.gnc_mlp_forward_agg_only_f32 if agg_only else lib.gnc_mlp_forward_f32
     # executed FLOPs of this launch: 2 * rows * sum(in*out) over the Linear layers
     flops = 2.0 * rows * sum(w.size(0) * w.size(1) for w in weights)
     with torch.cuda.device(dev):
         nadd = sum(1 for m in modes if m == SEG_ADD)
         _check(_launch(f"mlp_fused_in{weights[0].size(1)}{'+%dadd' % nadd if nadd else ''}_h{weights[0].size(0)}"
                        f"_out{weights[-1].size(0)}_L{len(weights)}", out,
-                       lambda: lib.gnc_mlp_forward_f32(ctypes.byref(desc), _stream(out)), flops),
-               "gnc_mlp_forward_f32")
+                       lambda: forward(ctypes.byref(desc), _stream(out)), flops),
+               forward.__name__)
         if agg is not None:  # the destinations cut by a wave-range boundary, from the stored rows (same stream)
             _check(lib.gnc_agg_fixup_f32(out.data_ptr(), _ld(out), rowptr.data_ptr(), fix.data_ptr(), fix.numel(), num_nodes,
                                          out.size(1), agg.data_ptr(), _ld(agg), _stream(out)), "gnc_agg_fixup_f32")
-    return (out, agg) if aggregate is not None else out
+    return (None if agg_only else out, agg) if aggregate is not None else out
 
 
 FOLD_EDGE_FEATURES = os.environ.get("GNC_NO_K6_FOLD") is None  # A/B switch: K6 as its own launch + a [E, 4] table

@@ -253,6 +253,15 @@ int gnc_mlp_forward_f32(const gnc_mlp_desc_t* desc /* host */, void* stream);
 /* fused aggregation epilogue: 0 if this description can run with agg_out set (shape fields only) */
 int gnc_mlp_agg_supported(const gnc_mlp_desc_t* desc /* host */);
 int gnc_mlp_agg_fix_len(void); /* entries of agg_fix (2 per wave of the persistent grid) */
+/* Aggregate-only launch: the description of an agg_out launch whose output rows nobody reads afterwards (the last GN block's
+ * edge processor in inference).  agg_out and agg_fix are formed exactly as gnc_mlp_forward_f32 forms them, bit for bit, but
+ * `out` [rows, ld_out] is written ONLY at the rows whose destination is listed in agg_fix - the rows gnc_agg_fixup_f32 reads;
+ * every other row of `out` is left as it was.  Run gnc_agg_fixup_f32 afterwards as for the storing launch.
+ * gnc_mlp_agg_only_supported() answers from the shape fields (GNC_ERR_UNSUPPORTED: use gnc_mlp_forward_f32): served for the
+ * 64-wide W-split edge processor (1 MATMUL + 2 ADD segments, residual = the MATMUL segment, three Linear layers, LayerNorm,
+ * 16-B aligned output) wherever gnc_mlp_agg_supported() serves it, without save_act. */
+int gnc_mlp_agg_only_supported(const gnc_mlp_desc_t* desc /* host */);
+int gnc_mlp_forward_agg_only_f32(const gnc_mlp_desc_t* desc /* host */, void* stream);
 /* ABI 19: 0 if the kernel that gnc_mlp_forward_f32 picks for this description reads its operands where they lie: weight
  * matrices of any row stride / alignment (the [H, 3] matrix of nn.Linear(3, H), models/GNN.py:251-256) and a contiguous
  * [rows, 3] table as the only segment (the node features of models/GNN.py:305) - no zero-padded copies needed.  Every other
