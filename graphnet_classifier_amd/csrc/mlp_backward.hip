@@ -1052,8 +1052,6 @@ __global__ __launch_bounds__(256) void colsum_pair_kernel(const float* __restric
   }
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // schedule shape shared by the support query and the launcher; returns 0 if unsupported
 int bwd_shape(const gnc_mlp_desc_t& d, int* nmm_out, int* nadd_out, int* T_out) {
   const int L = d.num_linear;
@@ -1182,10 +1180,9 @@ int launch_bwd_stream(const gnc_mlp_desc_t& d, const BwdArgs& b, const BwdPlan& 
 
 // waves per workgroup of the 32-row streaming kernel for T 32-column tiles (the dispatch below and the partial-row query)
 int bwd_stream_waves(int T, int64_t rows) {
-  static const bool w4 = getenv("GNC_BWD_STREAM_W4") != nullptr;  // A/B: the 4-wave (one per SIMD, 512 registers) form at 128
   if (T < 4) return 4;
   if (rows <= (int64_t)2 * RPW * gnc::num_cu()) return 2;  // small batch: see mlp_stream.hip
-  return w4 ? 4 : 8;
+  return 8;
 }
 
 int bwd_grid(int64_t rows) {
@@ -1338,13 +1335,9 @@ extern "C" int gnc_mlp_backward_f32(const gnc_mlp_bwd_desc_t* bd, void* stream_)
       case 1: return launch_bwd_stream<1, 4>(d, b, pl, st);
       case 2: return launch_bwd_stream<2, 4>(d, b, pl, st);
       default: {
-        const int wv = bwd_stream_waves(T, d.rows);
-        if (pl.saved) {
-          if (wv == 2) return launch_bwd_stream<4, 2, true>(d, b, pl, st);
-          return wv == 4 ? launch_bwd_stream<4, 4, true>(d, b, pl, st) : launch_bwd_stream<4, 8, true>(d, b, pl, st);
-        }
-        if (wv == 2) return launch_bwd_stream<4, 2>(d, b, pl, st);
-        return wv == 4 ? launch_bwd_stream<4, 4>(d, b, pl, st) : launch_bwd_stream<4, 8>(d, b, pl, st);
+        const bool small = bwd_stream_waves(T, d.rows) == 2;
+        if (pl.saved) return small ? launch_bwd_stream<4, 2, true>(d, b, pl, st) : launch_bwd_stream<4, 8, true>(d, b, pl, st);
+        return small ? launch_bwd_stream<4, 2>(d, b, pl, st) : launch_bwd_stream<4, 8>(d, b, pl, st);
       }
     }
   }
@@ -1374,7 +1367,7 @@ extern "C" int gnc_mlp_backward_saved_act_honoured(const gnc_mlp_bwd_desc_t* bd)
   const gnc_mlp_desc_t& d = bd->fwd;
   if (validate_desc(&d, false) != GNC_OK) return 0;
   for (int l = 0; l < d.num_linear - 1; ++l)  // contiguous [rows, out_dim[l]] rows read as 16-B pieces
-    if (!bd->act[l] || !fused_al16(bd->act[l]) || d.out_dim[l] % 4 != 0) return 0;
+    if (!bd->act[l] || !al16(bd->act[l]) || d.out_dim[l] % 4 != 0) return 0;
   if (bd->dw_partial[0]) return fused_shape(d) >= 0 ? 1 : 0;  // fused data + weight-gradient kernel (widths <= 64)
   if (d.num_linear >= 2 && bwd_col16_supported(d)) return 1;     // small batches: the column-split data kernel
   if (bwd_col16_persist_supported(d)) return 1;
@@ -1394,7 +1387,7 @@ extern "C" int gnc_mlp_backward_grad_gather_honoured(const gnc_mlp_bwd_desc_t* b
   if (off || !bd || !bd->grad_gather || !bd->grad_gather_index) return 0;
   if (!bd->dw_partial[0]) {  // split path: only the small-batch data kernel (saved activations) gathers in the launch
     return (bd->act_given && gnc_mlp::validate_desc(&bd->fwd, false) == GNC_OK && (bwd_col16_supported(bd->fwd) || (bwd_col16_persist_supported(bd->fwd) && bd->fwd.in_dim[0] <= 128)) &&
-            bd->ld_grad_gather % 4 == 0 && fused_al16(bd->grad_gather) && bd->ld_grad_gather >= bd->fwd.out_dim[bd->fwd.num_linear - 1])
+            bd->ld_grad_gather % 4 == 0 && al16(bd->grad_gather) && bd->ld_grad_gather >= bd->fwd.out_dim[bd->fwd.num_linear - 1])
                ? 1 : 0;
   }
   const gnc_mlp_desc_t& d = bd->fwd;
@@ -1402,7 +1395,7 @@ extern "C" int gnc_mlp_backward_grad_gather_honoured(const gnc_mlp_bwd_desc_t* b
   // the fused kernel gathers with the ids of its second ADD segment (in the edge processor both are the destination)
   if (bd->grad_gather_index != d.seg[2].index || bd->grad_gather_rows != d.seg[2].table_rows) return 0;
   const int64_t bytes = bd->grad_gather_rows * (int64_t)bd->ld_grad_gather * 4;
-  if (bd->ld_grad_gather % 4 != 0 || !fused_al16(bd->grad_gather) || bd->ld_grad_gather < d.out_dim[2]) return 0;
+  if (bd->ld_grad_gather % 4 != 0 || !al16(bd->grad_gather) || bd->ld_grad_gather < d.out_dim[2]) return 0;
   // ids one row past either table (rows beyond the end of the batch) must still be addressable in 32 bits
   if (bytes + 256 > 0xffffffffll || d.seg[2].table_rows * (int64_t)d.seg[2].ld * 4 + 256 > 0xffffffffll) return 0;
   return 1;

@@ -171,9 +171,9 @@ __device__ __forceinline__ void layer_norm_backward16(f32x4 (&y)[NTL], f32x4 (&g
   }
 }
 
-// NTL: 16-feature tiles of the widest layer (hidden / output): 16 for 129..256 features
-// SAVED (= pl.saved, as a template flag: the run-time branch alone cost the recomputing instance 460 B of scratch)
-template <int NTL, bool SAVED = false>
+// NTL: 16-feature tiles of the widest layer (hidden / output): 16 for 129..256 features.  Recomputes the forward of every
+// tile; saved post-activations go to mlp_backward_saved16_kernel below.
+template <int NTL>
 __global__ __launch_bounds__(NT16) void mlp_backward_stream16_kernel(const gnc_mlp_desc_t d, const BwdArgs b, const BPlan16 pl,
                                                                       const int num_tiles) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -325,14 +325,8 @@ __global__ __launch_bounds__(NT16) void mlp_backward_stream16_kernel(const gnc_m
     const gnc_mlp_segment_t& sg = d.seg[pl.step[st].seg];
     load_rows(pre, sg.ptr, sg.ld, sg.index, sg.table_rows, pl.step[st].c0, id_of(pl.step[st].seg), tile_of);
   };
-  // SAVED (pl.saved): the row stream of a tile is the slabs of the saved post-activations a_0 .. a_{L-2} (ReLU masks; the
-  // last tensor stays in registers for the LayerNorm recompute), then the grad_out slabs; no gathered input is read
-  auto load_first = [&](f32x4 (&pre)[NP16], int tile_of) {
-    if constexpr (SAVED) load_rows(pre, b.act[0], d.out_dim[0], nullptr, 0, 0, 0, tile_of);
-    else load_step(pre, 0, tile_of);
-  };
   f32x4 cur[NP16];
-  load_first(cur, tile);
+  load_step(cur, 0, tile);
   const int n_gslabs = (out_dim + KC - 1) / KC;
 
   B16P_BEGIN();
@@ -344,33 +338,6 @@ __global__ __launch_bounds__(NT16) void mlp_backward_stream16_kernel(const gnc_m
 
     f32x4 hid[NTL];
     unsigned mask[GNC_MAX_LINEAR - 1][MW];
-    if constexpr (SAVED) {
-#pragma unroll
-      for (int l = 0; l < GNC_MAX_LINEAR - 1; ++l) {
-        if (l < L - 1) {
-          const int width = d.out_dim[l];
-#pragma unroll
-          for (int cc = 0; cc < NCH; ++cc) {
-            if (cc * KC < width) {
-              stage(cur, cc * KC, width);
-              // the stream's next item: this tensor's next slab, the next tensor's first, or grad_out's first
-              if ((cc + 1) * KC < width) load_rows(cur, b.act[l], width, nullptr, 0, (cc + 1) * KC, 0, tile);
-              else if (l + 1 < L - 1) load_rows(cur, b.act[l + 1 < GNC_MAX_LINEAR ? l + 1 : 0], d.out_dim[l + 1 < GNC_MAX_LINEAR ? l + 1 : 0], nullptr, 0, 0, 0, tile);
-              else load_rows(cur, b.grad_out, b.ld_grad_out, nullptr, 0, 0, 0, tile);
-#pragma unroll
-              for (int cb = 0; cb < 4; ++cb)
-                if (4 * cc + cb < NTL) hid[4 * cc + cb < NTL ? 4 * cc + cb : 0] = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * cb + 4 * g);
-              compiler_lds_barrier();
-            } else {
-#pragma unroll
-              for (int cb = 0; cb < 4; ++cb)
-                if (4 * cc + cb < NTL) hid[4 * cc + cb < NTL ? 4 * cc + cb : 0] = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-          }
-          relu_mask16<NTL>(hid, mask[l]);  // values are post-ReLU already: this only forms the bit masks
-        }
-      }
-    } else {
     // ------------------------------------------------------------------ forward recompute: first Linear
     init_bias16<NTL>(hid, pbuf, g);
     auto stage_and_advance = [&](int st) {
@@ -423,8 +390,7 @@ __global__ __launch_bounds__(NT16) void mlp_backward_stream16_kernel(const gnc_m
         emit(hid, b.act[l], d.out_dim[l], d.out_dim[l], row0);
       }
     }
-    }  // forward recompute
-    B16P(0);  // saved tiles -> masks (or the forward recompute)
+    B16P(0);  // forward recompute
 
     // ------------------------------------------------------------------ grad_out tile (slab by slab), LayerNorm backward
     f32x4 gr[NTL];
@@ -440,7 +406,7 @@ __global__ __launch_bounds__(NT16) void mlp_backward_stream16_kernel(const gnc_m
             ids[k] = ids_next[k];
             if (k < d.num_segments) ids_next[k] = load_idx(ntile + (int)gridDim.x, k);
           }
-          load_first(cur, ntile);
+          load_step(cur, 0, ntile);
         }
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
@@ -1020,8 +986,6 @@ __global__ __launch_bounds__(NT16) void mlp_backward_saved16_kernel(const gnc_ml
   }
 }
 
-bool al16b(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 bool make_plan(const gnc_mlp_desc_t& d, bool want_dx, BPlan16* pl, bool saved = false) {
   const int L = d.num_linear;
   if (L < 2 || L > GNC_MAX_LINEAR - 1 || d.activation != GNC_ACT_RELU || d.rows < 1 || d.rows >= INT32_MAX - (1 << 22)) return false;
@@ -1029,13 +993,13 @@ bool make_plan(const gnc_mlp_desc_t& d, bool want_dx, BPlan16* pl, bool saved = 
   for (int l = 0; l < L; ++l) {
     if (d.out_dim[l] > wmax) wmax = d.out_dim[l];
     if (l > 0 && d.in_dim[l] > wmax) wmax = d.in_dim[l];
-    if (ldw_of(d, l) % 4 != 0 || !al16b(d.weight[l])) return false;
+    if (ldw_of(d, l) % 4 != 0 || !al16(d.weight[l])) return false;
   }
   if (wmax > 256) return false;
   *pl = BPlan16{};
   for (int s = 0; s < d.num_segments; ++s) {  // MATMUL segments first, chunk by chunk
     const gnc_mlp_segment_t& sg = d.seg[s];
-    if (sg.ld % 4 != 0 || !al16b(sg.ptr)) return false;
+    if (sg.ld % 4 != 0 || !al16(sg.ptr)) return false;
     if (sg.index && (sg.table_rows <= 0 || sg.table_rows * (int64_t)sg.ld * 4 > 0xffffffffll)) return false;
     if (sg.mode == GNC_SEG_ADD) continue;
     if (sg.wcol % 4 != 0) return false;
@@ -1117,10 +1081,8 @@ int gnc_mlp::launch_bwd_stream16(const gnc_mlp_desc_t& d, const BwdArgs& b, hipS
     kernel<<<dim3((unsigned)grid), dim3(NT16), smem, stream>>>(d, b, pl, (int)num_tiles);
     return GNC_OK;
   };
-  static bool attr_rc = false, attr_sv = false, attr_s3 = false;
-  static const bool first_saved = getenv("GNC_B16_FIRST_SAVED") != nullptr;  // A/B switch: the round-2 SAVED instance
-  const int rc = saved ? (first_saved ? go(&mlp_backward_stream16_kernel<NTL, true>, &attr_sv) : go(&mlp_backward_saved16_kernel<NTL>, &attr_s3))
-                       : go(&mlp_backward_stream16_kernel<NTL, false>, &attr_rc);
+  static bool attr_rc = false, attr_sv = false;
+  const int rc = saved ? go(&mlp_backward_saved16_kernel<NTL>, &attr_sv) : go(&mlp_backward_stream16_kernel<NTL>, &attr_rc);
   if (rc) return rc;
   return gnc::check_launch("mlp_backward_stream16_kernel");
 }

@@ -39,8 +39,6 @@ int launch_fused_saved(const gnc_mlp_desc_t& d, const BwdArgs& b, const FusedOut
 
 namespace {
 
-inline bool fused_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 // ---------------------------------------------------------------------------------------------------
 // Fused variant for the shape that dominates training (widths 33..64, three Linear layers, ONE row-ordered
 // MATMUL segment that may also be the residual, plus 0 or 2 gathered ADD segments): the weight gradients are
@@ -577,10 +575,10 @@ int fused_shape(const gnc_mlp_desc_t& d) {
     if (d.out_dim[l] > KC || (l > 0 && d.in_dim[l] > KC)) return -1;
   if (d.num_segments != 1 && d.num_segments != 3) return -1;
   const gnc_mlp_segment_t& s0 = d.seg[0];
-  if (s0.mode != GNC_SEG_MATMUL || s0.index || s0.width > KC || s0.ld % 4 != 0 || !fused_al16(s0.ptr)) return -1;
+  if (s0.mode != GNC_SEG_MATMUL || s0.index || s0.width > KC || s0.ld % 4 != 0 || !al16(s0.ptr)) return -1;
   for (int s = 1; s < d.num_segments; ++s) {
     const gnc_mlp_segment_t& g = d.seg[s];
-    if (g.mode != GNC_SEG_ADD || !g.index || g.width > KC || g.ld % 4 != 0 || !fused_al16(g.ptr)) return -1;
+    if (g.mode != GNC_SEG_ADD || !g.index || g.width > KC || g.ld % 4 != 0 || !al16(g.ptr)) return -1;
     if (g.table_rows <= 0 || g.table_rows * (int64_t)g.ld * 4 > 0xffffffffll) return -1;
   }
   return d.num_segments - 1;

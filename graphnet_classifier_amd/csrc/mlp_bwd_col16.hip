@@ -60,6 +60,7 @@ struct BPlan {
 
 __device__ __attribute__((aligned(16))) float gnc_bcol_dummy[4];
 
+// NT: waves per workgroup - 8 is the only size launched (widths 65..128)
 template <int NT>
 __global__ __launch_bounds__(NT * 64) void mlp_bwd_col16_kernel(const BPlan p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -581,8 +582,6 @@ int launch_b(const BPlan& p, hipStream_t stream) {
   return gnc::check_launch("mlp_bwd_col16_kernel");
 }
 
-bool al16b(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-
 int last_matmul(const gnc_mlp_desc_t& d) {
   int last = -1;
   for (int s = 0; s < d.num_segments; ++s)
@@ -600,15 +599,14 @@ bool gnc_mlp::bwd_col16_supported(const gnc_mlp_desc_t& d) {
   const int L = d.num_linear;
   if (L < 2 || L > NTR) return false;
   const int H = d.out_dim[0], od = d.out_dim[L - 1];
-  static const bool narrow = getenv("GNC_COL16_D64") != nullptr;
-  if (H > 128 || od > 128 || H % 4 != 0 || (!narrow && H <= 64 && od <= 64)) return false;
+  if (H > 128 || od > 128 || H % 4 != 0 || (H <= 64 && od <= 64)) return false;
   const int n0 = (d.in_dim[0] + CK - 1) / CK;
   if ((L - 1) + n0 > NTR) return false;
   for (int l = 0; l < L; ++l) {
     const int ldw = ldw_of(d, l);
     if ((int64_t)d.out_dim[l] * ldw * 4 > 0x7fffffffll) return false;
   }
-  if (d.ln_gamma && (ldw_of(d, L - 1) % 4 != 0 || !al16b(d.weight[L - 1]))) return false;  // the forward chunk: 16-B pieces
+  if (d.ln_gamma && (ldw_of(d, L - 1) % 4 != 0 || !al16(d.weight[L - 1]))) return false;  // the forward chunk: 16-B pieces
   const int lm = last_matmul(d);
   if (lm < 0) return false;
   // a residual's gradient lands on whole chunks of dx only
@@ -625,10 +623,10 @@ bool gnc_mlp::bwd_col16_persist_supported(const gnc_mlp_desc_t& d) {
   if (off || d.rows <= bwd_col16_max_rows() || d.rows >= INT32_MAX / 2) return false;
   if (d.num_linear != 3 || !d.ln_gamma || !d.ln_beta) return false;
   for (int l = 0; l < 3; ++l)
-    if (d.out_dim[l] != 128 || (l > 0 && d.in_dim[l] != 128) || (l == 2 && (ldw_of(d, l) % 4 != 0 || !al16b(d.weight[l]))) ||
+    if (d.out_dim[l] != 128 || (l > 0 && d.in_dim[l] != 128) || (l == 2 && (ldw_of(d, l) % 4 != 0 || !al16(d.weight[l]))) ||
         (int64_t)128 * ldw_of(d, l) * 4 > 0x7fffffffll)
       return false;
-  if (d.in_dim[0] > 256 || !al16b(d.ln_gamma) || (d.bias[2] && !al16b(d.bias[2]))) return false;
+  if (d.in_dim[0] > 256 || !al16(d.ln_gamma) || (d.bias[2] && !al16(d.bias[2]))) return false;
   const int lm = last_matmul(d);
   if (lm < 0) return false;
   // a residual's gradient is folded into dx only as the whole (one) chunk
@@ -641,11 +639,11 @@ int gnc_mlp::launch_bwd_col16_persist(const gnc_mlp_bwd_desc_t& bd, hipStream_t 
   const gnc_mlp_desc_t& d = bd.fwd;
   constexpr int D = 128;
   GNC_REQUIRE(bd.grad_out || bd.grad_gather, "gnc_mlp_backward_f32: grad_out is null");
-  GNC_REQUIRE(!bd.grad_out || (bd.ld_grad_out % 4 == 0 && al16b(bd.grad_out) && bd.ld_grad_out >= D),
+  GNC_REQUIRE(!bd.grad_out || (bd.ld_grad_out % 4 == 0 && al16(bd.grad_out) && bd.ld_grad_out >= D),
               "gnc_mlp_backward_f32: grad_out must be 16-B aligned with ld %% 4 == 0");
-  GNC_REQUIRE(!bd.grad_gather || (bd.ld_grad_gather % 4 == 0 && al16b(bd.grad_gather) && bd.grad_gather_index && bd.ld_grad_gather >= D),
+  GNC_REQUIRE(!bd.grad_gather || (bd.ld_grad_gather % 4 == 0 && al16(bd.grad_gather) && bd.grad_gather_index && bd.ld_grad_gather >= D),
               "gnc_mlp_backward_f32: grad_gather must be 16-B aligned with ld %% 4 == 0");
-  GNC_REQUIRE(bd.ln_partial && al16b(bd.ln_partial), "gnc_mlp_backward_f32: ln_partial is required (gnc_mlp_backward_ln_partial_rows rows)");
+  GNC_REQUIRE(bd.ln_partial && al16(bd.ln_partial), "gnc_mlp_backward_f32: ln_partial is required (gnc_mlp_backward_ln_partial_rows rows)");
   GNC_REQUIRE(!bd.dx || bd.ld_dx >= d.in_dim[0], "gnc_mlp_backward_f32: ld_dx < in_dim[0]");
   BPlan p = {};
   p.rows = (int)d.rows;
@@ -653,15 +651,15 @@ int gnc_mlp::launch_bwd_col16_persist(const gnc_mlp_bwd_desc_t& bd, hipStream_t 
   p.L = 3; p.H = D; p.od = D;
   p.n0 = bd.dx ? (d.in_dim[0] > CK ? 2 : 1) : 0;
   p.k_in = d.in_dim[0];
-  p.vec_dx = (bd.dx && bd.ld_dx % 4 == 0 && d.in_dim[0] % 4 == 0 && al16b(bd.dx)) ? 1 : 0;
+  p.vec_dx = (bd.dx && bd.ld_dx % 4 == 0 && d.in_dim[0] % 4 == 0 && al16(bd.dx)) ? 1 : 0;
   p.has_ln = 1;
   p.has_g = bd.grad_out ? 1 : 0;
   p.has_gg = bd.grad_gather ? 1 : 0;
   for (int l = 0; l < 3; ++l) {
-    GNC_REQUIRE(bd.dz[l] && al16b(bd.dz[l]), "gnc_mlp_backward_f32: dz[%d] must be given, 16-B aligned", l);
+    GNC_REQUIRE(bd.dz[l] && al16(bd.dz[l]), "gnc_mlp_backward_f32: dz[%d] must be given, 16-B aligned", l);
     p.dz[l] = bd.dz[l];
     if (l < 2) {
-      GNC_REQUIRE(bd.act[l] && al16b(bd.act[l]), "gnc_mlp_backward_f32: act[%d] must be given, 16-B aligned", l);
+      GNC_REQUIRE(bd.act[l] && al16(bd.act[l]), "gnc_mlp_backward_f32: act[%d] must be given, 16-B aligned", l);
       p.act[l] = bd.act[l];
     }
   }
@@ -720,7 +718,7 @@ int gnc_mlp::launch_bwd_col16(const gnc_mlp_bwd_desc_t& bd, hipStream_t stream) 
   GNC_REQUIRE(bd.grad_out || bd.grad_gather, "gnc_mlp_backward_f32: grad_out is null");
   GNC_REQUIRE(!bd.grad_out || (bd.ld_grad_out >= od && (int64_t)d.rows * bd.ld_grad_out * 4 <= 0x7fffffffll),
               "gnc_mlp_backward_f32: grad_out: ld < out_dim (or a table beyond 2 GiB)");
-  GNC_REQUIRE(!bd.grad_gather || (bd.ld_grad_gather % 4 == 0 && al16b(bd.grad_gather) && bd.grad_gather_index && bd.ld_grad_gather >= od),
+  GNC_REQUIRE(!bd.grad_gather || (bd.ld_grad_gather % 4 == 0 && al16(bd.grad_gather) && bd.grad_gather_index && bd.ld_grad_gather >= od),
               "gnc_mlp_backward_f32: grad_gather must be 16-B aligned with ld %% 4 == 0");
   GNC_REQUIRE(!d.ln_gamma || bd.ln_partial, "gnc_mlp_backward_f32: the small-batch kernel forms the LayerNorm sums itself (ln_partial)");
   GNC_REQUIRE(!bd.dx || bd.ld_dx >= d.in_dim[0], "gnc_mlp_backward_f32: ld_dx < in_dim[0]");
@@ -737,10 +735,10 @@ int gnc_mlp::launch_bwd_col16(const gnc_mlp_bwd_desc_t& bd, hipStream_t stream) 
     p.out_dim[l] = d.out_dim[l];
     p.in_dim[l] = d.in_dim[l];
     GNC_REQUIRE(bd.dz[l], "gnc_mlp_backward_f32: dz[%d] is null", l);
-    GNC_REQUIRE(al16b(bd.dz[l]), "gnc_mlp_backward_f32: dz[%d] must be 16-B aligned", l);
+    GNC_REQUIRE(al16(bd.dz[l]), "gnc_mlp_backward_f32: dz[%d] must be 16-B aligned", l);
     p.dz[l] = bd.dz[l];
     if (l < L - 1) {
-      GNC_REQUIRE(bd.act[l] && al16b(bd.act[l]), "gnc_mlp_backward_f32: act[%d] must be given, 16-B aligned", l);
+      GNC_REQUIRE(bd.act[l] && al16(bd.act[l]), "gnc_mlp_backward_f32: act[%d] must be given, 16-B aligned", l);
       p.act[l] = bd.act[l];
     }
   }
@@ -768,7 +766,7 @@ int gnc_mlp::launch_bwd_col16(const gnc_mlp_bwd_desc_t& bd, hipStream_t stream) 
   p.gg_rows = bd.grad_gather_rows > INT32_MAX ? (uint32_t)INT32_MAX : (uint32_t)bd.grad_gather_rows;
   p.dx = bd.dx;
   p.ld_dx = bd.ld_dx;
-  p.vec_dx = (bd.dx && bd.ld_dx % 4 == 0 && d.in_dim[0] % 4 == 0 && al16b(bd.dx)) ? 1 : 0;
+  p.vec_dx = (bd.dx && bd.ld_dx % 4 == 0 && d.in_dim[0] % 4 == 0 && al16(bd.dx)) ? 1 : 0;
   p.dx_add_chunk = -1;
   if (bd.dx && bd.dx_add_grad_out) {
     const int lm = last_matmul(d);
@@ -777,6 +775,5 @@ int gnc_mlp::launch_bwd_col16(const gnc_mlp_bwd_desc_t& bd, hipStream_t stream) 
     p.dx_add_chunk = d.seg[lm].wcol / CK;
   }
   p.ln_partial = d.ln_gamma ? bd.ln_partial : nullptr;
-  const int wmax = H > od ? H : od;
-  return wmax <= 64 ? launch_b<4>(p, stream) : launch_b<8>(p, stream);
+  return launch_b<8>(p, stream);
 }

@@ -35,7 +35,7 @@ constexpr int CK = 128;        // k columns of one register-resident weight chun
 constexpr int NKB = CK / 16;   // its 16-wide k blocks
 constexpr int NQ = 4;          // weight chunks of one tile: ceil(in_dim[0] / CK) + num_linear - 1 <= NQ
 constexpr int NSET = 3;        // register sets: chunk q lives in set q % NSET (chunk 3 is requested when chunk 0 has been consumed)
-constexpr int MAXPASS = 8;     // staging passes of the narrowest workgroup (4 waves: 64 columns per pass, NQ * CK columns)
+constexpr int MAXPASS = 8;     // ColPlan::ps entries (NQ * CK columns at 64 per pass); the 8-wave workgroups use the first 4
 
 struct ColChunk {   // one weight chunk: 16 rows per wave x CK columns
   const float* w;   // weight[l] + first column of the chunk
@@ -141,13 +141,14 @@ extern "C" int gnc_col_probe_read(void* dst, size_t bytes) {
 #define CPROBE(k) do {} while (0)
 #endif
 
+// NT: waves per workgroup - 8 is the only size launched (widths 65..128; the weights-resident kernel takes <= 64)
 template <int NT, bool SAVE, bool IDX, class S = ShapeAny>
 __global__ __launch_bounds__(NT * 64) void mlp_col16_kernel(const ColPlan p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int NTV = NT * 64;
   constexpr int LDH = NT * 16 + 4;
   constexpr int CPP = NTV / 16;               // staging: 16-B pieces of a row per pass
-  constexpr int NPASS = NQ * CK / (CPP * 4);  // 4 (8 waves) or 8 (4 waves)
+  constexpr int NPASS = NQ * CK / (CPP * 4);  // 4 (NT = 8 waves, the only workgroup size launched)
   const int tid0 = threadIdx.x;
   const int w = __builtin_amdgcn_readfirstlane(tid0 >> 6);
   const int rows = p.rows;
@@ -518,17 +519,11 @@ int launch_col(const ColPlan& p, hipStream_t stream) {
   return gnc::check_launch("mlp_col16_kernel");
 }
 
-template <int NT>
-int launch_col_nt(const ColPlan& p, bool save, bool idx, hipStream_t stream) {
-  if (idx) return save ? launch_col<NT, true, true>(p, stream) : launch_col<NT, false, true>(p, stream);
-  return save ? launch_col<NT, true, false>(p, stream) : launch_col<NT, false, false>(p, stream);
-}
-
 // the default model's launch shapes (ShapeProj .. ShapeDec): 0 = none of them
 enum { SHAPE_ANY = 0, SHAPE_PROJ, SHAPE_EDGE, SHAPE_NODE, SHAPE_ENC, SHAPE_DEC };
-int shape_of(const ColPlan& p, int nt, bool save, bool idx, bool row_ids) {
+int shape_of(const ColPlan& p, bool save, bool idx, bool row_ids) {
   static const bool off = getenv("GNC_COL16_NO_SHAPES") != nullptr;  // A/B: run-time shapes only
-  if (off || nt != 8 || p.H != 128 || row_ids) return SHAPE_ANY;
+  if (off || p.H != 128 || row_ids) return SHAPE_ANY;
   const bool ln = p.gamma != nullptr, res = p.residual != nullptr;
   if (p.L == 1 && p.k_in == 128 && p.nadd == 0 && !ln && !res && p.vec_stage && !p.narrow_w0 && !idx && !save && p.vec_out)
     return SHAPE_PROJ;
@@ -543,7 +538,6 @@ int shape_of(const ColPlan& p, int nt, bool save, bool idx, bool row_ids) {
   return SHAPE_ANY;
 }
 
-bool al16h(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 uint32_t rows32(int64_t r) { return r > INT32_MAX ? (uint32_t)INT32_MAX : (uint32_t)r; }
 
 }  // namespace
@@ -576,13 +570,10 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
   const int L = d.num_linear;
   if (L > 1 && d.activation != GNC_ACT_RELU) return GNC_OK;
   const int H = d.out_dim[0], od = d.out_dim[L - 1];
-  static const bool narrow = getenv("GNC_COL16_D64") != nullptr;  // A/B: also widths <= 64 (weights-resident kernel otherwise)
-  if (H > 128 || od > 128 || (!narrow && H <= 64 && od <= 64)) return GNC_OK;
+  if (H > 128 || od > 128 || (H <= 64 && od <= 64)) return GNC_OK;  // widths <= 64: the weights-resident kernel
   const int n0 = (d.in_dim[0] + CK - 1) / CK;
   if (n0 + L - 1 > NQ) return GNC_OK;  // (the default model: 1 + 2 everywhere, 2 + 2 for the node processor's [x | agg])
-  const int wmax = H > od ? H : od;
-  const int nt = wmax <= 64 ? 4 : 8;
-  const int pw = nt * 16;  // columns of one staging pass
+  const int pw = 8 * 16;  // columns of one staging pass (8-wave workgroups)
 
   ColPlan p = {};
   p.rows = (int)d.rows;
@@ -598,7 +589,7 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
     p.out_dim[l] = d.out_dim[l];
     p.in_dim[l] = d.in_dim[l];
     p.bias[l] = d.bias[l];
-    if (ldw % 4 == 0 && al16h(d.weight[l])) continue;  // rows of 16-B pieces (a width that is not a multiple of 4 is masked)
+    if (ldw % 4 == 0 && al16(d.weight[l])) continue;  // rows of 16-B pieces (a width that is not a multiple of 4 is masked)
     if (l == 0 && d.in_dim[0] <= 16) p.narrow_w0 = 1;
     else return GNC_OK;
   }
@@ -620,13 +611,13 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
   for (int s = 0; s < d.num_segments; ++s) {
     const gnc_mlp_segment_t& sg = d.seg[s];
     if (sg.mode == GNC_SEG_ADD) {
-      if (sg.width != H || H % 4 != 0 || sg.ld % 4 != 0 || !al16h(sg.ptr) || p.nadd >= GNC_MAX_SEGMENTS) return GNC_OK;
+      if (sg.width != H || H % 4 != 0 || sg.ld % 4 != 0 || !al16(sg.ptr) || p.nadd >= GNC_MAX_SEGMENTS) return GNC_OK;
       p.ad[p.nadd++] = {sg.ptr, sg.index, sg.index ? rows32(sg.table_rows) : (uint32_t)INT32_MAX, sg.ld};
       continue;
     }
     if (sg.wcol < 0 || sg.wcol + sg.width > d.in_dim[0]) return GNC_OK;
     p.sg[p.nseg++] = {sg.ptr, sg.index, sg.index ? rows32(sg.table_rows) : (uint32_t)INT32_MAX, sg.width, sg.ld, sg.wcol};
-    if (sg.ld % 4 != 0 || sg.width % 4 != 0 || sg.wcol % pw != 0 || !al16h(sg.ptr)) p.vec_stage = 0;
+    if (sg.ld % 4 != 0 || sg.width % 4 != 0 || sg.wcol % pw != 0 || !al16(sg.ptr)) p.vec_stage = 0;
   }
   if (p.vec_stage) {
     for (int s = 0; s < p.nseg; ++s) {
@@ -646,7 +637,7 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
   p.eps = d.ln_eps;
   p.res_xcol = -1;
   if (d.residual) {
-    if (d.ld_residual % 4 != 0 || od % 4 != 0 || !al16h(d.residual)) return GNC_OK;
+    if (d.ld_residual % 4 != 0 || od % 4 != 0 || !al16(d.residual)) return GNC_OK;
     p.residual = d.residual;
     p.ld_res = d.ld_residual;
     for (int s = 0; s < p.nseg; ++s)  // the residual is one of the staged row-ordered tables: its rows are in the input tile
@@ -655,12 +646,12 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
   }
   p.out = d.out;
   p.ld_out = d.ld_out;
-  p.vec_out = (d.ld_out % 4 == 0 && od % 4 == 0 && al16h(d.out)) ? 1 : 0;
+  p.vec_out = (d.ld_out % 4 == 0 && od % 4 == 0 && al16(d.out)) ? 1 : 0;
   const bool save = d.save_act[0] != nullptr;
   if (save) {
     if (L < 2 || H % 4 != 0) return GNC_OK;
     for (int l = 0; l < L - 1; ++l) {
-      if (!d.save_act[l] || !al16h(d.save_act[l])) return GNC_OK;
+      if (!d.save_act[l] || !al16(d.save_act[l])) return GNC_OK;
       p.save[l] = d.save_act[l];
     }
   }
@@ -671,7 +662,7 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
   for (int s = 0; s < p.nseg; ++s) row_ids = row_ids || p.sg[s].index != nullptr;
   *launched = true;
   if (probe_only) return GNC_OK;
-  switch (shape_of(p, nt, save, idx, row_ids)) {
+  switch (shape_of(p, save, idx, row_ids)) {
     case SHAPE_PROJ: return launch_col<8, false, false, ShapeProj>(p, stream);
     case SHAPE_EDGE: return save ? launch_col<8, true, true, ShapeEdge>(p, stream) : launch_col<8, false, true, ShapeEdge>(p, stream);
     case SHAPE_NODE: return save ? launch_col<8, true, false, ShapeNode>(p, stream) : launch_col<8, false, false, ShapeNode>(p, stream);
@@ -679,7 +670,8 @@ int gnc_mlp::launch_col16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* lau
     case SHAPE_DEC: return save ? launch_col<8, true, false, ShapeDec>(p, stream) : launch_col<8, false, false, ShapeDec>(p, stream);
     default: break;
   }
-  return nt == 4 ? launch_col_nt<4>(p, save, idx, stream) : launch_col_nt<8>(p, save, idx, stream);
+  if (idx) return save ? launch_col<8, true, true>(p, stream) : launch_col<8, false, true>(p, stream);
+  return save ? launch_col<8, true, false>(p, stream) : launch_col<8, false, false>(p, stream);
 }
 
 extern "C" int64_t gnc_mlp_small_batch_max_rows(void) { return gnc_mlp::col16_max_rows(); }
@@ -699,8 +691,8 @@ extern "C" int gnc_mlp_dual_projection_f32(const float* x, int64_t ld_x, int64_t
     if (rc || launched) return rc;
   }
   if (off || !x || !wa || !wb || !out_a || !out_b || rows < 1 || rows > gnc_mlp::col16_max_rows() || in_dim != 128 || out_dim != 128 ||
-      ld_wa != ld_wb || ld_wa % 4 != 0 || ld_x % 4 != 0 || ld_out % 4 != 0 || !al16h(x) || !al16h(wa) || !al16h(wb) || !al16h(out_a) ||
-      !al16h(out_b) || (int64_t)128 * ld_wa * 4 > 0x7fffffffll) {
+      ld_wa != ld_wb || ld_wa % 4 != 0 || ld_x % 4 != 0 || ld_out % 4 != 0 || !al16(x) || !al16(wa) || !al16(wb) || !al16(out_a) ||
+      !al16(out_b) || (int64_t)128 * ld_wa * 4 > 0x7fffffffll) {
     gnc::set_error("gnc_mlp_dual_projection_f32: outside the small-batch projection shape (128 -> 128, 16-B rows) and the large-batch one (widths 33..64)");
     return GNC_ERR_UNSUPPORTED;
   }
@@ -732,7 +724,7 @@ extern "C" int gnc_mlp_projection_t2_f32(const float* a, int64_t ld_a, const flo
                                          int64_t ld_w, int32_t hidden, int32_t dn, float* out, int64_t ld_out, void* stream) {
   static const bool off = getenv("GNC_NO_PROJECTION_T2") != nullptr;  // A/B switch
   if (off || !a || !b || !wmat || !out || rows < 1 || rows > gnc_mlp::col16_max_rows() || hidden != 128 || dn != 128 || ld_a % 4 != 0 ||
-      ld_b % 4 != 0 || ld_out % 4 != 0 || ld_w < 2 * dn || !al16h(a) || !al16h(b) || !al16h(out) || (int64_t)128 * ld_w * 4 > 0x7fffffffll) {
+      ld_b % 4 != 0 || ld_out % 4 != 0 || ld_w < 2 * dn || !al16(a) || !al16(b) || !al16(out) || (int64_t)128 * ld_w * 4 > 0x7fffffffll) {
     gnc::set_error("gnc_mlp_projection_t2_f32: outside the small-batch shape (two [rows, 128] tables, W [128, >= 256])");
     return GNC_ERR_UNSUPPORTED;
   }

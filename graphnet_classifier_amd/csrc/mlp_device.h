@@ -872,6 +872,9 @@ struct BwdArgs {
 // smallest of {1,2,4,8} accumulator tiles (32 features each) covering `width`
 __host__ __device__ inline int ldw_of(const gnc_mlp_desc_t& d, int l) { return d.ld_weight[l] ? d.ld_weight[l] : d.in_dim[l]; }
 
+// host: p lies on a 16-B boundary (with an ld that is a multiple of 4, its rows can be read as 16-B pieces)
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 inline int tiles_for(int width) {
   const int t = (width + 31) / 32;
   return t <= 1 ? 1 : t <= 2 ? 2 : t <= 4 ? 4 : 8;

@@ -660,8 +660,6 @@ int launch_cls(int split, const gnc_mlp_desc_t& d, int total_chunks, size_t smem
   return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 0, AGGONLY>(d, total_chunks, smem, stream);
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int gnc_mlp_agg_fix_len(void) { return 2 * gnc::num_cu() * RWAVES; }

@@ -493,8 +493,6 @@ int launch(const gnc_mlp_desc_t& d, const StreamPlan& pl, hipStream_t stream) {
   return gnc::check_launch("mlp_stream_kernel");
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 int gnc_mlp::launch_stream(const gnc_mlp_desc_t& d, int T, bool narrow_out, hipStream_t stream, bool* launched,
@@ -579,10 +577,7 @@ int gnc_mlp::launch_stream(const gnc_mlp_desc_t& d, int T, bool narrow_out, hipS
   switch (T) {
     case 1: return launch<1, 1, 8, true, true>(d, pl, stream);
     case 2: return launch<2, 2, 8, true, true>(d, pl, stream);
-    case 4: {
-      static const bool w4 = getenv("GNC_STREAM_W4") != nullptr;  // A/B: 4 waves x 512 registers instead of 8 x 256
-      return w4 ? launch<4, 4, 4, true, false>(d, pl, stream) : launch<4, 4, 8, true, false>(d, pl, stream);
-    }
+    case 4: return launch<4, 4, 8, true, false>(d, pl, stream);
     default: return launch<8, 8, 4, false, false>(d, pl, stream);
   }
 }

@@ -445,8 +445,6 @@ int launch16(const gnc_mlp_desc_t& d, const Plan16& pl, hipStream_t stream) {
   return gnc::check_launch("mlp_stream16_kernel");
 }
 
-bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 int gnc_mlp::launch_stream16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* launched, bool probe_only) {
@@ -457,18 +455,18 @@ int gnc_mlp::launch_stream16(const gnc_mlp_desc_t& d, hipStream_t stream, bool* 
   if (L > 1 && d.activation != GNC_ACT_RELU) return GNC_OK;
   const int H = d.out_dim[0], od = d.out_dim[L - 1];
   if (H > 256 || od > 256) return GNC_OK;
-  if (d.residual && (d.ld_residual % 4 != 0 || !al16p(d.residual))) return GNC_OK;
+  if (d.residual && (d.ld_residual % 4 != 0 || !al16(d.residual))) return GNC_OK;
   if (d.save_act[0]) {  // saved post-activations: whole rows of 16-B pieces
     if (L < 2) return GNC_OK;
     for (int l = 0; l < L - 1; ++l)
-      if (!d.save_act[l] || d.out_dim[l] % 4 != 0 || !al16p(d.save_act[l])) return GNC_OK;
+      if (!d.save_act[l] || d.out_dim[l] % 4 != 0 || !al16(d.save_act[l])) return GNC_OK;
   }
   for (int l = 0; l < L; ++l)
-    if (ldw_of(d, l) % 4 != 0 || !al16p(d.weight[l])) return GNC_OK;
+    if (ldw_of(d, l) % 4 != 0 || !al16(d.weight[l])) return GNC_OK;
   Plan16 pl = {};
   for (int s = 0; s < d.num_segments; ++s) {  // MATMUL segments first, chunk by chunk
     const gnc_mlp_segment_t& sg = d.seg[s];
-    if (sg.ld % 4 != 0 || !al16p(sg.ptr)) return GNC_OK;
+    if (sg.ld % 4 != 0 || !al16(sg.ptr)) return GNC_OK;
     if (sg.mode == GNC_SEG_ADD) continue;
     if (sg.wcol % 4 != 0) return GNC_OK;
     for (int c0 = 0; c0 < sg.width; c0 += KC) {
