@@ -319,13 +319,29 @@ class CapturedForward:
     no destination becomes a hub); the topology build - device flags, no host sync - is part of the graph, so a replay
     sorts whatever edge list the buffer holds.  Dummy rows only talk to dummies and are dropped from the result, which is
     therefore the plain forward's, bit for bit.  ``check()`` reads the flags of the last replay (ids outside the graph).
+
+    ``node_capacity`` given as well (a ``CombinedModel`` with ``ragged_readout``): any graph of at most ``node_capacity``
+    nodes and ``edge_capacity`` edges (superpixel graphs: SLIC returns another number of segments per image).  The buffers
+    hold ``node_capacity`` node slots in front of the dummies (and at least the read-out's ``num_nodes`` rows); the slots
+    behind a sample's own nodes are isolated zero-feature nodes, and inside the graph the read-out takes rows
+    ``[0, num_nodes)`` and zeroes those at or behind a device-side count that every call writes in front of the replay -
+    the rule of ``CombinedModel.ragged_readout``.
     """
 
-    def __init__(self, model: nn.Module, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int | None = None):
+    def __init__(self, model: nn.Module, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int | None = None,
+                 node_capacity: int | None = None):
         gnet = model.graph_net if isinstance(model, CombinedModel) else model
         dev = require_gpu_param(next(model.parameters()), "CapturedForward")
         self.model, self.device = model, dev
         self.edge_capacity, self.num_nodes = edge_capacity, int(x.size(0))
+        self.node_capacity = node_capacity
+        if node_capacity is not None:
+            if edge_capacity is None:
+                raise ValueError("CapturedForward: node_capacity requires edge_capacity")
+            if not (isinstance(model, CombinedModel) and model.ragged_readout):
+                raise TypeError("CapturedForward(node_capacity=...): a CombinedModel with ragged_readout = True expected")
+            if self.num_nodes > node_capacity:
+                raise ValueError(f"CapturedForward: {self.num_nodes} nodes exceed node_capacity {node_capacity}")
         if edge_capacity is None:
             self.x = x.to(device=dev, dtype=torch.float32).clone()
             self.pos = pos.to(device=dev, dtype=torch.float32).clone()
@@ -342,20 +358,27 @@ class CapturedForward:
                 # batch statistics span ALL rows: the dummy rows would enter them (eval mode normalises row by row)
                 raise NotImplementedError("CapturedForward(edge_capacity=...): a BatchNorm model must be in eval() mode")
             dummies = max(1, (edge_capacity + 7) // 8)
-            self.x = torch.zeros(n + dummies, *x.shape[1:], dtype=torch.float32, device=dev)
-            self.pos = torch.zeros(n + dummies, *pos.shape[1:], dtype=torch.float32, device=dev)
-            self._tail = n + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies
+            slots = n if node_capacity is None else node_capacity  # node slots in front of the dummies
+            rows = slots + dummies if node_capacity is None else max(slots + dummies, model.num_nodes)
+            self.x = torch.zeros(rows, *x.shape[1:], dtype=torch.float32, device=dev)
+            self.pos = torch.zeros(rows, *pos.shape[1:], dtype=torch.float32, device=dev)
+            self._tail = slots + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies
             self.edge_index = self._tail.repeat(2, 1)
             self.x[:n].copy_(x)
             self.pos[:n].copy_(pos)
             self.edge_index[:, :e].copy_(edge_index)
             self.topo, self._status = None, None
             self._range_flag = torch.zeros((), dtype=torch.bool, device=dev)
+            self._filled = n                                                        # rows of x / pos that hold a sample
+            self.valid_nodes = torch.full((), n, dtype=torch.int64, device=dev)    # read inside the graph (node_capacity form)
 
             def run():
-                topo = GraphTopology(self.edge_index, n + dummies, device=dev, validate="deferred")  # never the cache
+                topo = GraphTopology(self.edge_index, rows, device=dev, validate="deferred")  # never the cache
                 self._status = topo.status  # the capture's own flags: every replay rewrites them
-                y = gnet.forward_device(self.x, self.pos, topo)[:n]
+                y = gnet.forward_device(self.x, self.pos, topo)
+                if node_capacity is not None:
+                    return model.classifier(masked_readout_rows(y, model.num_nodes, self.valid_nodes).flatten())
+                y = y[:n]
                 return model.classifier(y.flatten()) if isinstance(model, CombinedModel) else y
 
         with torch.no_grad():
@@ -376,8 +399,22 @@ class CapturedForward:
                 self.pos.copy_(pos, non_blocking=True)
         else:
             n = self.num_nodes
-            if x.size(0) != n:
-                raise ValueError(f"CapturedForward: {x.size(0)} nodes, captured for {n}")
+            if self.node_capacity is None:
+                if x.size(0) != n:
+                    raise ValueError(f"CapturedForward: {x.size(0)} nodes, captured for {n}")
+            else:
+                n = self.num_nodes = int(x.size(0))
+                if n > self.node_capacity:
+                    raise ValueError(f"CapturedForward: {n} nodes exceed node_capacity {self.node_capacity}")
+                if edge_index is None or pos is None:
+                    raise ValueError("CapturedForward(node_capacity=...): every call needs x, pos and edge_index")
+                if int(edge_index.size(1)) > self.edge_capacity:
+                    raise ValueError(f"CapturedForward: {int(edge_index.size(1))} edges exceed edge_capacity {self.edge_capacity}")
+                if n < self._filled:  # a smaller graph after a larger one: its slots become isolated zero nodes again
+                    self.x[n:self._filled].zero_()
+                    self.pos[n:self._filled].zero_()
+                self._filled = n
+                self.valid_nodes.fill_(n)
             self.x[:n].copy_(x, non_blocking=True)
             if pos is not None:
                 self.pos[:n].copy_(pos, non_blocking=True)
@@ -406,6 +443,22 @@ class CapturedForward:
 
 
 # --------------------------------------------------------------------------- a8 read-out
+def ragged_readout_rows(y: Tensor, num_nodes: int) -> Tensor:
+    """The read-out rule for a graph whose node count is not ``num_nodes`` (``forward_batched(graph_ptr=...)``'s): the
+    first ``num_nodes`` rows of ``y`` [N, out_dim], zero rows behind a smaller graph.  Differentiable."""
+    n = y.size(0)
+    if n >= num_nodes:
+        return y[:num_nodes]
+    return torch.cat([y, y.new_zeros(num_nodes - n, *y.shape[1:])])
+
+
+def masked_readout_rows(y: Tensor, num_nodes: int, valid_nodes: Tensor) -> Tensor:
+    """The same rule on fixed shapes, for a hipGraph: rows ``[0, num_nodes)`` of a padded ``y``, those at or behind the
+    DEVICE count ``valid_nodes`` replaced by zeros (a select, not a product: no ``-0.0`` from a negative row)."""
+    keep = torch.arange(num_nodes, device=y.device) < valid_nodes
+    return torch.where(keep[:, None], y[:num_nodes], y.new_zeros(()))
+
+
 class LinearClassifier(nn.Module):
     def __init__(self, in_features=128 * 128, classes=2):
         """models/GNN.py:312-325; three small dense layers left to PyTorch-ROCm."""
@@ -434,6 +487,10 @@ class CombinedModel(nn.Module):
         self.num_nodes = num_nodes
         in_features = num_nodes * self.graph_net.out_dim
         self.classifier = LinearClassifier(in_features=in_features, classes=classes)
+        # True: ``forward`` accepts a graph of any node count N and feeds fc1 rows [0, min(N, num_nodes)) of the GraphNet
+        # output, the rest of the vector zero (forward_batched(graph_ptr=...)'s rule; the reference's read-out is only
+        # defined for N == num_nodes).  A plain attribute, not a constructor argument and not in the state_dict.
+        self.ragged_readout = False
         self.to(next(self.graph_net.parameters()).device)
 
     def forward(self, x, pos=None, edge_index=None):
@@ -445,8 +502,10 @@ class CombinedModel(nn.Module):
         x = x.to(device=dev, dtype=torch.float32)
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
-        y = self.graph_net.forward_device(x, pos, topo).flatten()
-        logits = self.classifier(y)
+        y = self.graph_net.forward_device(x, pos, topo)
+        if self.ragged_readout and y.size(0) != self.num_nodes:
+            y = ragged_readout_rows(y, self.num_nodes)  # full num_nodes * out_dim length: dW1 keeps fc1.weight's layout
+        logits = self.classifier(y.flatten())
         return logits if back == dev else logits.to(back)
 
     def forward_batched(self, x, pos, edge_index, num_graphs: int | None = None, graph_ptr: Tensor | None = None):

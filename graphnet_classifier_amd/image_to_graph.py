@@ -14,6 +14,7 @@ the resize and SLIC run as batched launches.
 """
 from __future__ import annotations
 
+import collections
 import functools
 
 import numpy as np
@@ -173,6 +174,84 @@ def slic(image_u8, n_segments: int = 100, compactness: float = 10, max_iter: int
     return (labels, counts) if return_counts else labels
 
 
+SuperpixelGraphBatch = collections.namedtuple("SuperpixelGraphBatch", "x pos edge_index counts")
+
+# what one launch of gnc_rag_build_batched takes (csrc/rag_batched.hip)
+RAG_BATCHED_MAX_NODES, RAG_BATCHED_MAX_EDGES = 512, 4096
+
+
+def superpixel_capacities(n_segments: int) -> tuple[int, int]:
+    """Node and edge capacities of the batched region-graph build for ``slic(n_segments=...)`` images, chosen on the
+    host.  SLIC hands out about ``n_segments`` labels (its grid rounds, and the connectivity pass merges and splits: the
+    fixture graphs have 0.69 - 1.19 x n_segments nodes), a planar region adjacency has fewer than 3 undirected = 6
+    directed edges per node (the fixtures: 4.5 - 4.9).  1.5 x and 8 x leave room on both; a graph that still does not fit
+    is flagged by the kernel and built by the per-image path."""
+    n = max(1, int(n_segments))
+    nodes = min(RAG_BATCHED_MAX_NODES, (n * 3 // 2 + 31) // 32 * 32)
+    edges = min(RAG_BATCHED_MAX_EDGES, (nodes * 8 + 255) // 256 * 256)
+    return nodes, edges
+
+
+def superpixel_graphs_batched(images_u8, labels=None, *, n_segments: int = 100, compactness: float = 10,
+                              node_capacity: int, edge_capacity: int) -> SuperpixelGraphBatch:
+    """Region graphs of a batch of resized uint8 RGB images ``[B, H, W, 3]`` in ONE launch (csrc/rag_batched.hip), with
+    no host synchronisation: ``x [B, node_capacity, 3]``, ``pos [B, node_capacity, 2]``, ``edge_index [B, 2,
+    edge_capacity]`` and int32 ``counts [B, 4]`` = (nodes, directed edges, bad-label flag, overflow flag) on the device.
+    ``labels`` ``[B, H, W]`` given: the segmentation to use; otherwise the batched ``slic(n_segments, compactness)``.
+
+    Image ``b``'s graph is ``x[b, :nodes]``, ``pos[b, :nodes]``, ``edge_index[b, :, :edges]`` and equals
+    ``superpixel_graph_from_labels`` of that image bit for bit; rows behind it are 0, edge slots -1.  An image whose
+    overflow flag is set reports its true sizes (edges = -1 above 512 nodes) and holds padding only."""
+    lib = native.load_library()
+    img = images_u8 if isinstance(images_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images_u8))
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3:
+        raise ValueError("superpixel_graphs_batched: expected a uint8 RGB batch [B, H, W, 3]")
+    img = img.to(_device()).contiguous()
+    B, H, W, _ = img.shape
+    if labels is None:
+        labels = slic(img, n_segments=n_segments, compactness=compactness, start_label=0)
+    elif not isinstance(labels, torch.Tensor):
+        labels = torch.from_numpy(np.ascontiguousarray(labels))
+    if tuple(labels.shape) != (B, H, W):
+        raise ValueError("superpixel_graphs_batched: expected label images [B, H, W] of the images' size")
+    labels = labels.to(device=img.device, dtype=torch.int32).contiguous()
+    node_capacity, edge_capacity = int(node_capacity), int(edge_capacity)
+    with torch.cuda.device(img.device):
+        nbytes = lib.gnc_rag_batched_workspace_bytes(B, H, W, node_capacity, edge_capacity)
+        if nbytes == 0:
+            raise NotImplementedError(f"superpixel_graphs_batched: {B} images of {H} x {W} at {node_capacity} nodes / "
+                                      f"{edge_capacity} edges is outside the supported set (H*W <= 65536, "
+                                      f"{RAG_BATCHED_MAX_NODES} nodes, {RAG_BATCHED_MAX_EDGES} edges)")
+        x = torch.empty(B, node_capacity, 3, dtype=torch.float32, device=img.device)
+        pos = torch.empty(B, node_capacity, 2, dtype=torch.float32, device=img.device)
+        ei = torch.empty(B, 2, edge_capacity, dtype=torch.int64, device=img.device)
+        counts = torch.empty(B, 4, dtype=torch.int32, device=img.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        native._check(lib.gnc_rag_build_batched(labels.data_ptr(), img.data_ptr(), B, H, W, node_capacity, edge_capacity,
+                                                x.data_ptr(), pos.data_ptr(), ei.data_ptr(), counts.data_ptr(),
+                                                ws.data_ptr(), nbytes, torch.cuda.current_stream(img.device).cuda_stream),
+                      "gnc_rag_build_batched")
+    return SuperpixelGraphBatch(x, pos, ei, counts)
+
+
+def _superpixel_graphs_from_device_batch(imgs: torch.Tensor, labels: torch.Tensor, node_capacity: int, edge_capacity: int):
+    """The loader's list of ``(x, pos, edge_index)`` for a device batch: one batched build, ONE host read of the sizes;
+    an image that does not fit the capacities (or a batch outside the kernel's supported set) takes the per-image path."""
+    B, H, W, _ = imgs.shape
+    if native.load_library().gnc_rag_batched_workspace_bytes(B, H, W, node_capacity, edge_capacity) == 0:
+        return [_superpixel_graph_from_device_labels(im, lab) for im, lab in zip(imgs, labels)]
+    batch = superpixel_graphs_batched(imgs, labels, node_capacity=node_capacity, edge_capacity=edge_capacity)
+    graphs = []
+    for b, (s, e, bad, overflow) in enumerate(batch.counts.tolist()):  # the chunk's one host sync
+        if bad:
+            raise ValueError("label image has values outside [0, H*W)")
+        if overflow:
+            graphs.append(_superpixel_graph_from_device_labels(imgs[b], labels[b]))
+        else:  # contiguous copies: the topology cache and the capture's copies see what the per-image path hands them
+            graphs.append((batch.x[b, :s].contiguous(), batch.pos[b, :s].contiguous(), batch.edge_index[b, :, :e].contiguous()))
+    return graphs
+
+
 def superpixel_graph_from_array(img_u8: np.ndarray, n_segments: int = 100, compactness: float = 10):
     """superpixel.py:29-71 for an already resized uint8 RGB array: device SLIC, then the region graph."""
     labels = slic(img_u8, n_segments=n_segments, compactness=compactness, start_label=0)
@@ -294,12 +373,16 @@ METHODS = ("pixel", "patch", "superpixel")
 
 
 def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128, diagonals: bool = False,
-                       use_cache: bool = True, n_segments: int = 100, patch_size: int = 8, compactness: float = 10):
+                       use_cache: bool = True, n_segments: int = 100, patch_size: int = 8, compactness: float = 10, *,
+                       node_capacity: int | None = None, edge_capacity: int | None = None):
     """Graphs of a batch of decoded uint8 RGB images ``[H_i, W_i, 3]`` (any sizes): a list of ``(x, pos, edge_index)``
     equal to ``image_to_graph_pixel_optimized`` / ``image_to_graph_patch`` / ``image_to_graph_superpixel`` of each
     image, with arguments named as ``utils/dataloader.py``'s ``OptimizedDatasetLoader``.  The resize of the whole
-    batch is one launch (``resize``), superpixel runs one batched ``slic``; pixel and patch nodes are one launch per
-    image, and every superpixel region graph costs one host synchronisation (its sizes depend on the data)."""
+    batch is one launch (``resize``), superpixel runs one batched ``slic`` and one batched region-graph build
+    (``superpixel_graphs_batched`` at capacities derived from ``n_segments``) with ONE host synchronisation per call for
+    the graphs' sizes, which depend on the data; pixel and patch nodes are one launch per image.  A superpixel image
+    that does not fit the capacities is built by the per-image path (one more synchronisation each);
+    ``node_capacity`` / ``edge_capacity`` override the derived capacities (the result does not depend on them)."""
     if method not in METHODS:
         raise ValueError(f"Unknown method: {method}")
     if len(images_u8) == 0:
@@ -310,4 +393,6 @@ def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128
     if method == "patch":
         return [_patch_graph(im, patch_size) for im in imgs]
     labels = slic(imgs, n_segments=n_segments, compactness=compactness, start_label=0)
-    return [_superpixel_graph_from_device_labels(im, lab) for im, lab in zip(imgs, labels)]
+    nodes, edges = superpixel_capacities(n_segments)
+    return _superpixel_graphs_from_device_batch(imgs, labels, nodes if node_capacity is None else int(node_capacity),
+                                                edges if edge_capacity is None else int(edge_capacity))

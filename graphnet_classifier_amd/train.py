@@ -122,6 +122,17 @@ def _same_topology(a: torch.Tensor, b: torch.Tensor) -> bool:
     return a is b or (a.shape == b.shape and a.dtype == b.dtype and a.device == b.device and bool(torch.equal(a, b)))
 
 
+def padded_capacity(needed: int, current: int = 0, quantum: int = 256) -> int:
+    """Capacity of a padded capture for ``needed`` edges (or nodes): ``current`` while that still fits, otherwise half as
+    much again as needed, rounded up to ``quantum`` - room to spare, so that a data set whose sizes vary around a typical
+    value is captured once.  Never below ``needed``, monotone in ``needed``, and a fixed point for every size that
+    fits: ``padded_capacity(m, padded_capacity(n)) == padded_capacity(n)`` for ``m <= padded_capacity(n)``."""
+    needed, current = int(needed), int(current)
+    if needed <= current:
+        return current
+    return (needed * 3 // 2 + quantum - 1) // quantum * quantum
+
+
 def _world(group=None) -> int:
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
 
@@ -164,20 +175,37 @@ class CapturedTrainStep:
     topology per sample: superpixel graphs) - see the comment in ``__init__``.  A custom ``forward`` then receives the PADDED
     buffers (``x`` / ``pos`` with the dummy rows behind the first ``num_nodes``, ``edge_index`` [2, C]); it must build its
     topology from them in every call (``GraphTopology(..., validate="deferred")``, never the cache) and read out the first
-    ``num_nodes`` rows only.  ``check()`` raises the IndexError of a replayed edge list with ids outside the graph."""
+    ``num_nodes`` rows only.  ``check()`` raises the IndexError of a replayed edge list with ids outside the graph.
+
+    ``node_capacity=M`` with it: ANY graph of at most M nodes and C edges (superpixel graphs: SLIC hands out another number
+    of segments per image), for a ``CombinedModel`` with ``ragged_readout`` set.  The buffers hold M node slots in front of
+    the dummies (and at least the read-out's ``num_nodes`` rows); slots behind a sample's own nodes are isolated zero nodes,
+    and the captured read-out takes rows ``[0, num_nodes)`` and zeroes those at or behind the device count ``valid_nodes``
+    that every call writes in front of the replay (``GNN.masked_readout_rows``), so unused rows contribute exact zeros to
+    the logits and to every gradient, as the dummies do.  A custom ``forward`` reads ``valid_nodes`` itself."""
 
     def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, sample, label, loss_sum: torch.Tensor, *,
-                 forward=None, loss_scale: float = 1.0, capture_error_mode: str = "global", edge_capacity: int | None = None):
+                 forward=None, loss_scale: float = 1.0, capture_error_mode: str = "global", edge_capacity: int | None = None,
+                 node_capacity: int | None = None):
         x, pos, edge_index = sample
         dev = require_gpu_param(next(model.parameters()), "CapturedTrainStep")
         fp = optimizer.fp
         self.optimizer = optimizer
         self.edge_index_host = edge_index
         self.edge_capacity = edge_capacity
+        self.node_capacity = node_capacity
         self.num_nodes = int(x.size(0))
+        if node_capacity is not None:
+            if edge_capacity is None:
+                raise ValueError("CapturedTrainStep: node_capacity requires edge_capacity")
+            if forward is None and not getattr(model, "ragged_readout", False):
+                raise TypeError("CapturedTrainStep(node_capacity=...): a CombinedModel with ragged_readout = True (or forward=) expected")
+            if self.num_nodes > node_capacity:
+                raise ValueError(f"CapturedTrainStep: {self.num_nodes} nodes exceed node_capacity {node_capacity}")
         self.label = torch.as_tensor(label).to(dev).clone()
         self.loss_sum = loss_sum
         self.collective_outside = _world(fp.reducer.group) > 1
+        from .GNN import masked_readout_rows
         from .topology import GraphTopology, get_topology
         if edge_capacity is None:
             self.x = x.to(device=dev, dtype=torch.float32).clone()
@@ -204,20 +232,28 @@ class CapturedTrainStep:
             if forward is None and not (hasattr(model, "graph_net") and hasattr(model, "classifier")):
                 raise TypeError("CapturedTrainStep(edge_capacity=...): pass forward= for a module that is not a CombinedModel")
             dummies = max(1, (edge_capacity + 7) // 8)
-            self.x = torch.zeros(n + dummies, *x.shape[1:], dtype=torch.float32, device=dev)
-            self.pos = torch.zeros(n + dummies, *pos.shape[1:], dtype=torch.float32, device=dev)
-            self._tail = n + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies  # slot k's dummy self-loop
+            slots = n if node_capacity is None else node_capacity  # node slots in front of the dummies
+            rows = slots + dummies
+            if node_capacity is not None and hasattr(model, "num_nodes"):
+                rows = max(rows, int(model.num_nodes))  # the read-out takes rows [0, num_nodes)
+            self.x = torch.zeros(rows, *x.shape[1:], dtype=torch.float32, device=dev)
+            self.pos = torch.zeros(rows, *pos.shape[1:], dtype=torch.float32, device=dev)
+            self._tail = slots + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies  # slot k's dummy self-loop
             self.edge_index = self._tail.repeat(2, 1)
             self.x[:n].copy_(x)
             self.pos[:n].copy_(pos)
             self.edge_index[:, :e].copy_(edge_index)
             self.topo, self._status = None, None
             self._range_flag = torch.zeros((), dtype=torch.bool, device=dev)
+            self._filled = n                                                        # rows of x / pos that hold a sample
+            self.valid_nodes = torch.full((), n, dtype=torch.int64, device=dev)    # read inside the graph (node_capacity form)
 
             def padded_forward(mod, xx, pp, ee):
                 topo = GraphTopology(ee, xx.size(0), device=dev, validate="deferred")  # never the cache: built in every step
                 self._status = topo.status  # the capture's own flags: every replay rewrites them
                 y = mod.graph_net.forward_device(xx, pp, topo)
+                if node_capacity is not None:
+                    return mod.classifier(masked_readout_rows(y, mod.num_nodes, self.valid_nodes).flatten())
                 return mod.classifier(y[:n].flatten())
             fwd = forward if forward is not None else padded_forward
         through = _Through(model, fwd)
@@ -279,7 +315,8 @@ class CapturedTrainStep:
     def matches(self, sample) -> bool:
         x, pos, edge_index = sample
         if self.edge_capacity is not None:
-            return (x.size(0) == self.num_nodes and x.shape[1:] == self.x.shape[1:] and pos.shape[1:] == self.pos.shape[1:]
+            nodes_fit = x.size(0) == self.num_nodes if self.node_capacity is None else x.size(0) <= self.node_capacity
+            return (nodes_fit and x.shape[1:] == self.x.shape[1:] and pos.shape[1:] == self.pos.shape[1:]
                     and edge_index.dim() == 2 and edge_index.size(1) <= self.edge_capacity)
         return x.shape == self.x.shape and pos.shape == self.pos.shape and _same_topology(edge_index, self.edge_index_host)
 
@@ -296,6 +333,17 @@ class CapturedTrainStep:
             self.pos.copy_(pos, non_blocking=True)
         else:
             n, e = self.num_nodes, int(edge_index.size(1))
+            if self.node_capacity is not None:
+                n = int(x.size(0))
+                if n > self.node_capacity or e > self.edge_capacity:
+                    raise ValueError(f"CapturedTrainStep: sample with {n} nodes / {e} edges does not fit the captured "
+                                     f"{self.node_capacity} nodes / {self.edge_capacity} edges")
+                self.num_nodes = n
+                if n < self._filled:  # a smaller graph after a larger one: its slots become isolated zero nodes again
+                    self.x[n:self._filled].zero_()
+                    self.pos[n:self._filled].zero_()
+                self._filled = n
+                self.valid_nodes.fill_(n)
             if x.size(0) != n or e > self.edge_capacity:
                 raise ValueError(f"CapturedTrainStep: sample with {x.size(0)} nodes / {e} edges does not fit the captured "
                                  f"{n} nodes / {self.edge_capacity} edges")
@@ -407,6 +455,7 @@ class _SampleStepper:
         self.captured: CapturedTrainStep | None = None
         self.padded: CapturedTrainStep | None = None
         self._padded_captures = 0
+        self._edge_capacity = self._node_capacity = 0  # of the node-capacity captures made so far
         self._previous = None
 
     MAX_PADDED_CAPTURES = 4  # a dataset whose edge counts keep outgrowing the capacity goes back to eager steps
@@ -419,16 +468,26 @@ class _SampleStepper:
         if self.captured is not None and self.captured.matches(sample):
             self.captured(sample, label)
             return True
-        # a NEW topology over the same node count (superpixel graphs): the padded form, topology build inside the graph
-        if self.padded is not None and not self.padded.matches(sample) and sample[0].size(0) == self.padded.num_nodes:
-            self.padded = None  # more edges than the capacity: capture again with room to spare
-        if (self.padded is None and same_nodes and self._padded_captures < self.MAX_PADDED_CAPTURES
+        # a NEW topology over the same node count (superpixel graphs): the padded form, topology build inside the graph;
+        # with the model's ragged read-out also another node count (SLIC's segment count varies per image): node capacity
+        same_features = prev is not None and prev[0].shape[1:] == sample[0].shape[1:] and prev[1].shape[1:] == sample[1].shape[1:]
+        ragged = bool(getattr(self.model, "ragged_readout", False)) and same_features and (
+            not same_nodes or (self.padded is not None and self.padded.node_capacity is not None) or self._node_capacity > 0)
+        if self.padded is not None and not self.padded.matches(sample) and (
+                ragged or sample[0].size(0) == self.padded.num_nodes):
+            self.padded = None  # more edges (or nodes) than the capacity: capture again with room to spare
+        if (self.padded is None and (same_nodes or ragged) and self._padded_captures < self.MAX_PADDED_CAPTURES
                 and hasattr(self.model, "graph_net") and hasattr(self.model, "classifier")
                 and not any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in self.model.modules())):
-            most = max(int(prev[2].size(1)), int(sample[2].size(1)))
-            capacity = (most * 3 // 2 + 255) // 256 * 256
-            self.padded = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum,
-                                            edge_capacity=capacity)
+            if ragged:  # capacities only grow from one capture to the next
+                self._edge_capacity = padded_capacity(max(int(prev[2].size(1)), int(sample[2].size(1))), self._edge_capacity)
+                self._node_capacity = padded_capacity(max(int(prev[0].size(0)), int(sample[0].size(0))), self._node_capacity, 32)
+                self.padded = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum,
+                                                edge_capacity=self._edge_capacity, node_capacity=self._node_capacity)
+            else:
+                capacity = padded_capacity(max(int(prev[2].size(1)), int(sample[2].size(1))))
+                self.padded = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum,
+                                                edge_capacity=capacity)
             self._padded_captures += 1
         if self.padded is not None and self.padded.matches(sample):
             self.padded(sample, label)
@@ -504,4 +563,5 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     finally:
         torch.cuda.current_stream(dev).wait_stream(run_stream)
     return {"avg_loss": history, "best_loss": stopper.best, "log_path": journal.path, "captured": stepper.captured is not None, "captured_any_topology": stepper.padded is not None,
+            "captured_ragged": stepper.padded is not None and stepper.padded.node_capacity is not None,
             "optimizer": optimizer}

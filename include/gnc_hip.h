@@ -486,6 +486,23 @@ int gnc_rag_build(const int32_t* labels, const uint8_t* img, int32_t H, int32_t 
                   int64_t* edge_index, int64_t ld_edges, int32_t* counts, void* workspace, size_t workspace_bytes,
                   void* stream);
 
+/* gnc_rag_build_batched  gnc_rag_build for B label images of one size in ONE launch, at fixed capacities and without
+ *                      a host read: `labels` [B, H, W] int32, `img` [B, H, W, 3] uint8 -> x [B, node_capacity, 3],
+ *                      pos [B, node_capacity, 2], edge_index [B, 2, edge_capacity], counts [B, 4] = (segments, directed
+ *                      edges, 1 if a label was outside [0, H*W), 1 if the graph does not fit the capacities).  Per image
+ *                      the first `segments` rows and `edges` columns equal gnc_rag_build's bit for bit; rows behind them
+ *                      are 0, edge slots behind them -1.  An image whose overflow flag is set still reports its true
+ *                      sizes (edges = -1 where it has more than 512 segments: the adjacency is not formed then) and its
+ *                      slices hold padding only.  Supported: H*W <= 65536, node_capacity <= 512, edge_capacity <= 4096;
+ *                      gnc_rag_batched_workspace_bytes returns 0 outside that set.  Integer atomics only
+ *                      (deterministic), stream-ordered, no host synchronisation, safe under stream capture.  Added
+ *                      without an ABI bump: a library without these symbols fails the symbol lookup of the binding.
+ */
+size_t gnc_rag_batched_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t node_capacity, int32_t edge_capacity);
+int gnc_rag_build_batched(const int32_t* labels, const uint8_t* img, int32_t B, int32_t H, int32_t W,
+                          int32_t node_capacity, int32_t edge_capacity, float* x, float* pos, int64_t* edge_index,
+                          int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SLIC superpixels on the device (ABI 20; image_to_graph_superpixel.py:31) ------------------
  * gnc_slic_rgb_u8      scikit-image 0.18.3 `slic(img_as_float(img), n_segments, compactness, max_iter,
  *                      enforce_connectivity, min_size_factor, max_size_factor, start_label)` with sigma = 0, no

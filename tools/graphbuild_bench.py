@@ -1,6 +1,19 @@
 #!/usr/bin/env python3
-"""Timing of the device-side superpixel graph build (post-SLIC part) on synthetic Voronoi label images.
+"""Timing of the device-side superpixel graph build (post-SLIC part).
+
+    python tools/graphbuild_bench.py [--legs single,batched,chunk,step] [--batch 64] [--size 128] [--rounds 7]
+
+single   one image per call (gnc_rag_build) on synthetic Voronoi label images, upload and the host sync included.
+batched  region graphs of --batch label images (device SLIC of the fixture photos, rolled / flipped into distinct
+         images): the per-image path (gnc_rag_build per image, each with its host read of the sizes, as the loader paid)
+         against the batched call (gnc_rag_build_batched) plus its one counts.tolist().  The two alternate in the same
+         process, each warmed up; wall-clock between device synchronisations over windows of about 50 ms, median of --rounds, per image.
+chunk    a whole superpixel chunk of the loader (resize + SLIC + graphs) with the per-image builds and as
+         graphs_from_images runs it now.
+step     one training step on the fixture graphs (node counts differ): eager against the node-capacity capture.
 (The CPU comparison quoted in DESIGN.md was taken with the test-suite oracle; tools never import oracle/.)"""
+import argparse
+import json
 import os
 import sys
 import time
@@ -8,20 +21,158 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from graphnet_classifier_amd import image_to_graph as I2G  # noqa: E402
 
-rng = np.random.default_rng(0)
-for size, nseg in ((32, 100), (128, 100), (256, 400)):
-    img = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
-    pts = rng.random((nseg, 2)) * size
-    yy, xx = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
-    seg = ((yy[..., None] - pts[:, 0]) ** 2 + (xx[..., None] - pts[:, 1]) ** 2).argmin(-1).astype(np.int32)
-    I2G.superpixel_graph_from_labels(img, seg)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(10):
-        x, pos, ei = I2G.superpixel_graph_from_labels(img, seg)
-    torch.cuda.synchronize()
-    gpu = (time.perf_counter() - t0) / 10
-    print(f"R={size} segments={x.size(0)} edges={ei.size(1)}: device {gpu*1e3:.2f} ms (incl. H2D + 1 sync)", flush=True)
+
+def single_leg():
+    rng = np.random.default_rng(0)
+    for size, nseg in ((32, 100), (128, 100), (256, 400)):
+        img = rng.integers(0, 256, size=(size, size, 3), dtype=np.uint8)
+        pts = rng.random((nseg, 2)) * size
+        yy, xx = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
+        seg = ((yy[..., None] - pts[:, 0]) ** 2 + (xx[..., None] - pts[:, 1]) ** 2).argmin(-1).astype(np.int32)
+        I2G.superpixel_graph_from_labels(img, seg)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(10):
+            x, pos, ei = I2G.superpixel_graph_from_labels(img, seg)
+        torch.cuda.synchronize()
+        gpu = (time.perf_counter() - t0) / 10
+        print(f"R={size} segments={x.size(0)} edges={ei.size(1)}: device {gpu*1e3:.2f} ms (incl. H2D + 1 sync)", flush=True)
+
+
+def photos(batch, size):
+    """--batch distinct uint8 images of one size from the fixture photos (rolled / flipped copies), on the device"""
+    from PIL import Image
+    with np.load(os.path.join(ROOT, "tests", "golden", "g10_superpixel.npz")) as z:
+        base = [z[k] for k in sorted(z.files) if k.startswith("img_") and z[k].shape == (128, 128, 3)]
+    base = [np.array(Image.fromarray(im).resize((size, size))) if size != 128 else im for im in base]
+    out = []
+    for i in range(batch):
+        im = np.roll(base[i % len(base)], i, axis=1)
+        out.append(im[::-1] if (i // len(base)) % 2 else im)
+    return np.ascontiguousarray(np.stack(out))
+
+
+def alternate(legs, rounds, window=0.05):
+    """{name: median seconds per call} of callables run in turn, `rounds` times, after a warm-up call each; every timed
+    window repeats its call until it lasts about `window` seconds (a single call of the batched build is 0.2 ms)"""
+    times, reps = {name: [] for name in legs}, {}
+    for name, fn in legs.items():
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        reps[name] = max(1, int(window / max(time.perf_counter() - t0, 1e-6)))
+    for _ in range(rounds):
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps[name]):
+                fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / reps[name])
+    return {name: float(np.median(v)) for name, v in times.items()}
+
+
+def batched_leg(batch, size, rounds):
+    imgs = torch.from_numpy(photos(batch, size)).cuda()
+    labels = I2G.slic(imgs)
+    nodes, edges = I2G.superpixel_capacities(100)
+
+    def per_image():
+        return [I2G._superpixel_graph_from_device_labels(im, lab) for im, lab in zip(imgs, labels)]
+
+    def batched():
+        b = I2G.superpixel_graphs_batched(imgs, labels, node_capacity=nodes, edge_capacity=edges)
+        return b, b.counts.tolist()
+
+    b, counts = batched()
+    assert not any(c[2] or c[3] for c in counts), "a bench image does not fit the capacities"
+    for (x, pos, ei), (s, e, _, _), k in zip(per_image(), counts, range(batch)):
+        assert torch.equal(x, b.x[k, :s]) and torch.equal(pos, b.pos[k, :s]) and torch.equal(ei, b.edge_index[k, :, :e])
+    t = alternate({"per_image": per_image, "batched": batched}, rounds)
+    print(json.dumps({"leg": "batched", "B": batch, "R": size, "node_capacity": nodes, "edge_capacity": edges,
+                      "nodes_min_max": [min(c[0] for c in counts), max(c[0] for c in counts)],
+                      "per_image_path_ms_per_image": round(t["per_image"] / batch * 1e3, 4),
+                      "batched_path_ms_per_image": round(t["batched"] / batch * 1e3, 4),
+                      "ratio": round(t["per_image"] / t["batched"], 2), "rounds": rounds}), flush=True)
+
+
+def chunk_leg(batch, size, rounds):
+    raw = list(photos(batch, size))
+
+    def before():
+        imgs = I2G.resize(raw, (size, size))
+        labels = I2G.slic(imgs, n_segments=100, compactness=10, start_label=0)
+        return [I2G._superpixel_graph_from_device_labels(im, lab) for im, lab in zip(imgs, labels)]
+
+    def after():
+        return I2G.graphs_from_images(raw, method="superpixel", resize_value=size)
+
+    t = alternate({"before": before, "after": after}, rounds)
+    print(json.dumps({"leg": "chunk", "B": batch, "R": size, "per_image_builds_ms_per_chunk": round(t["before"] * 1e3, 3),
+                      "batched_build_ms_per_chunk": round(t["after"] * 1e3, 3), "rounds": rounds}), flush=True)
+
+
+def step_leg(rounds):
+    from graphnet_classifier_amd import synthetic
+    from graphnet_classifier_amd.GNN import CombinedModel, GraphNet
+    from graphnet_classifier_amd.train import CapturedTrainStep, FlatParameters, FusedAdam
+    imgs = torch.from_numpy(photos(16, 64)).cuda()
+    graphs = I2G._superpixel_graphs_from_device_batch(imgs, I2G.slic(imgs), *I2G.superpixel_capacities(100))
+    torch.manual_seed(0)
+    model = CombinedModel(GraphNet(**synthetic.graphnet_kwargs(64, 2)), num_nodes=100, classes=2)
+    model.ragged_readout = True
+    opt = FusedAdam(FlatParameters(model))
+    crit = torch.nn.CrossEntropyLoss()
+    loss_sum = torch.zeros((), dtype=torch.float64, device="cuda")
+    labels = [torch.tensor(i % 2, device="cuda") for i in range(len(graphs))]
+    big = max(range(len(graphs)), key=lambda i: graphs[i][0].size(0))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        captured = CapturedTrainStep(model, opt, crit, graphs[big], labels[big], loss_sum, edge_capacity=1024, node_capacity=192)
+
+        def eager():
+            for g, lab in zip(graphs, labels):
+                loss = crit(model(g), lab)
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
+
+        def replayed():
+            for g, lab in zip(graphs, labels):
+                captured(g, lab)
+
+        t = alternate({"eager": eager, "captured": replayed}, rounds)
+    torch.cuda.current_stream().wait_stream(side)
+    print(json.dumps({"leg": "step", "graphs": len(graphs), "nodes": sorted({int(g[0].size(0)) for g in graphs}),
+                      "eager_ms_per_step": round(t["eager"] / len(graphs) * 1e3, 4),
+                      "node_capacity_capture_ms_per_step": round(t["captured"] / len(graphs) * 1e3, 4), "rounds": rounds}),
+          flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="single,batched,chunk,step")
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--rounds", type=int, default=7)
+    args = ap.parse_args()
+    legs = args.legs.split(",")
+    if "single" in legs:
+        single_leg()
+    if "batched" in legs:
+        batched_leg(args.batch, args.size, args.rounds)
+    if "chunk" in legs:
+        chunk_leg(args.batch, args.size, args.rounds)
+    if "step" in legs:
+        step_leg(args.rounds)
+
+
+if __name__ == "__main__":
+    main()
