@@ -26,7 +26,8 @@ from .topology import GraphTopology, get_destination_csr, get_topology
 # Algebraic split of the edge processor's first Linear (DESIGN.md, K4 "W-split"); GNC_NO_WSPLIT=1
 # keeps the reference-form concat for A/B measurements.
 WSPLIT = os.environ.get("GNC_NO_WSPLIT") is None
-# A/B switch: GNC_NO_READOUT_KERNEL=1 leaves the single-graph read-out classifier to PyTorch-ROCm (3 GEMM + 2 clamp + copies)
+# A/B switch: GNC_NO_READOUT_KERNEL=1 leaves the read-out classifier (one graph, or the G graphs of forward_batched) to PyTorch-ROCm
+# (3 GEMM + 2 clamp + copies; batched with graph_ptr also an index gather and a product that store a [G, F] feature matrix)
 READOUT_HIP = os.environ.get("GNC_NO_READOUT_KERNEL") is None
 # Inference: the edge processor's launch also forms the node model's per-destination sums (fused aggregation
 # epilogue); GNC_NO_FUSED_AGG=1 keeps K1 as a separate launch for A/B measurements.
@@ -509,8 +510,8 @@ class CombinedModel(nn.Module):
         return logits if back == dev else logits.to(back)
 
     def forward_batched(self, x, pos, edge_index, num_graphs: int | None = None, graph_ptr: Tensor | None = None):
-        """Block-diagonal batch: one GraphNet pass over all graphs, then the read-out as one
-        [G, num_nodes*out_dim] GEMM.  The reference has no batching (main.py:60, SURVEY.md section 2.4-2);
+        """Block-diagonal batch: one GraphNet pass over all graphs, then the read-out of all G graphs in the batched
+        HIP read-out (``functional.readout_batched``; a shape it does not serve: one [G, num_nodes*out_dim] GEMM).  The reference has no batching (main.py:60, SURVEY.md section 2.4-2);
         this equals G independent ``forward`` calls.
 
         * ``num_graphs`` given: every graph has exactly ``num_nodes`` nodes (graph g owns rows g*num_nodes ...).
@@ -526,13 +527,26 @@ class CombinedModel(nn.Module):
         topo = get_topology(edge_index, x.size(0), dev)
         y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
         od = self.graph_net.out_dim
+        gp = None
         if graph_ptr is None:
             if num_graphs is None or x.size(0) != num_graphs * self.num_nodes:
                 raise ValueError(f"expected num_graphs x {self.num_nodes} node rows (got {x.size(0)}); pass graph_ptr "
                                  f"for graphs of other sizes")
-            feats = y.view(num_graphs, -1)
         else:
             gp = graph_ptr.to(device=dev, dtype=torch.int64)
+            num_graphs = gp.numel() - 1
+        fc1, fc2, fc3 = self.classifier.fc1, self.classifier.fc2, self.classifier.fc3
+        if (READOUT_HIP and num_graphs >= 1 and y.dtype == torch.float32 and fc1.in_features == self.num_nodes * od
+                and native.readout_batched_supported(num_graphs, fc1.in_features, fc1.out_features, fc2.out_features,
+                                                     fc3.out_features)):
+            # the gather rule below fused into fc1's operand load, fc1 on MFMA, fc2 / fc3 from LDS (csrc/readout_batched.hip);
+            # a shape the library does not take stays on the torch path
+            logits = Fn.readout_batched(y, gp, num_graphs, self.num_nodes, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                                        fc3.weight, fc3.bias)
+            return logits if back == dev else logits.to(back)
+        if gp is None:
+            feats = y.view(num_graphs, -1)
+        else:
             start, size = gp[:-1], gp[1:] - gp[:-1]
             k = torch.arange(self.num_nodes, device=dev)
             valid = k[None, :] < size[:, None]                                   # [G, num_nodes]

@@ -108,27 +108,38 @@ class GraphImageFolder(Dataset):
         path, label = self.samples[idx]
         return self._graphs([load_rgb(path)])[0], torch.tensor(label, dtype=torch.long)
 
-    def loader(self, shuffle: bool = True, chunk: int = 64, workers: int | None = None):
-        """Iterable over ``((x, pos, edge_index), label)`` for ``train(model, ds.loader(), epochs, ...)``; every
-        iteration is one epoch, in the order ``DataLoader(self, batch_size=1, shuffle=shuffle)`` would give under the
-        same global RNG state."""
-        return GraphFolderLoader(self, shuffle, chunk, workers)
+    def loader(self, shuffle: bool = True, chunk: int = 64, workers: int | None = None, batch_size: int = 1,
+               drop_last: bool = False):
+        """Iterable for ``train(model, ds.loader(), epochs, ...)``; every iteration is one epoch.
+
+        ``batch_size=1``: ``((x, pos, edge_index), label)`` per image, in the order ``DataLoader(self, batch_size=1,
+        shuffle=shuffle)`` would give under the same global RNG state.  ``batch_size=B > 1``: ``(GraphBatch, labels [B])``
+        per mini-batch (``image_to_graph.collate_graphs``), the batches being those of ``DataLoader(self, batch_size=B,
+        shuffle=shuffle, drop_last=drop_last)`` under the same global RNG state; without ``drop_last`` the last batch
+        may be shorter."""
+        return GraphFolderLoader(self, shuffle, chunk, workers, batch_size, drop_last)
 
 
 class GraphFolderLoader:
     """Epochs over a ``GraphImageFolder``: decode on a thread pool (the next chunk's decode is in flight while the
     current chunk is consumed), then resize and graph builds per chunk in batched launches."""
 
-    def __init__(self, dataset: GraphImageFolder, shuffle: bool = True, chunk: int = 64, workers: int | None = None):
+    def __init__(self, dataset: GraphImageFolder, shuffle: bool = True, chunk: int = 64, workers: int | None = None,
+                 batch_size: int = 1, drop_last: bool = False):
         if chunk < 1:
             raise ValueError("chunk must be at least 1")
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
         self.dataset = dataset
         self.shuffle = shuffle
         self.chunk = int(chunk)
+        self.batch_size = int(batch_size)
+        self.drop_last = bool(drop_last)
         self.workers = default_workers() if workers is None else max(1, min(int(workers), MAX_WORKERS))
 
     def __len__(self):
-        return len(self.dataset)
+        n, b = len(self.dataset), self.batch_size
+        return n // b if self.drop_last else (n + b - 1) // b
 
     def order(self):
         """The epoch's sample indices, drawing from the global RNG exactly as a single-process ``DataLoader`` does:
@@ -142,10 +153,27 @@ class GraphFolderLoader:
         generator.manual_seed(seed)
         return torch.randperm(n, generator=generator).tolist()
 
+    def index_batches(self):
+        """The epoch's index batches (host only): ``order()`` cut as ``BatchSampler(batch_size, drop_last)`` cuts it, so
+        the same lists, and the same draws from the global RNG, as ``DataLoader(dataset, batch_size=batch_size,
+        shuffle=shuffle, drop_last=drop_last)``."""
+        order, b = self.order(), self.batch_size
+        batches = [order[i:i + b] for i in range(0, len(order), b)]
+        if self.drop_last and batches and len(batches[-1]) < b:
+            batches.pop()
+        return batches
+
     def __iter__(self):
-        order = self.order()
         samples = self.dataset.samples
-        chunks = [order[i:i + self.chunk] for i in range(0, len(order), self.chunk)]
+        if self.batch_size == 1:
+            batches = None
+            order = self.order()
+            chunks = [order[i:i + self.chunk] for i in range(0, len(order), self.chunk)]
+        else:  # a chunk holds whole mini-batches
+            batches = self.index_batches()
+            per = max(1, self.chunk // self.batch_size)
+            groups = [batches[i:i + per] for i in range(0, len(batches), per)]
+            chunks = [[i for b in group for i in b] for group in groups]
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             def decode(idx):
                 return [pool.submit(load_rgb, samples[i][0]) for i in idx]
@@ -156,5 +184,12 @@ class GraphFolderLoader:
                 pending = decode(chunks[c + 1]) if c + 1 < len(chunks) else []
                 graphs = self.dataset._graphs(images)
                 del images
-                for i, g in zip(idx, graphs):
-                    yield g, torch.tensor(samples[i][1], dtype=torch.long)
+                if batches is None:
+                    for i, g in zip(idx, graphs):
+                        yield g, torch.tensor(samples[i][1], dtype=torch.long)
+                    continue
+                at = 0
+                for b in groups[c]:
+                    yield (I2G.collate_graphs(graphs[at:at + len(b)]),
+                           torch.tensor([samples[i][1] for i in b], dtype=torch.long))
+                    at += len(b)

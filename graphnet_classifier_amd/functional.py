@@ -524,6 +524,37 @@ def readout(y, w1, b1, w2, b2, w3, b3):
     return _Readout.apply(y, w1, b1, w2, b2, w3, b3)
 
 
+class _ReadoutBatched(torch.autograd.Function):
+    """LinearClassifier.forward over the G graphs of a block-diagonal batch with forward_batched's gather rule fused into fc1's
+    operand load (csrc/readout_batched.hip): no [G, F] feature matrix, two launches forward."""
+
+    @staticmethod
+    def forward(ctx, y, graph_ptr, num_graphs, num_nodes, w1, b1, w2, b2, w3, b3):
+        logits, h1, h2 = native.readout_batched_forward(y, graph_ptr, num_graphs, num_nodes, w1, b1, w2, b2, w3, b3)
+        ctx.save_for_backward(y, graph_ptr, w1, w2, w3, h1, h2)
+        ctx.shape = (num_graphs, num_nodes)
+        ctx.has_bias = (b1 is not None, b2 is not None, b3 is not None)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_logits):
+        y, graph_ptr, w1, w2, w3, h1, h2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy, dw1, db1, dw2, db2, dw3, db3 = native.readout_batched_backward(grad_logits, y, graph_ptr, ctx.shape[0], ctx.shape[1], w1, w2,
+                                                                           w3, h1, h2, need_dy=need[0])
+        hb = ctx.has_bias
+        return (dy.view_as(y) if need[0] else None, None, None, None, dw1 if need[4] else None, db1 if (need[5] and hb[0]) else None,
+                dw2 if need[6] else None, db2 if (need[7] and hb[1]) else None, dw3 if need[8] else None,
+                db3 if (need[9] and hb[2]) else None)
+
+
+def readout_batched(y, graph_ptr, num_graphs, num_nodes, w1, b1, w2, b2, w3, b3):
+    """Read-out MLP of ``num_graphs`` graphs: ``y`` [N_total, out_dim] float32 on the GPU; ``graph_ptr`` int64 [G + 1] on the same
+    device (graphs of any size: the first ``num_nodes`` rows of a graph feed fc1, a smaller graph is zero-padded) or None (graph g
+    owns rows ``[g * num_nodes, (g + 1) * num_nodes)``).  Returns logits [G, C]."""
+    return _ReadoutBatched.apply(y, graph_ptr, int(num_graphs), int(num_nodes), w1, b1, w2, b2, w3, b3)
+
+
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """[pos[dst]-pos[src], L1 norm] per edge (models/GNN.py:299-302).  ``pos`` is input data
     (utils/dataloader.py:50); gradients with respect to it are not provided."""

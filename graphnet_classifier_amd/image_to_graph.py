@@ -369,6 +369,28 @@ def resize(images, size, resample="bicubic", box=None, reducing_gap=None) -> tor
     return out[0] if single else out
 
 
+def collate_graphs(graphs):
+    """A list of ``(x, pos, edge_index)`` graphs as ONE block-diagonal ``synthetic.GraphBatch``: ``x`` and ``pos`` concatenated,
+    node ids of graph g shifted by the nodes in front of it, ``graph_ptr`` / ``edge_ptr`` int64 [G + 1] (host tensors, from the
+    shapes).  One concatenation per tensor and one add on the tensors' own device: no per-graph launches, no host
+    synchronisation.  ``batch.slice_graphs(g, g + 1)`` gives graph g back; ``CombinedModel.forward_batched(batch.x, batch.pos,
+    batch.edge_index, graph_ptr=batch.graph_ptr)`` runs the batch."""
+    from .synthetic import GraphBatch
+    graphs = list(graphs)
+    if not graphs:
+        raise ValueError("collate_graphs: empty list of graphs")
+    nodes = torch.tensor([0] + [int(g[0].size(0)) for g in graphs], dtype=torch.int64)
+    edges = torch.tensor([0] + [int(g[2].size(1)) for g in graphs], dtype=torch.int64)
+    graph_ptr, edge_ptr = nodes.cumsum(0), edges.cumsum(0)
+    x = torch.cat([g[0] for g in graphs])
+    pos = torch.cat([g[1] for g in graphs])
+    edge_index = torch.cat([g[2] for g in graphs], dim=1)
+    shift = torch.repeat_interleave(graph_ptr[:-1], edges[1:])  # [E] on the host: sizes only, no tensor is read back
+    if edge_index.is_cuda:
+        shift = shift.pin_memory().to(edge_index.device, non_blocking=True)
+    return GraphBatch(x, pos, edge_index + shift, graph_ptr, edge_ptr)
+
+
 METHODS = ("pixel", "patch", "superpixel")
 
 

@@ -48,6 +48,13 @@ _SIGNATURES = {
     "gnc_readout_backward_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p,
                                            c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    "gnc_readout_batched_supported": (c_int32, [c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p]),
+    "gnc_readout_batched_forward_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int64, c_void_p,
+                                                  c_int32, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnc_readout_batched_backward_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int64,
+                                                   c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnc_xty_small_max_rows": (c_int32, []),
     "gnc_xty_small_f32": (c_int32, [c_void_p, c_int32, c_void_p]),
     "gnc_agg_fixup_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64,
@@ -145,6 +152,11 @@ class MlpBwdDesc(Structure):
 class XtyJob(Structure):
     _fields_ = [("a", c_void_p), ("lda", c_int64), ("b", c_void_p), ("ldb", c_int64), ("rows", c_int64), ("m", c_int32),
                 ("k", c_int32), ("dw", c_void_p), ("ld_dw", c_int64), ("db", c_void_p), ("kind", c_int32)]
+
+
+class ReadoutBatchedPlan(Structure):
+    _fields_ = [(name, c_int64) for name in ("f_slices", "f_slice_len", "tail_rows", "small_parts", "dw1_parts", "dw1_graph_range",
+                                              "dy_groups", "forward_workspace_floats", "backward_workspace_floats")]
 
 
 GNC_XTY_MAX_JOBS = 8
@@ -713,6 +725,87 @@ def readout_backward(grad_logits, y, w1, w2, w3, h1, h2, need_dy: bool = True):
                                                             db3.data_ptr(), dy.data_ptr() if dy is not None else None, _stream(y)),
                        4.0 * w1.numel()), "gnc_readout_backward_f32")
     return dy, dw1, db1, dw2, db2, dw3, db3
+
+
+def readout_batched_plan(num_graphs: int, features: int, h1: int, h2: int, classes: int) -> dict | None:
+    """The library's decision for the batched read-out of ``num_graphs`` graphs with ``features`` fc1 inputs each (host only, no
+    GPU needed): None when the shape is left to the torch path, otherwise the split the launches will use - ``f_slices`` x
+    ``f_slice_len`` of F in the forward, the graph chunks of the backward - and the workspace sizes in floats."""
+    plan = ReadoutBatchedPlan()
+    if not load_library().gnc_readout_batched_supported(int(num_graphs), int(features), int(h1), int(h2), int(classes), ctypes.byref(plan)):
+        return None
+    return {name: int(getattr(plan, name)) for name, _ in ReadoutBatchedPlan._fields_}
+
+
+def readout_batched_supported(num_graphs: int, features: int, h1: int, h2: int, classes: int) -> bool:
+    return bool(load_library().gnc_readout_batched_supported(int(num_graphs), int(features), int(h1), int(h2), int(classes), None))
+
+
+def _graph_ptr_arg(graph_ptr, num_graphs: int, dev):
+    if graph_ptr is None:
+        return None
+    if graph_ptr.dtype != torch.int64 or graph_ptr.device != dev or graph_ptr.numel() != num_graphs + 1:
+        raise ValueError("readout_batched: graph_ptr must be int64 [num_graphs + 1] on the device of y")
+    return graph_ptr.contiguous()
+
+
+def readout_batched_forward(y, graph_ptr, num_graphs: int, num_nodes: int, w1, b1, w2, b2, w3, b3):
+    """logits [G, C] = fc3(relu(fc2(relu(fc1(feats))))) for the G graphs of a block-diagonal batch, ``y`` [N_total, out_dim] being
+    the GraphNet output (gnc_readout_batched_forward_f32: fc1 with the gather fused into its operand load, then the tail).
+    ``graph_ptr`` int64 [G + 1] on the device, or None for G graphs of exactly ``num_nodes`` rows.  Also returns the post-ReLU
+    ``h1`` [G, 128] and ``h2`` [G, H2] for the backward."""
+    lib = load_library()
+    _require_cuda(y, w1, w2, w3)
+    y = _rowmajor(y).contiguous()
+    w1, w2, w3 = _rowmajor(w1.detach()), _rowmajor(w2.detach()), _rowmajor(w3.detach())
+    dev, G, od = y.device, int(num_graphs), y.size(1)
+    gp = _graph_ptr_arg(graph_ptr, G, dev)
+    plan = readout_batched_plan(G, int(num_nodes) * od, w1.size(0), w2.size(0), w3.size(0))
+    if plan is None:
+        raise RuntimeError("readout_batched_forward: shape outside the kernel's set (ask readout_batched_supported first)")
+    e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)  # noqa: E731
+    h1, h2, logits = e(G, w1.size(0)), e(G, w2.size(0)), e(G, w3.size(0))
+    ws = e(max(plan["forward_workspace_floats"], 1))
+    bp = [b.detach().contiguous() if b is not None else None for b in (b1, b2, b3)]
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _check(_launch("readout_batched_forward", y,
+                       lambda: lib.gnc_readout_batched_forward_f32(
+                           y.data_ptr(), ptr(gp), G, int(num_nodes), od, y.size(0), w1.data_ptr(), _ld(w1), ptr(bp[0]), w1.size(0),
+                           w2.data_ptr(), _ld(w2), ptr(bp[1]), w2.size(0), w3.data_ptr(), _ld(w3), ptr(bp[2]), w3.size(0),
+                           h1.data_ptr(), h2.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), _stream(y)),
+                       2.0 * G * (int(num_nodes) * od * w1.size(0) + w2.numel() + w3.numel())), "gnc_readout_batched_forward_f32")
+    return logits, h1, h2
+
+
+def readout_batched_backward(grad_logits, y, graph_ptr, num_graphs: int, num_nodes: int, w1, w2, w3, h1, h2, need_dy: bool = True):
+    """All gradients of ``readout_batched_forward``: (dy [N_total, out_dim] or None, dW1, db1, dW2, db2, dW3, db3).  ``dy`` is written
+    for every row (exact zeros where a row does not reach fc1); the five small gradients are views of one buffer."""
+    lib = load_library()
+    g = grad_logits.contiguous()
+    y = _rowmajor(y).contiguous()
+    w1, w2, w3 = _rowmajor(w1.detach()), _rowmajor(w2.detach()), _rowmajor(w3.detach())
+    dev, G, od = y.device, int(num_graphs), y.size(1)
+    H1, H2, C = w1.size(0), w2.size(0), w3.size(0)
+    gp = _graph_ptr_arg(graph_ptr, G, dev)
+    plan = readout_batched_plan(G, int(num_nodes) * od, H1, H2, C)
+    if plan is None:
+        raise RuntimeError("readout_batched_backward: shape outside the kernel's set")
+    e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)  # noqa: E731
+    dw1 = e(H1, int(num_nodes) * od)
+    small = e(H2 * H1 + H2 + C * H2 + C + H1)
+    dy = e(y.size(0), od) if need_dy else None
+    ws = e(max(plan["backward_workspace_floats"], 1))
+    with torch.cuda.device(dev):
+        _check(_launch("readout_batched_backward", y,
+                       lambda: lib.gnc_readout_batched_backward_f32(
+                           g.data_ptr(), y.data_ptr(), gp.data_ptr() if gp is not None else None, G, int(num_nodes), od, y.size(0),
+                           w1.data_ptr(), _ld(w1), H1, w2.data_ptr(), _ld(w2), H2, w3.data_ptr(), _ld(w3), C, h1.data_ptr(),
+                           h2.data_ptr(), dw1.data_ptr(), small.data_ptr(), dy.data_ptr() if dy is not None else None, ws.data_ptr(),
+                           ws.numel(), _stream(y)),
+                       4.0 * G * w1.numel()), "gnc_readout_batched_backward_f32")
+    dw2, db2, dw3, db3, db1 = small.split([H2 * H1, H2, C * H2, C, H1])
+    return dy, dw1, db1, dw2.view(H2, H1), db2, dw3.view(C, H2), db3
 
 
 def dual_projection(x: torch.Tensor, wa: torch.Tensor, wb: torch.Tensor):

@@ -14,6 +14,9 @@ dataset order (:35-45), average training loss per epoch, early stopping on it (:
   utils/image_to_graph/image_to_graph_optimized.py:42-47) the whole step - forward, loss, backward, gradient pack,
   Adam - is captured into a hipGraph once and replayed per sample (``CapturedTrainStep``): one launch per step
   instead of ~150;
+* a loader that yields ``(synthetic.GraphBatch, labels [B])`` (``GraphImageFolder.loader(batch_size=B)``) is stepped once per
+  mini-batch through ``CombinedModel.forward_batched`` - mean cross-entropy over the batch, captured when consecutive full
+  batches share a topology; ``evaluate`` / ``predict`` score a model over either loader form;
 * the run's side effects live in three small objects: ``RunJournal`` (the log file and the console lines),
   ``PlateauStopper`` (best loss so far, epochs without improvement) and ``CheckpointShelf`` (the ``.pth`` files).
 
@@ -33,6 +36,7 @@ import torch.nn as nn
 from . import native
 from .MLP import require_gpu_param
 from .sharding import FlatGradAllReduce
+from .synthetic import GraphBatch
 
 ALIGN = 64  # floats: every parameter starts on a 256-B boundary of the flat buffer (the MLP kernels want 16-B aligned weights)
 
@@ -457,6 +461,9 @@ class _SampleStepper:
         self._padded_captures = 0
         self._edge_capacity = self._node_capacity = 0  # of the node-capacity captures made so far
         self._previous = None
+        self.captured_batch: CapturedTrainStep | None = None  # mini-batches (GraphBatch samples)
+        self._previous_batch = None
+        self.batched = False
 
     MAX_PADDED_CAPTURES = 4  # a dataset whose edge counts keep outgrowing the capacity goes back to eager steps
 
@@ -499,8 +506,47 @@ class _SampleStepper:
         if self.padded is not None:
             self.padded.check()
 
+    def _batch_forward(self, batch):
+        """``forward(model, x, pos, edge_index) -> logits [G, C]`` of a mini-batch: the ``num_graphs`` form for graphs of exactly
+        ``num_nodes`` nodes on a model without ``ragged_readout``, else the ``graph_ptr`` form (a device copy made here, once)."""
+        G = batch.num_graphs
+        sizes = batch.graph_ptr[1:] - batch.graph_ptr[:-1]
+        if not getattr(self.model, "ragged_readout", False) and bool((sizes == self.model.num_nodes).all()):
+            return lambda mod, xx, pp, ee: mod.forward_batched(xx, pp, ee, num_graphs=G)
+        gptr = batch.graph_ptr.to(self.device)
+        return lambda mod, xx, pp, ee: mod.forward_batched(xx, pp, ee, graph_ptr=gptr)
+
+    def _step_batch(self, batch, labels) -> None:
+        """One optimizer step on a mini-batch (``synthetic.GraphBatch``, labels [B]): mean cross-entropy over the batch.  A
+        replay of the captured step when this batch has the topology of the one before it (pixel / patch graphs of one size:
+        every full batch), an eager step otherwise (a short last batch; superpixel graphs, whose topology changes)."""
+        dev = self.device
+        self.batched = True
+        sample = (batch.x, batch.pos, batch.edge_index)
+        if self.capture:
+            prev = self._previous_batch
+            if (self.captured_batch is None and prev is not None and prev[0].shape == sample[0].shape
+                    and prev[1].shape == sample[1].shape and torch.equal(prev[3], batch.graph_ptr) and _same_topology(prev[2], sample[2])):
+                self.captured_batch = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, labels, self.loss_sum,
+                                                        forward=self._batch_forward(batch))
+                self._captured_graph_ptr = batch.graph_ptr.clone()
+            if (self.captured_batch is not None and torch.equal(self._captured_graph_ptr, batch.graph_ptr)
+                    and self.captured_batch.matches(sample)):
+                self.captured_batch(sample, labels)
+                return
+            self._previous_batch = sample + (batch.graph_ptr,)
+        x, pos = batch.x.to(dev, non_blocking=True), batch.pos.to(dev, non_blocking=True)
+        logits = self._batch_forward(batch)(self.model, x, pos, batch.edge_index)
+        loss = self.criterion(logits, torch.as_tensor(labels).to(dev, non_blocking=True))
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        self.loss_sum += loss.detach().double()
+
     def __call__(self, sample, label) -> None:
         dev = self.device
+        if isinstance(sample, GraphBatch):
+            return self._step_batch(sample, label)
         is_graph = isinstance(sample, (tuple, list)) and len(sample) == 3
         if self.capture and is_graph and self._try_replay(sample, label):
             return
@@ -520,7 +566,15 @@ class _SampleStepper:
 
 def train(model, dataset, epochs, patience=5, output_path='weights', start_weights=None, *, capture: bool = True, lr: float = 1e-3):
     """utils/train_model.py:8-81 (same positional arguments, files and log lines).  Returns a dict with the per-epoch
-    average losses (the reference returns None; nothing in it reads the return value)."""
+    average losses (the reference returns None; nothing in it reads the return value).
+
+    Mini-batches: a ``dataset`` that yields ``(synthetic.GraphBatch, labels [B])`` - ``GraphImageFolder.loader(batch_size=B)`` -
+    takes one optimizer step per batch through ``model.forward_batched`` (the ``num_graphs`` form for equal-size batches on a
+    model without ``ragged_readout``, otherwise ``graph_ptr``); the loss is ``CrossEntropyLoss()``'s mean over the batch
+    (:38 on a batched input, as the reference's image-MLP path with ``batch_size=8``, main.py:13-29) and the epoch average is
+    taken over steps (:47).  When consecutive full batches share one topology (pixel / patch graphs of one size) the step is
+    captured once and replayed; a short last batch runs eagerly, and so does every batch whose topology changes (superpixel
+    graphs): captured steps over ragged batches are not built.  ``"batched"`` in the returned dict says which form ran."""
     if start_weights:
         model.load_state_dict(torch.load(start_weights, map_location="cpu"))           # :14-15
     dev = require_gpu_param(next(model.parameters()), "train")
@@ -562,6 +616,64 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
             journal.close(stopper.best, final_path)
     finally:
         torch.cuda.current_stream(dev).wait_stream(run_stream)
-    return {"avg_loss": history, "best_loss": stopper.best, "log_path": journal.path, "captured": stepper.captured is not None, "captured_any_topology": stepper.padded is not None,
+    return {"avg_loss": history, "best_loss": stopper.best, "log_path": journal.path,
+            "captured": stepper.captured is not None or stepper.captured_batch is not None, "batched": stepper.batched,
+            "captured_any_topology": stepper.padded is not None,
             "captured_ragged": stepper.padded is not None and stepper.padded.node_capacity is not None,
             "optimizer": optimizer}
+
+
+# --------------------------------------------------------------------------- evaluation
+def _logits_of(model, sample, dev):
+    """Logits [B, C] of one loader item: a ``GraphBatch`` through ``forward_batched``, an ``(x, pos, edge_index)`` graph through
+    ``model(sample)`` (one row)."""
+    if isinstance(sample, GraphBatch):
+        x, pos = sample.x.to(dev, non_blocking=True), sample.pos.to(dev, non_blocking=True)
+        sizes = sample.graph_ptr[1:] - sample.graph_ptr[:-1]
+        if not getattr(model, "ragged_readout", False) and bool((sizes == model.num_nodes).all()):
+            return model.forward_batched(x, pos, sample.edge_index, num_graphs=sample.num_graphs)
+        return model.forward_batched(x, pos, sample.edge_index, graph_ptr=sample.graph_ptr)
+    if isinstance(sample, (tuple, list)) and len(sample) == 3:
+        sample = (sample[0].to(dev, non_blocking=True), sample[1].to(dev, non_blocking=True), sample[2])
+    else:
+        sample = sample.to(dev, non_blocking=True)
+    logits = model(sample)
+    return logits.unsqueeze(0) if logits.dim() == 1 else logits
+
+
+def predict(model, loader):
+    """``(logits [n, C], probabilities [n, C])`` of every sample of ``loader`` in loader order, on the model's device - the pair
+    ``utils/inference.py:68-71`` returns per image (softmax over the classes).  ``loader`` yields ``(sample, label)`` with a
+    single graph or a ``GraphBatch`` (``GraphImageFolder.loader(shuffle=False, batch_size=...)``); labels are not read."""
+    dev = require_gpu_param(next(model.parameters()), "predict")
+    with torch.no_grad():
+        rows = [_logits_of(model, sample, dev) for sample, _ in loader]
+        if not rows:
+            raise ValueError("predict: the loader yielded nothing")
+        logits = torch.cat(rows)
+        return logits, torch.softmax(logits, dim=-1)
+
+
+def evaluate(model, loader):
+    """Scores ``model`` on every sample of ``loader`` (either loader form) under ``no_grad``: ``{"loss": mean cross-entropy over
+    the samples, "accuracy", "confusion": int64 [C, C] with rows = true class and columns = predicted class, "count"}``.
+    Loss and confusion matrix are accumulated on the device (integer scatter-adds, float64 loss) and read ONCE at the end."""
+    dev = require_gpu_param(next(model.parameters()), "evaluate")
+    loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+    confusion, count = None, 0
+    with torch.no_grad():
+        for sample, label in loader:
+            logits = _logits_of(model, sample, dev)
+            labels = torch.as_tensor(label).to(dev, non_blocking=True).reshape(-1)
+            if confusion is None:
+                classes = logits.size(1)
+                confusion = torch.zeros(classes * classes, dtype=torch.int64, device=dev)
+            loss_sum += nn.functional.cross_entropy(logits, labels, reduction="sum").double()
+            confusion.index_add_(0, labels * classes + logits.argmax(dim=1), torch.ones_like(labels))
+            count += int(labels.numel())
+        if confusion is None:
+            raise ValueError("evaluate: the loader yielded nothing")
+        stats = torch.cat([loss_sum, confusion.double()]).cpu()  # the one host read
+    confusion = stats[1:].round().to(torch.int64).view(classes, classes)
+    return {"loss": float(stats[0]) / count, "accuracy": float(confusion.diagonal().sum()) / count, "confusion": confusion,
+            "count": count}

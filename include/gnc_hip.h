@@ -461,6 +461,47 @@ int gnc_readout_backward_f32(const float* grad_logits, const float* y, int64_t F
                              int64_t ld2, int32_t H2, const float* w3, int64_t ld3, int32_t C, const float* h1, const float* h2, float* dw1,
                              float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dy, void* stream);
 
+/* ---- read-out classifier of G graphs: a block-diagonal batch (VERDICT row f4) --------------------------------------------------
+ * logits [G, C] = fc3(relu(fc2(relu(fc1(feats))))) with the gather rule of `CombinedModel.forward_batched` applied where fc1's
+ * operand is loaded: feature k * out_dim + j of graph g is y[start_g + k, j] for k < min(size_g, num_nodes) and 0 otherwise; no
+ * [G, F] feature matrix is stored (F = num_nodes * out_dim).  `y` [n_total, out_dim] contiguous; `graph_ptr` DEVICE int64 [G + 1]
+ * node offsets, or NULL: graph g owns rows [g num_nodes, (g + 1) num_nodes) and n_total == G num_nodes.  Offsets that point outside
+ * y read as shorter or empty graphs, never outside the table.  Weights as nn.Linear holds them, read where they lie (row-major,
+ * leading dimensions as in gnc_readout_forward_f32); biases may be NULL.
+ *
+ * Forward: fc1 on v_mfma_f32_16x16x4_f32, 16 graphs per workgroup, F split into `f_slices` slices whose partial [G, H1] tiles go
+ * to `workspace` (`forward_workspace_floats` floats) and are summed in ascending slice order by the tail launch, which adds b1,
+ * applies ReLU (NaN kept) and runs fc2 / fc3 from LDS.  h1 [G, H1], h2 [G, H2]: the post-ReLU activations, kept for the backward.
+ * Backward: dw1 [H1, F] contiguous (columns no graph reaches: exact zeros), `small_grads` = [dW2 H2 x H1 | db2 H2 | dW3 C x H2 |
+ * db3 C | db1 H1] contiguous, dy [n_total, out_dim] or NULL (every row written: rows a graph does not feed into fc1 get exact
+ * zeros).  `workspace`: `backward_workspace_floats` floats, 16-B aligned.  Sums over graphs run over fixed chunks whose partials
+ * are added in ascending order.  No atomics, no persistent counter, no memset: the workspaces belong to the call, results are
+ * bitwise reproducible, every launch is a kernel node under stream capture.
+ *
+ * Served: H1 == 128, H2 <= 32, C <= 64, any F >= 1.  gnc_readout_batched_supported answers on the host (no device needed) from the
+ * same decision the launchers read, and fills `plan` (may be NULL) with the split it chose; 1 = served.  The launchers return
+ * GNC_ERR_UNSUPPORTED outside the set.  Added without an ABI bump: a library without these symbols fails the symbol lookup of
+ * the binding. */
+typedef struct gnc_readout_batched_plan {
+  int64_t f_slices, f_slice_len;     /* forward: slices of F and their length (a multiple of 32)                        */
+  int64_t tail_rows;                 /* graphs per workgroup of the tail launch                                         */
+  int64_t small_parts;               /* backward: chunks of graphs behind the small gradients                           */
+  int64_t dw1_parts, dw1_graph_range; /* backward: ranges of graphs behind dW1 and their length                         */
+  int64_t dy_groups;                 /* backward: groups of graph tiles of the dy launch                                */
+  int64_t forward_workspace_floats, backward_workspace_floats;
+} gnc_readout_batched_plan_t;
+int32_t gnc_readout_batched_supported(int64_t num_graphs, int64_t F, int32_t H1, int32_t H2, int32_t C,
+                                      gnc_readout_batched_plan_t* plan);
+int gnc_readout_batched_forward_f32(const float* y, const int64_t* graph_ptr, int64_t num_graphs, int64_t num_nodes, int32_t out_dim,
+                                    int64_t n_total, const float* w1, int64_t ld1, const float* b1, int32_t H1, const float* w2,
+                                    int64_t ld2, const float* b2, int32_t H2, const float* w3, int64_t ld3, const float* b3, int32_t C,
+                                    float* h1, float* h2, float* logits, float* workspace, int64_t workspace_floats, void* stream);
+int gnc_readout_batched_backward_f32(const float* grad_logits, const float* y, const int64_t* graph_ptr, int64_t num_graphs,
+                                     int64_t num_nodes, int32_t out_dim, int64_t n_total, const float* w1, int64_t ld1, int32_t H1,
+                                     const float* w2, int64_t ld2, int32_t H2, const float* w3, int64_t ld3, int32_t C, const float* h1,
+                                     const float* h2, float* dw1, float* small_grads, float* dy, float* workspace,
+                                     int64_t workspace_floats, void* stream);
+
 /* ---- graph construction on the device ---------------------------
  * Inputs: an already resized uint8 RGB image [H, W, C] in HBM.  Outputs: the tensors
  * utils/dataloader.py:49-51 builds (x, pos float32; edge_index int64 [2, E] row-major), in the
