@@ -288,7 +288,10 @@ def test_hip_backward_agrees_with_torch_recompute_backward(G, monkeypatch):
     batch = S.superpixel_like_graphs(6, seed=11)
     x, pos, ei = batch.x.to(DEV), batch.pos.to(DEV), batch.edge_index.to(DEV)
     w = torch.randn(batch.num_nodes, 1, device=DEV)
-    for width in (64, 128, 256):  # resident-weights, streamed-weights (32-row) and 16-row streamed-weights backward kernels
+    # six superpixel graphs are a small batch: the fused / weights-resident K8 kernels at 64, the column-split small-batch
+    # backward (mlp_bwd_col16.hip) at 128, the 16-row streamed kernel at 256.  The throughput kernels of each width class run
+    # in tests/test_gpu_mlp_families.py.
+    for width in (64, 128, 256):
         torch.manual_seed(5)
         m = G.GraphNet(**S.graphnet_kwargs(width, 2))
         grads = {}
@@ -612,8 +615,10 @@ def test_deferred_validation_poisons_the_output_and_raises_at_the_check(G):
 
 @pytest.mark.parametrize("width", [40, 96, 160, 200])
 def test_hip_backward_odd_widths_agree_with_torch_recompute_backward(G, monkeypatch, width):
-    """Widths that are not a multiple of 64 (tails of the 64-column chunks, partial accumulator tiles) through every K8
-    width class, against the PyTorch-ROCm recompute backward of the same ops."""
+    """Widths that are not a multiple of 64 (tails of the 64-column chunks, partial accumulator tiles) through the K8 kernels
+    a batch of four superpixel graphs reaches - the fused / weights-resident kernels (40), the column-split small-batch
+    backward (96), the 16-row streamed kernel (160, 200) - against the PyTorch-ROCm recompute backward of the same ops.  The
+    throughput kernels of each width class run in tests/test_gpu_mlp_families.py."""
     from graphnet_classifier_amd import functional as Fn
     from graphnet_classifier_amd import synthetic as S
     batch = S.superpixel_like_graphs(4, seed=width)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.mlp_family_cases import _ref_forward  # the float64 definition of gnc_mlp_forward_f32
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -30,27 +32,6 @@ def _lin(rng, o, i):
 
 def _D(x):
     return x.double().cpu()
-
-
-def _ref_forward(segs, modes, ws, bs, ln, residual):
-    """float64 definition of gnc_mlp_forward_f32; returns (out, hidden post-activations)."""
-    modes = modes or [0] * len(segs)
-    rows = [(_D(tb) if ix is None else _D(tb)[ix.cpu().long()]) for tb, ix in segs]
-    x = torch.cat([r for r, m in zip(rows, modes) if m == 0], dim=1)
-    z = x @ _D(ws[0]).t() + (_D(bs[0]) if bs[0] is not None else 0)
-    for r, m in zip(rows, modes):
-        if m == 1:
-            z = z + r
-    acts = []
-    for w, b in zip(ws[1:], bs[1:]):
-        z = torch.relu(z)
-        acts.append(z)
-        z = z @ _D(w).t() + (_D(b) if b is not None else 0)
-    if ln is not None:
-        z = torch.nn.functional.layer_norm(z, (z.size(1),), _D(ln[0]), _D(ln[1]), ln[2])
-    if residual is not None:
-        z = z + _D(residual)
-    return z, acts
 
 
 SHAPES = ["encoder3", "projection", "edge_wsplit", "node", "decoder", "h100", "concat_edge", "two_linears"]
