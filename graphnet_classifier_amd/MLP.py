@@ -1,5 +1,6 @@
 """Drop-in for the reference's ``models/MLP.py``: same constructor, same ``state_dict``
-keys (``model.<i>.weight`` ...), forward executed by the fused HIP kernel K4.
+keys (``model.<i>.weight`` ...), forward executed by the fused HIP kernel K4 (``norm_type='BatchNorm1d'``: K4 + the batch-norm
+kernels K14).
 
 Reference: models/MLP.py:5-47.
 """
@@ -76,35 +77,79 @@ class MLP(nn.Module):
         a = self.activation
         return float(getattr(a, "negative_slope", getattr(a, "alpha", 0.0)))
 
+    def _batchnorm_in_library(self, norm) -> bool:
+        """Is this BatchNorm1d served by the K14 kernels?  The constructor defaults are (``momentum=None`` would need a host-side
+        running average factor); any other configuration stays on the PyTorch-ROCm module."""
+        return bool(norm.affine and norm.track_running_stats and norm.momentum == 0.1 and norm.running_mean is not None
+                    and norm.weight.is_cuda and norm.weight.dtype == torch.float32 and norm.num_features <= native.BN_MAX_WIDTH)
+
+    def _folded_batchnorm(self, lin, norm):
+        """(weights, biases) of the Linear chain with the eval-mode BatchNorm folded into the last Linear (K14 fold kernel).
+        Formed from the live parameters and running statistics on every call: nothing is cached, so in-place edits,
+        ``load_state_dict`` and a graph replay always see the current values."""
+        w, b = native.bn_fold(lin[-1].weight, lin[-1].bias, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps)
+        return [m.weight.detach() for m in lin[:-1]] + [w], [m.bias.detach() if m.bias is not None else None for m in lin[:-1]] + [b]
+
     def forward_segments(self, segments, residual: Tensor | None = None, rows: int | None = None) -> Tensor:
         """Run the MLP on the virtual concat of ``segments`` = [(table, int32 index | None)]
         (device tensors), optionally adding ``residual``: concat, gathers, Linear chain,
-        LayerNorm and residual are one kernel launch."""
+        LayerNorm and residual are one kernel launch.  With ``norm_type='BatchNorm1d'``: in training mode the Linear chain is
+        that launch and the batch statistics, the normalisation (+ residual) and their backward run on the K14 kernels; in eval
+        mode without a wanted gradient the normalisation is folded into the last Linear and everything is the one launch again."""
         lin = self._linears()
         require_gpu_param(lin[0].weight, "MLP")
         if self.activation_name not in native.ACTIVATIONS:
             raise NotImplementedError(f"activation nn.{self.activation_name} has no HIP kernel "
                                       f"(available: {sorted(native.ACTIVATIONS)})")
         norm = self.model[-1] if self.norm_type is not None else None
+        if isinstance(norm, nn.BatchNorm1d):
+            return self._forward_batchnorm(lin, norm, segments, residual, rows)
         ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
-        fuse_res = residual if not isinstance(norm, nn.BatchNorm1d) else None
-        y = Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=ln,
-                         activation=self.activation_name, act_param=self._act_param(), residual=fuse_res, rows=rows)
-        if isinstance(norm, nn.BatchNorm1d):  # batch statistics span all rows: PyTorch-ROCm op on the GPU
-            y = norm(y)
-            if residual is not None:
-                y = y + residual
+        return Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=ln,
+                            activation=self.activation_name, act_param=self._act_param(), residual=residual, rows=rows)
+
+    def _forward_batchnorm(self, lin, norm, segments, residual, rows):
+        t0, i0 = segments[0]
+        n_rows = int(rows) if rows is not None else int(i0.numel() if i0 is not None else t0.size(0))
+        wants_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                                  or any(t.requires_grad for t, _ in segments)
+                                                  or (residual is not None and residual.requires_grad))
+        kw = dict(activation=self.activation_name, act_param=self._act_param(), rows=rows)
+        if n_rows > 0 and self._batchnorm_in_library(norm):
+            if norm.training:
+                if n_rows == 1:  # torch.nn.functional.batch_norm's check, before any launch
+                    raise ValueError(f"Expected more than 1 value per channel when training, got input size "
+                                     f"{torch.Size([1, norm.num_features])}")
+                z = Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=None, residual=None, **kw)
+                y = Fn.batch_norm_rows(z, norm.weight, norm.bias, residual, norm.running_mean, norm.running_var, norm.momentum,
+                                       norm.eps, True, inplace=True)  # z is this call's own table
+                norm.num_batches_tracked.add_(1)  # a device op: no host value enters a captured step
+                return y
+            if not wants_grad:
+                weights, biases = self._folded_batchnorm(lin, norm)
+                return Fn.fused_mlp(segments, weights, biases, ln=None, residual=residual, **kw)
+        # every other case (eval mode with a wanted gradient, no rows, a non-default BatchNorm1d): the PyTorch-ROCm module
+        y = Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=None, residual=None, **kw)
+        y = norm(y)
+        if residual is not None:
+            y = y + residual
         return y
 
     def forward_edge_features(self, pos: Tensor, src: Tensor, dst: Tensor) -> Tensor | None:
         """This MLP on the edge features of models/GNN.py:299-302 WITHOUT storing them (K6 as the launch's prologue); None
-        when that form is not available (training, BatchNorm, a shape / batch size no kernel serves this way)."""
+        when that form is not available (training, a BatchNorm the fold does not serve, a shape / batch size no kernel serves
+        this way)."""
         lin = self._linears()
-        if self.activation_name != "ReLU" or isinstance(self.model[-1], nn.BatchNorm1d):
+        if self.activation_name != "ReLU":
             return None
         if torch.is_grad_enabled() and (pos.requires_grad or any(p.requires_grad for p in self.parameters())):
             return None  # the backward needs the feature rows (dW_0)
         norm = self.model[-1] if self.norm_type is not None else None
+        if isinstance(norm, nn.BatchNorm1d):  # eval mode: folded into the last Linear; training mode needs the batch statistics
+            if norm.training or not self._batchnorm_in_library(norm) or not lin[0].weight.is_cuda:
+                return None
+            weights, biases = self._folded_batchnorm(lin, norm)
+            return native.mlp_forward_edge_features(pos, src, dst, weights, biases, ln=None)
         ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
         return native.mlp_forward_edge_features(pos, src, dst, [m.weight for m in lin], [m.bias for m in lin], ln=ln)
 

@@ -8,7 +8,8 @@ reference's only caller that needs gradients is ``utils/train_model.py:41``
 * the fused-MLP backward runs on the hand-written K8 kernels (every width class up to 256); the training
   forward of the widths <= 64 kernels keeps the hidden layers' post-activations for it, the wider ones
   recompute the forward of each tile from the inputs (``GNC_TORCH_BACKWARD=1`` switches to a PyTorch-ROCm
-  recompute for A/B runs; nothing here ever runs on the CPU).
+  recompute for A/B runs; nothing here ever runs on the CPU);
+* batch normalisation over table rows (``norm_type='BatchNorm1d'``) runs on the K14 kernels both ways.
 """
 from __future__ import annotations
 
@@ -306,6 +307,46 @@ def fused_mlp(segments, weights, biases, ln=None, activation: str = "ReLU", act_
     if residual is not None:
         args.append(residual)
     return _FusedMLP.apply(meta, *args)
+
+
+class _BatchNormRows(torch.autograd.Function):
+    """Training-mode batch norm over table rows (K14, csrc/batchnorm.hip), residual add fused into the apply launch."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, residual, running_mean, running_var, momentum, eps):
+        out, mean, invstd = native.bn_forward(z, gamma, beta, residual, running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(z, mean, invstd, gamma)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        z, mean, invstd, gamma = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dz = dgamma = dbeta = None
+        if need[0] or need[1] or need[2]:
+            dz, dgamma, dbeta = native.bn_backward(grad_out, z, mean, invstd, gamma, need_dz=need[0])
+        # x_hat is recomputed from z in both launches; the residual's gradient is grad_out itself (no copy)
+        return (dz, dgamma if need[1] else None, dbeta if need[2] else None, grad_out if need[3] else None, None, None, None, None)
+
+
+def batch_norm_rows(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, residual: torch.Tensor | None,
+                    running_mean: torch.Tensor | None, running_var: torch.Tensor | None, momentum: float, eps: float,
+                    training: bool = True, inplace: bool = False) -> torch.Tensor:
+    """``nn.BatchNorm1d`` in training mode on ``z`` [rows, C] (C <= 256) plus an optional residual, on the K14 kernels: batch
+    statistics (biased variance) normalise the rows, the running statistics - when given - are updated in place with
+    ``momentum``.  ``inplace``: the caller does not need ``z`` afterwards; honoured when no gradient is wanted (the backward
+    reads ``z``).  Eval mode has no operator of its own: an eval-mode module folds the normalisation into its last Linear
+    (``native.bn_fold``)."""
+    if not training:
+        raise NotImplementedError("batch_norm_rows: eval mode is served by folding the normalisation into the last Linear "
+                                  "(native.bn_fold), not by this operator")
+    if z.dim() != 2:
+        raise ValueError(f"batch_norm_rows: expected a [rows, C] table, got shape {tuple(z.shape)}")
+    if z.size(0) == 1:  # torch.nn.functional.batch_norm's check, before any launch
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.size()}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (z, gamma, beta, residual)):
+        return _BatchNormRows.apply(z, gamma, beta, residual, running_mean, running_var, float(momentum), float(eps))
+    return native.bn_forward(z, gamma, beta, residual, running_mean, running_var, float(momentum), float(eps), inplace=inplace)[0]
 
 
 class _EdgeProcessorWSplit(torch.autograd.Function):

@@ -110,6 +110,23 @@ _SIGNATURES = {
                                               c_void_p]),
     "gnc_layer_norm_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_float, c_void_p, c_int64,
                                               c_void_p, c_int64, c_void_p]),
+    "gnc_bn_partials": (c_int32, [c_int64, c_int32]),
+    "gnc_bn_stats_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
+    "gnc_bn_finalize_f32": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "gnc_bn_apply_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                   c_void_p, c_int64, c_void_p]),
+    "gnc_bn_backward_sums_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int32,
+                                           c_void_p]),
+    "gnc_bn_backward_dz_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                         c_int32, c_void_p, c_int64, c_void_p]),
+    "gnc_bn_small_max_rows": (c_int32, []),
+    "gnc_bn_forward_small_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_float, c_float,
+                                           c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gnc_bn_backward_small_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                            c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gnc_bn_fold_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32,
+                                  c_void_p, c_int64, c_void_p, c_void_p]),
     "gnc_adam_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p]),
 }
@@ -1192,6 +1209,165 @@ def layer_norm_backward(y: torch.Tensor, gamma: torch.Tensor, grad_out: torch.Te
                                                y.size(0), y.size(1), eps, gy.data_ptr(), _ld(gy), yhat.data_ptr(), _ld(yhat),
                                                _stream(y)), "gnc_layer_norm_backward_f32")
     return gy, yhat
+
+
+# --------------------------------------------------------------------------- K14 batch normalisation
+BN_MAX_WIDTH = 256
+
+
+def _bn_table(t: torch.Tensor, what: str) -> torch.Tensor:
+    _require_cuda(t)
+    t = _rowmajor(t)
+    if not 1 <= t.size(1) <= BN_MAX_WIDTH:
+        raise NotImplementedError(f"{what}: width {t.size(1)} is outside the batch-norm kernels (1..{BN_MAX_WIDTH})")
+    return t
+
+
+def _bn_vec(t: torch.Tensor, width: int) -> torch.Tensor:
+    _require_cuda(t)
+    if t.dtype != torch.float32 or t.numel() != width:
+        raise ValueError(f"expected a float32 vector of {width} values, got {t.dtype} {tuple(t.shape)}")
+    return t if t.is_contiguous() else t.contiguous()  # only its address is used
+
+
+def bn_partials(rows: int, width: int) -> int:
+    """Partial rows the reducing K14 kernels write for a [rows, width] table (gnc_bn_partials)."""
+    return int(load_library().gnc_bn_partials(rows, width))
+
+
+def bn_stats(z: torch.Tensor, eps: float, momentum: float = 0.0, running_mean: torch.Tensor | None = None,
+             running_var: torch.Tensor | None = None):
+    """(mean, invstd) [C] each of the columns of ``z`` [rows, C] (biased variance, invstd = 1 / sqrt(var + eps)); the running
+    statistics, when given (contiguous float32 [C]), are updated IN PLACE with ``momentum`` (unbiased variance)."""
+    lib = load_library()
+    z = _bn_table(z, "bn_stats")
+    rows, width = z.shape
+    if rows < 1:
+        raise ValueError("bn_stats: no rows")
+    for r in (running_mean, running_var):
+        if r is not None and (not r.is_cuda or r.dtype != torch.float32 or r.numel() != width or not r.is_contiguous()):
+            raise ValueError("bn_stats: running statistics must be contiguous float32 [C] on the GPU")
+    both = torch.empty(2, width, dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        p = lib.gnc_bn_partials(rows, width)
+        part = torch.empty(p, 3 * width, dtype=torch.float32, device=z.device)
+        _check(_launch("bn_stats", z, lambda: lib.gnc_bn_stats_f32(z.data_ptr(), _ld(z), rows, width, part.data_ptr(), p, _stream(z))),
+               "gnc_bn_stats_f32")
+        _check(lib.gnc_bn_finalize_f32(part.data_ptr(), p, rows, width, eps, momentum, both[0].data_ptr(), both[1].data_ptr(),
+                                       running_mean.data_ptr() if running_mean is not None else None,
+                                       running_var.data_ptr() if running_var is not None else None, _stream(z)),
+               "gnc_bn_finalize_f32")
+    return both[0], both[1]
+
+
+def bn_apply(z: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+             residual: torch.Tensor | None = None, inplace: bool = False) -> torch.Tensor:
+    """(z - mean) * invstd * gamma + beta (+ residual); ``inplace`` writes the result over ``z``."""
+    lib = load_library()
+    zt = _bn_table(z, "bn_apply")
+    rows, width = zt.shape
+    if residual is not None:
+        residual = _bn_table(residual, "bn_apply")
+        if residual.shape != zt.shape:
+            raise ValueError(f"bn_apply: residual {tuple(residual.shape)} does not match {tuple(zt.shape)}")
+    out = zt if (inplace and zt is z) else torch.empty(rows, width, dtype=torch.float32, device=zt.device)
+    mean, invstd, gamma, beta = (_bn_vec(v, width) for v in (mean, invstd, gamma, beta))
+    with torch.cuda.device(zt.device):
+        _check(_launch("bn_apply", zt, lambda: lib.gnc_bn_apply_f32(
+            zt.data_ptr(), _ld(zt), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+            residual.data_ptr() if residual is not None else None, _ld(residual) if residual is not None else 0, rows, width,
+            out.data_ptr(), _ld(out), _stream(zt))), "gnc_bn_apply_f32")
+    return out
+
+
+def bn_small_max_rows() -> int:
+    """Row limit of the one-launch kernels (gnc_bn_small_max_rows)."""
+    return int(load_library().gnc_bn_small_max_rows())
+
+
+def bn_forward(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, residual: torch.Tensor | None = None,
+               running_mean: torch.Tensor | None = None, running_var: torch.Tensor | None = None, momentum: float = 0.0,
+               eps: float = 1e-5, inplace: bool = False):
+    """Training-mode batch norm of ``z`` [rows, C] (+ residual): ``(out, mean, invstd)``.  Up to ``bn_small_max_rows()`` rows it is
+    one launch (statistics, running statistics and normalisation), above that ``bn_stats`` + ``bn_apply``."""
+    lib = load_library()
+    zt = _bn_table(z, "bn_forward")
+    rows, width = zt.shape
+    if rows < 1 or rows > lib.gnc_bn_small_max_rows():
+        mean, invstd = bn_stats(zt, eps, momentum, running_mean, running_var)
+        return bn_apply(zt, mean, invstd, gamma, beta, residual, inplace=inplace and zt is z), mean, invstd
+    if residual is not None:
+        residual = _bn_table(residual, "bn_forward")
+        if residual.shape != zt.shape:
+            raise ValueError(f"bn_forward: residual {tuple(residual.shape)} does not match {tuple(zt.shape)}")
+    for r in (running_mean, running_var):
+        if r is not None and (not r.is_cuda or r.dtype != torch.float32 or r.numel() != width or not r.is_contiguous()):
+            raise ValueError("bn_forward: running statistics must be contiguous float32 [C] on the GPU")
+    gamma, beta = _bn_vec(gamma, width), _bn_vec(beta, width)
+    out = zt if (inplace and zt is z) else torch.empty(rows, width, dtype=torch.float32, device=zt.device)
+    both = torch.empty(2, width, dtype=torch.float32, device=zt.device)
+    with torch.cuda.device(zt.device):
+        _check(_launch("bn_forward_small", zt, lambda: lib.gnc_bn_forward_small_f32(
+            zt.data_ptr(), _ld(zt), gamma.data_ptr(), beta.data_ptr(), residual.data_ptr() if residual is not None else None,
+            _ld(residual) if residual is not None else 0, rows, width, eps, momentum, out.data_ptr(), _ld(out), both[0].data_ptr(),
+            both[1].data_ptr(), running_mean.data_ptr() if running_mean is not None else None,
+            running_var.data_ptr() if running_var is not None else None, _stream(zt))), "gnc_bn_forward_small_f32")
+    return out, both[0], both[1]
+
+
+def bn_backward(grad_out: torch.Tensor, z: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: torch.Tensor,
+                need_dz: bool = True):
+    """(dz, dgamma, dbeta) of out = (z - mean(z)) * invstd(z) * gamma + beta over the rows of ``z``; ``dz`` is None when not asked."""
+    lib = load_library()
+    z, grad_out = _bn_table(z, "bn_backward"), _bn_table(grad_out, "bn_backward")
+    rows, width = z.shape
+    if grad_out.shape != z.shape or rows < 1:
+        raise ValueError(f"bn_backward: grad_out {tuple(grad_out.shape)} does not match z {tuple(z.shape)}")
+    mean, invstd, gamma = (_bn_vec(v, width) for v in (mean, invstd, gamma))
+    sums = torch.empty(2, width, dtype=torch.float32, device=z.device)  # row 0: d beta, row 1: d gamma
+    dz = torch.empty(rows, width, dtype=torch.float32, device=z.device) if need_dz else None
+    if rows <= lib.gnc_bn_small_max_rows():  # one launch: a workgroup per 4 columns sums its rows, then writes its dz columns
+        with torch.cuda.device(z.device):
+            _check(_launch("bn_backward_small", z, lambda: lib.gnc_bn_backward_small_f32(
+                grad_out.data_ptr(), _ld(grad_out), z.data_ptr(), _ld(z), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), rows,
+                width, dz.data_ptr() if need_dz else None, _ld(dz) if need_dz else 0, sums[0].data_ptr(), sums[1].data_ptr(),
+                _stream(z))), "gnc_bn_backward_small_f32")
+        return dz, sums[1], sums[0]
+    with torch.cuda.device(z.device):
+        p = lib.gnc_bn_partials(rows, width)
+        part = torch.empty(p, 2 * width, dtype=torch.float32, device=z.device)
+        _check(_launch("bn_backward_sums", z, lambda: lib.gnc_bn_backward_sums_f32(
+            grad_out.data_ptr(), _ld(grad_out), z.data_ptr(), _ld(z), mean.data_ptr(), invstd.data_ptr(), rows, width,
+            part.data_ptr(), p, _stream(z))), "gnc_bn_backward_sums_f32")
+        _check(lib.gnc_reduce_partials_f32(part.data_ptr(), p, 2 * width, 2, width, sums.data_ptr(), width, None, _stream(z)),
+               "gnc_reduce_partials_f32")
+        if need_dz:
+            _check(_launch("bn_backward_dz", z, lambda: lib.gnc_bn_backward_dz_f32(
+                grad_out.data_ptr(), _ld(grad_out), z.data_ptr(), _ld(z), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+                sums[0].data_ptr(), sums[1].data_ptr(), rows, width, dz.data_ptr(), _ld(dz), _stream(z))), "gnc_bn_backward_dz_f32")
+    return dz, sums[1], sums[0]
+
+
+def bn_fold(weight: torch.Tensor, bias: torch.Tensor | None, gamma: torch.Tensor, beta: torch.Tensor, running_mean: torch.Tensor,
+            running_var: torch.Tensor, eps: float):
+    """(W', b'): the Linear (weight [out, in], bias) followed by an eval-mode batch norm, as one Linear.  Fresh buffers on every
+    call (nothing is cached: the live parameters and running statistics are read each time)."""
+    lib = load_library()
+    _require_cuda(weight, bias)
+    w = _rowmajor(weight.detach())
+    m, k = w.shape
+    if not 1 <= m <= BN_MAX_WIDTH:
+        raise NotImplementedError(f"bn_fold: width {m} is outside the batch-norm kernels (1..{BN_MAX_WIDTH})")
+    gamma, beta, running_mean, running_var = (_bn_vec(v, m) for v in (gamma, beta, running_mean, running_var))
+    b = _bn_vec(bias, m) if bias is not None else None
+    ldo = (k + 3) // 4 * 4  # rows of 16-B pieces for the kernels that read the weights as vectors
+    w_out = torch.empty(m, ldo, dtype=torch.float32, device=w.device)[:, :k]
+    b_out = torch.empty(m, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        _check(lib.gnc_bn_fold_f32(w.data_ptr(), _ld(w), b.data_ptr() if b is not None else None, gamma.data_ptr(), beta.data_ptr(),
+                                   running_mean.data_ptr(), running_var.data_ptr(), eps, m, k, w_out.data_ptr(), ldo,
+                                   b_out.data_ptr(), _stream(w)), "gnc_bn_fold_f32")
+    return w_out, b_out
 
 
 # --------------------------------------------------------------------------- fused Adam

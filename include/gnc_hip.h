@@ -448,6 +448,62 @@ int gnc_layer_norm_backward_f32(const float* y, int64_t ld_y, const float* gamma
                                 int64_t rows, int32_t width, float eps, float* grad_y, int64_t ld_gy, float* yhat,
                                 int64_t ld_yhat, void* stream);
 
+/* ---- K14: batch normalisation over table rows (added within ABI 20: new entry points only, nothing existing changes; two
+ * host tests pin the version to 20) ---------------------------------------------------------
+ * Replaces the `nn.BatchNorm1d(out_dim)` that models/MLP.py:29-35 appends for norm_type='BatchNorm1d' (the module runs at
+ * models/MLP.py:47), its autograd, and - in eval mode - the op altogether.  z [rows, width] fp32, row stride ld >= width,
+ * 1 <= width <= 256, any row count (64-bit row offsets).  Rows of 16-B pieces (width % 4 == 0, ld % 4 == 0, 16-B aligned
+ * base) are read with vector loads, anything else with scalar loads by the same kernels.
+ *
+ * Training forward, three launches:
+ *   gnc_bn_stats_f32     partial[b] = [ count (width) | mean (width) | M2 (width) ] of the b-th CONTIGUOUS range of rows,
+ *                        gnc_bn_partials(rows, width) rows in all, every one fully written (no zero-initialised scratch).
+ *                        Chunked two-pass + Chan merges: no sum-of-squares cancellation for columns with |mean| >> std.
+ *   gnc_bn_finalize_f32  merges the partial rows in index order: mean[c], invstd[c] = 1 / sqrt(var + eps) (biased var), and,
+ *                        where given (either may be NULL), in place
+ *                          running_mean = (1 - momentum) running_mean + momentum mean
+ *                          running_var  = (1 - momentum) running_var  + momentum var rows / (rows - 1)     (rows >= 2)
+ *   gnc_bn_apply_f32     out = (z - mean) * invstd * gamma + beta (+ residual; NULL = none).  `out` may be `z`.
+ * Backward, three launches:
+ *   gnc_bn_backward_sums_f32  partial[b] = [ colsum(G) (width) | colsum(G * x_hat) (width) ], x_hat = (z - mean) * invstd
+ *                             recomputed from z: the partial layout of gnc_colsum_pair_f32, gnc_bn_partials(rows, width) rows;
+ *                             gnc_reduce_partials_f32(partial, parts, 2 * width, 2, width, sums, width, NULL) leaves
+ *                             sums = [ d beta | d gamma ]
+ *   gnc_bn_backward_dz_f32    grad_z = gamma * invstd * (G - d beta / rows - x_hat * d gamma / rows)
+ *   (the gradient of the residual is grad_out itself)
+ * Small tables (rows <= gnc_bn_small_max_rows(), the one-graph-per-step regime), ONE launch each way - a workgroup owns 4 columns
+ * over all rows, so nothing is exchanged between workgroups and no scratch is needed:
+ *   gnc_bn_forward_small_f32   statistics + running statistics + normalise (+ residual); also writes mean / invstd [width]
+ *   gnc_bn_backward_small_f32  dbeta / dgamma [width] and grad_z (NULL: not wanted)
+ * Eval mode:
+ *   gnc_bn_fold_f32      weight_out[m, :] = s[m] weight[m, :], bias_out[m] = s[m] bias[m] + beta[m] - running_mean[m] s[m] with
+ *                        s = gamma / sqrt(running_var + eps) (bias may be NULL = zeros): the last Linear of the MLP with the
+ *                        normalisation folded in, so that one gnc_mlp_forward_f32 launch without a norm does everything
+ *                        (residual and the edge-feature prologue included).  Call it on every forward: nothing is cached.
+ * Fixed summation / merge order everywhere: bitwise reproducible, no float atomics.
+ */
+int gnc_bn_partials(int64_t rows, int32_t width);
+int gnc_bn_stats_f32(const float* z, int64_t ld_z, int64_t rows, int32_t width, float* partial, int32_t num_partials, void* stream);
+int gnc_bn_finalize_f32(const float* partial, int32_t num_partials, int64_t rows, int32_t width, float eps, float momentum,
+                        float* mean, float* invstd, float* running_mean, float* running_var, void* stream);
+int gnc_bn_apply_f32(const float* z, int64_t ld_z, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                     const float* residual, int64_t ld_res, int64_t rows, int32_t width, float* out, int64_t ld_out, void* stream);
+int gnc_bn_backward_sums_f32(const float* grad_out, int64_t ld_grad, const float* z, int64_t ld_z, const float* mean,
+                             const float* invstd, int64_t rows, int32_t width, float* partial, int32_t num_partials, void* stream);
+int gnc_bn_backward_dz_f32(const float* grad_out, int64_t ld_grad, const float* z, int64_t ld_z, const float* mean,
+                           const float* invstd, const float* gamma, const float* dbeta, const float* dgamma, int64_t rows,
+                           int32_t width, float* grad_z, int64_t ld_gz, void* stream);
+int gnc_bn_small_max_rows(void);
+int gnc_bn_forward_small_f32(const float* z, int64_t ld_z, const float* gamma, const float* beta, const float* residual,
+                             int64_t ld_res, int64_t rows, int32_t width, float eps, float momentum, float* out, int64_t ld_out,
+                             float* mean, float* invstd, float* running_mean, float* running_var, void* stream);
+int gnc_bn_backward_small_f32(const float* grad_out, int64_t ld_grad, const float* z, int64_t ld_z, const float* mean,
+                              const float* invstd, const float* gamma, int64_t rows, int32_t width, float* grad_z, int64_t ld_gz,
+                              float* dbeta, float* dgamma, void* stream);
+int gnc_bn_fold_f32(const float* weight, int64_t ld_w, const float* bias, const float* gamma, const float* beta,
+                    const float* running_mean, const float* running_var, float eps, int32_t out_dim, int32_t in_dim,
+                    float* weight_out, int64_t ld_wo, float* bias_out, void* stream);
+
 /* ---- read-out classifier of ONE graph (ABI 18) -------------------------------------------------------------------
  * Replaces `LinearClassifier.forward` (models/GNN.py:312-325, called at :340) for the single-graph call of the reference's loops:
  * logits = fc3(relu(fc2(relu(fc1(y))))) over the flattened node outputs y [F]; weights as nn.Linear holds them.  One launch
