@@ -93,9 +93,11 @@ constexpr int RNT = RWAVES * 64;
 // per row and tile (lane & 31 = tile row) where it lies - no zero-padded [rows, 4] copy in front of the launch.
 // SPLIT (chosen by the launcher from the launch's shape, never by another template flag): which Linears run on the bf16
 // matrix pipe in the fp32-accurate 3-way split form (mlp_device.h) - 1: all of them (the W-split edge processor: one
-// row-ordered MATMUL step, two ADD segments, residual in registers), 2: all but the first (the encoders: first Linear
-// K <= 4, one fp32 MFMA k-group).  Their weights are resident as three bf16 planes (SCH floats per chunk, after the
-// fp32 chunks).  0: every Linear in fp32 MFMA (GNC_MLP_F32_EXACT=1 keeps every launch there).
+// row-ordered MATMUL step, two ADD segments, residual in registers; plain stacks of one MATMUL step with no ADD segments:
+// the decoder's one output tile, the single-Linear projection and its DUAL form, which splits a K-group's rows once for
+// both matrices), 2: all but the first (the encoders: first Linear K <= 4, one fp32 MFMA k-group; the node processors:
+// two MATMUL steps, whose four chunks do not fit in LDS as planes).  Their weights are resident as three bf16 planes (SCH
+// floats per chunk, after the fp32 chunks).  0: every Linear in fp32 MFMA (GNC_MLP_F32_EXACT=1 keeps every launch there).
 // AGGONLY (with AGG; gnc_mlp_forward_agg_only_f32): only the aggregate is wanted - the output rows are stored only where
 // gnc_agg_fixup_f32 reads them, i.e. the rows of the wave range's first and last destination; every other row is dropped.
 // A destination cut by range boundaries is the first or the last destination of EVERY range that holds rows of it, so the
@@ -107,7 +109,9 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int WT = HT > OT ? HT : OT;
   constexpr int CH = WT * 32 * LDSW;  // floats per resident weight chunk
-  static_assert(SPLIT == 0 || (WT == 2 && NMM == 1 && !DUAL && (SPLIT == 1 || NADD == 0)), "split shapes");
+  static_assert(SPLIT == 0 || (HT == 2 && SPLIT == 1 && NMM == 1 && ((NADD == 2 && RESREG && !DUAL) || (NADD == 0 && !RESREG))) ||
+                    (HT == 2 && OT == 2 && SPLIT == 2 && NADD == 0 && !DUAL),
+                "split shapes");
   // split instances: chunks [0, nf32) fp32, the rest split
   constexpr int nf32 = SPLIT == 1 ? 0 : NMM;
   __bf16* const wsp = reinterpret_cast<__bf16*>(lds + nf32 * CH);
@@ -132,11 +136,21 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   stage_params<RNT>(pbuf, d, PSTRIDE, tid);
   if constexpr (SPLIT != 0) {  // split chunks: three bf16 planes each (mlp_device.h)
     const int ldw0 = ldw_of(d, 0);
-    const bool w0v = (ldw0 % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[0]) & 15u) == 0) && (d.seg[0].wcol % 4 == 0);
-    if constexpr (SPLIT == 1)
-      stage_weights_split<RNT>(wsp, d.weight[0], ldw0, d.out_dim[0], d.seg[0].wcol, d.seg[0].wcol + d.seg[0].width, w0v, tid);
-    else
-      stage_weights<WT * 32, RNT>(wres, d.weight[0], ldw0, d.out_dim[0], d.seg[0].wcol, d.seg[0].wcol + d.seg[0].width, 16, w0v, tid);
+    const bool w0v = (ldw0 % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[0]) & 15u) == 0);
+    if constexpr (SPLIT == 1) {
+      stage_weights_split<RNT>(wsp, d.weight[0], ldw0, d.out_dim[0], d.seg[0].wcol, d.seg[0].wcol + d.seg[0].width,
+                               w0v && (d.seg[0].wcol % 4 == 0), tid);
+    } else {  // class 2: every chunk of the first Linear stays fp32
+#pragma unroll
+      for (int s = 0; s < NMM; ++s)
+        stage_weights<WT * 32, RNT>(wres + s * CH, d.weight[0], ldw0, d.out_dim[0], d.seg[s].wcol, d.seg[s].wcol + d.seg[s].width, 16,
+                                    w0v && (d.seg[s].wcol % 4 == 0), tid);
+    }
+    if constexpr (DUAL) {  // the second matrix's planes behind the first's
+      const int ldw1 = ldw_of(d, 1);
+      const bool w1v = (ldw1 % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[1]) & 15u) == 0) && (d.seg[0].wcol % 4 == 0);
+      stage_weights_split<RNT>(wsp + 3 * SPLANE, d.weight[1], ldw1, d.out_dim[0], d.seg[0].wcol, d.seg[0].wcol + d.seg[0].width, w1v, tid);
+    }
     for (int l = 1; l < L; ++l) {
       const int ldw = ldw_of(d, l);
       const bool wv = (ldw % 4 == 0) && ((reinterpret_cast<uintptr_t>(d.weight[l]) & 15u) == 0);
@@ -412,7 +426,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       }
       PROBE(7);  // issue of the next rows' loads
       if (!interleaved) {
-        if constexpr (SPLIT == 1) mma_chunk_from_lds_split<HT>(hid, abuf, wsplit(s), (sv[s].width + 15) >> 4, i, h);
+        if constexpr (SPLIT == 1 && DUAL) {}  // both products below, from one split of the rows
+        else if constexpr (SPLIT == 1) mma_chunk_from_lds_split<HT>(hid, abuf, wsplit(s), (sv[s].width + 15) >> 4, i, h);
         else mma_chunk_from_lds<HT>(hid, abuf, wres + s * CH, (sv[s].width + 7) >> 3, i, h);
       }
       if constexpr (RESREG) if (s == NMM - 1) {
@@ -440,7 +455,18 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
     f32x16 hidb[DUAL ? HT : 1];
     if constexpr (DUAL) {  // the second projection of the staged rows (same tile, the other resident weight chunk)
       init_bias<HT>(hidb, pbuf, h);  // (no bias: zeros)
-      mma_chunk_from_lds<HT>(hidb, abuf, wres + CH, (sv[0].width + 7) >> 3, i, h);
+      if constexpr (SPLIT == 1) {  // a K-group's rows are split once and feed both matrices' six products
+        const int kc16 = (sv[0].width + 15) >> 4;
+#pragma unroll
+        for (int kg = 0; kg < 4; ++kg)
+          if (kg < kc16) {
+            const bf16x8x3 x = split_lds_group(abuf, kg, i, h);
+            mma_group_split<HT>(hid, x, wsplit(0), kg, i, h);
+            mma_group_split<HT>(hidb, x, wsplit(1), kg, i, h);
+          }
+      } else {
+        mma_chunk_from_lds<HT>(hidb, abuf, wres + CH, (sv[0].width + 7) >> 3, i, h);
+      }
     }
     if (L == 1) {  // plain projection
       if (d.ln_gamma) layer_norm_tiles<HT>(hid, pbuf + L * PSTRIDE, pbuf + (L + 1) * PSTRIDE, out_dim, d.ln_eps, h);
@@ -646,14 +672,18 @@ int launch(const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t s
   return gnc::check_launch("mlp_resident_kernel");
 }
 
-// the launch in its split class (see SPLIT at mlp_resident_kernel): 1 = the W-split edge processor, 2 = the encoders
+// the launch in its split class (see SPLIT at mlp_resident_kernel): 1 = the W-split edge processor, the decoder and the
+// single-Linear projection, 2 = the encoders and the node processors
 template <int HT, int OT, int NMM, int NADD, bool RESREG, bool AGG = false, bool SAVE = false, bool FULL = false, int EF = 0,
           bool AGGONLY = false>
 int launch_cls(int split, const gnc_mlp_desc_t& d, int total_chunks, size_t smem, hipStream_t stream) {
   if constexpr (HT == 2 && OT == 2 && NMM == 1 && NADD == 2 && RESREG) {
     if (split == 1) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 1, AGGONLY>(d, total_chunks, smem, stream);
   }
-  if constexpr (HT == 2 && OT == 2 && NMM == 1 && NADD == 0 && !RESREG && !AGG && !FULL) {
+  if constexpr (HT == 2 && NMM == 1 && NADD == 0 && !RESREG && !AGG && !SAVE && !FULL && EF == 0) {
+    if (split == 1) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 1>(d, total_chunks, smem, stream);
+  }
+  if constexpr (HT == 2 && OT == 2 && NADD == 0 && !AGG && !FULL && ((NMM == 1 && !RESREG) || (NMM == 2 && EF == 0))) {
     if (split == 2) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 2>(d, total_chunks, smem, stream);
   }
   if (split) return GNC_ERR_UNSUPPORTED;  // a class without its instance: never taken (the launcher's tests below)
@@ -661,6 +691,12 @@ int launch_cls(int split, const gnc_mlp_desc_t& d, int total_chunks, size_t smem
 }
 
 }  // namespace
+
+// A/B switch: the fp32 path for every launch
+static bool f32_exact() {
+  static const bool v = getenv("GNC_MLP_F32_EXACT") != nullptr;
+  return v;
+}
 
 extern "C" int gnc_mlp_agg_fix_len(void) { return 2 * gnc::num_cu() * RWAVES; }
 
@@ -694,9 +730,12 @@ int gnc_mlp::launch_resident_dual(const float* x, int64_t ld_x, int64_t rows, co
   d.ld_out = (int32_t)ld_out;
   d.rows = rows;
   const int total_chunks = 2;
-  const size_t floats = (size_t)total_chunks * 2 * 32 * LDSW + (size_t)(1 + 2) * 2 * 32 + (size_t)RWAVES * RPW * LDSW;
+  // split class 1 like the single-Linear projection of launch_resident (bit-identical to two such launches): 122.8 KB
+  const bool split = !f32_exact();
+  const size_t floats = (size_t)total_chunks * (split ? SCH : 2 * 32 * LDSW) + (size_t)(1 + 2) * 2 * 32 + (size_t)RWAVES * RPW * LDSW;
   *launched = true;
-  return launch<2, 2, 1, 0, false, false, false, false, 0, true>(d, total_chunks, floats * sizeof(float), stream);
+  return split ? launch<2, 2, 1, 0, false, false, false, false, 0, true, 1>(d, total_chunks, floats * sizeof(float), stream)
+               : launch<2, 2, 1, 0, false, false, false, false, 0, true>(d, total_chunks, floats * sizeof(float), stream);
 }
 
 int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hipStream_t stream, bool* launched,
@@ -755,23 +794,35 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
 
   // Split class (bf16 matrix pipe, fp32-accurate 3-way split; mlp_resident_kernel): decided by the shape alone, so that
   // every instance of a shape (AGG / SAVE / FULL / EF variants, fused or separate K1) computes the same bits.
-  //   1: the W-split edge processor - one MATMUL segment, two ADD segments, residual = the MATMUL rows;
-  //   2: the encoders - first Linear K <= 4 (computed K6 rows, the [rows, 3] node features, or a [rows, <= 4] table),
-  //      hidden width 64.
-  // Everything else (node processors, projections, decoder, 64-wide plain shapes) stays in fp32 MFMA.
-  static const bool f32_exact = getenv("GNC_MLP_F32_EXACT") != nullptr;  // A/B switch: the fp32 path everywhere
+  //   1: every Linear split -
+  //      the W-split edge processor: one MATMUL segment, two ADD segments, residual = the MATMUL rows;
+  //      the decoder: one row-ordered MATMUL segment, hidden width 64, out width <= 32 (one output tile);
+  //      the single-Linear projection: one row-ordered MATMUL segment, out width 33..64 (launch_resident_dual is its
+  //      two-matrix form and lands in the same class);
+  //   2: all but the first Linear, hidden width 64 -
+  //      the encoders: first Linear K <= 4 (computed K6 rows, the [rows, 3] node features, or a [rows, <= 4] table);
+  //      the node processors: two row-ordered MATMUL segments (four chunks of planes would not fit in LDS).
+  // Everything else (64-wide plain stacks with a wide output, three MATMUL segments, gathered MATMUL rows) stays in fp32 MFMA.
   int split = 0;
-  if (!f32_exact && T == 2 && L >= 2 && !narrow_out && nmm == 1) {
-    bool hidden64 = true;
+  if (!f32_exact() && T == 2) {
+    bool hidden64 = true, row_ordered = !d.ef_pos && !n3;
     for (int l = 0; l < L - 1; ++l) hidden64 = hidden64 && d.out_dim[l] == KC;
-    if (nadd == 2 && resreg) split = 1;
-    else if (nadd == 0 && !resreg && hidden64 && d.seg[0].width <= 4) split = 2;
+    for (int s = 0; s < d.num_segments; ++s) row_ordered = row_ordered && !d.seg[s].index;
+    if (nadd == 2) {
+      if (nmm == 1 && resreg && L >= 2 && !narrow_out) split = 1;
+    } else if (nmm == 1 && !resreg && row_ordered && (L == 1 ? !narrow_out : (narrow_out && hidden64))) {
+      split = 1;
+    } else if (L >= 2 && !narrow_out && hidden64) {
+      if (nmm == 1 && !resreg && d.seg[0].width <= 4) split = 2;
+      else if (nmm == 2 && row_ordered) split = 2;
+    }
   }
   auto smem_of = [&](int nsplit) {  // bytes of LDS: fp32 chunks, split chunks (1.6x), parameters, the waves' row tiles
     return ((size_t)(total_chunks - nsplit) * T * 32 * LDSW + (size_t)nsplit * SCH + (size_t)(L + 2) * T * 32 +
             (size_t)RWAVES * RPW * LDSW) * sizeof(float);
   };
-  // c3: 150.3 KB for the edge processor (3 split chunks), 140.3 KB for a 3-Linear encoder; deeper stacks keep fp32
+  // c3: 150.3 KB for the edge processor and the decoder (3 split chunks), 140.3 KB for a 3-Linear encoder, 157.3 KB for the
+  // node processor (2 fp32 + 2 split chunks); deeper stacks keep fp32
   if (split && smem_of(split == 1 ? total_chunks : total_chunks - nmm) > 160 * 1024) split = 0;
   const size_t smem = smem_of(split == 1 ? total_chunks : (split == 2 ? total_chunks - nmm : 0));
   if (smem > 160 * 1024) return GNC_OK;
@@ -802,8 +853,8 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
     *launched = true;
     if (probe_only) return GNC_OK;
     if (nmm == 2)
-      return resreg ? launch<2, 2, 2, 0, true, false, true>(d, total_chunks, smem, stream)
-                    : launch<2, 2, 2, 0, false, false, true>(d, total_chunks, smem, stream);
+      return resreg ? launch_cls<2, 2, 2, 0, true, false, true>(split, d, total_chunks, smem, stream)
+                    : launch_cls<2, 2, 2, 0, false, false, true>(split, d, total_chunks, smem, stream);
     if (d.agg_out) return full64 ? launch_cls<2, 2, 1, 2, true, true, true, true>(split, d, total_chunks, smem, stream)
                                  : launch_cls<2, 2, 1, 2, true, true, true>(split, d, total_chunks, smem, stream);
     if (nadd == 2) return launch_cls<2, 2, 1, 2, true, false, true>(split, d, total_chunks, smem, stream);
@@ -833,7 +884,7 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
   } while (0)
   if (narrow_out) {  // one output tile
     *launched = true;
-    return T == 2 ? launch<2, 1, 1, 0, false>(d, total_chunks, smem, stream)
+    return T == 2 ? launch_cls<2, 1, 1, 0, false>(split, d, total_chunks, smem, stream)
                   : launch<1, 1, 1, 0, false>(d, total_chunks, smem, stream);
   }
   if (T == 2) {
@@ -842,7 +893,8 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
                                  : launch<2, 2, 1, 2, false>(d, total_chunks, smem, stream);
     if (nmm == 1) return resreg ? launch<2, 2, 1, 0, true>(d, total_chunks, smem, stream)
                                 : launch_cls<2, 2, 1, 0, false>(split, d, total_chunks, smem, stream);
-    if (nmm == 2) GNC_RES(2, 2, 0);
+    if (nmm == 2) return resreg ? launch_cls<2, 2, 2, 0, true>(split, d, total_chunks, smem, stream)
+                                : launch_cls<2, 2, 2, 0, false>(split, d, total_chunks, smem, stream);
     GNC_RES(2, 3, 0);
   }
   if (nadd == 2) GNC_RES(1, 1, 2);
