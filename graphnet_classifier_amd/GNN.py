@@ -382,6 +382,11 @@ class CapturedForward:
                 y = y[:n]
                 return model.classifier(y.flatten()) if isinstance(model, CombinedModel) else y
 
+        self._capture(run)
+
+    def _capture(self, run) -> None:
+        """Warm ``run`` up on a side stream, then record it: ``self.graph`` replays it, ``self.out`` is its result."""
+        dev = self.device
         with torch.no_grad():
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
@@ -441,6 +446,117 @@ class CapturedForward:
         if status is not None and bool((status.any() | self._range_flag).item()):
             self._range_flag.zero_()
             raise IndexError(f"edge_index has node ids outside [0, {self.num_nodes})")
+
+
+class RaggedBatchFeed:
+    """The fixed input buffers of a hipGraph captured over RAGGED mini-batches (superpixel batches: another region adjacency and
+    other node counts in every batch) and the ONE launch that fills them from a collated ``synthetic.GraphBatch``
+    (``native.pad_graph_batch``; the host offsets and labels travel in the kernel arguments, so a call copies nothing else).
+
+    With ``M = node_capacity``, ``C = edge_capacity`` and ``rows, D = native.ragged_batch_layout(M, C)``: ``x`` / ``pos`` hold the
+    batch's N rows, zero slack rows ``[N, M)`` that belong to no graph, and D zero dummy rows that are never written;
+    ``edge_index`` [2, C] holds the batch's E edges and, behind them, self-loops of the dummies; ``graph_ptr`` [G + 1] and
+    ``labels`` [G] are int64.  ``flag`` is sticky: the feed sets it when an edge leaves its own graph's node range (another
+    graph, a slack or dummy row, a negative id), and only ``check`` clears it.  G is fixed."""
+
+    def __init__(self, batch, edge_capacity: int, node_capacity: int, device, with_labels: bool, who: str = "RaggedBatchFeed"):
+        self.who = who
+        self.num_graphs = G = int(batch.num_graphs)
+        self.edge_capacity, self.node_capacity = C, M = int(edge_capacity), int(node_capacity)
+        if G > native.PAD_BATCH_MAX_GRAPHS:
+            raise ValueError(f"{who}: {G} graphs, the feed launch takes at most {native.PAD_BATCH_MAX_GRAPHS}")
+        self.feature_shapes = (tuple(batch.x.shape[1:]), tuple(batch.pos.shape[1:]))
+        self._require_fit(batch)
+        self.rows, self.dummies = native.ragged_batch_layout(M, C)
+        self.x = torch.zeros(self.rows, *self.feature_shapes[0], dtype=torch.float32, device=device)
+        self.pos = torch.zeros(self.rows, *self.feature_shapes[1], dtype=torch.float32, device=device)
+        self.edge_index = torch.zeros(2, C, dtype=torch.int64, device=device)
+        self.graph_ptr = torch.zeros(G + 1, dtype=torch.int64, device=device)
+        self.labels = torch.zeros(G, dtype=torch.int64, device=device) if with_labels else None
+        self.flag = torch.zeros(1, dtype=torch.int32, device=device)
+        self.num_nodes = 0  # of the batch fed last (the IndexError's message)
+
+    def matches(self, batch) -> bool:
+        return (int(batch.num_graphs) == self.num_graphs and batch.x.size(0) <= self.node_capacity
+                and batch.edge_index.dim() == 2 and batch.edge_index.size(1) <= self.edge_capacity
+                and (tuple(batch.x.shape[1:]), tuple(batch.pos.shape[1:])) == self.feature_shapes)
+
+    def _require_fit(self, batch) -> None:
+        if not self.matches(batch):
+            raise ValueError(f"{self.who}: a batch of {int(batch.num_graphs)} graphs / {batch.x.size(0)} nodes / "
+                             f"{batch.edge_index.size(1)} edges with features {tuple(batch.x.shape[1:])} / {tuple(batch.pos.shape[1:])} "
+                             f"does not fit the captured {self.num_graphs} graphs / {self.node_capacity} nodes / "
+                             f"{self.edge_capacity} edges with features {self.feature_shapes[0]} / {self.feature_shapes[1]}")
+
+    def __call__(self, batch, labels=None) -> None:
+        self._require_fit(batch)
+        if (labels is None) != (self.labels is None):
+            raise ValueError(f"{self.who}: labels are {'not ' if self.labels is None else ''}part of this capture")
+        dev = self.x.device
+        x = batch.x.to(device=dev, dtype=torch.float32, non_blocking=True)
+        pos = batch.pos.to(device=dev, dtype=torch.float32, non_blocking=True)
+        ei = batch.edge_index.to(device=dev, dtype=torch.int64, non_blocking=True)
+        by_value = labels
+        if isinstance(labels, Tensor) and labels.is_cuda:  # device labels: reading them would synchronise; one small copy instead
+            self.labels.copy_(labels.reshape(-1), non_blocking=True)
+            by_value = None
+        native.pad_graph_batch(x, pos, ei, batch.graph_ptr, batch.edge_ptr, by_value, self.node_capacity, self.edge_capacity,
+                               self.x, self.pos, self.edge_index, self.graph_ptr, self.labels if by_value is not None else None,
+                               self.flag)
+        self.num_nodes = int(batch.x.size(0))
+
+    def check(self, status: Tensor | None) -> None:
+        """One host sync for the sticky flag and ``status`` (the flags of the LAST replayed topology build); clears the sticky
+        flag and raises the IndexError of models/GNN.py:18-20 when either is set."""
+        flags = self.flag if status is None else torch.cat([self.flag, status.reshape(-1).to(torch.int32)])
+        if any(flags.tolist()):
+            self.flag.zero_()
+            raise IndexError(f"edge_index has node ids outside their graph's node range (batch of {self.num_nodes} nodes)")
+
+
+def _has_batchnorm(model: nn.Module) -> bool:
+    return any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules())
+
+
+class CapturedRaggedBatchForward(CapturedForward):
+    """``CombinedModel.forward_batched(graph_ptr=...)`` for ANY mini-batch of G graphs with at most ``node_capacity`` nodes and
+    ``edge_capacity`` edges in all, captured into a hipGraph: ``CapturedForward``'s padded form extended to G graphs.  A call is
+    the feed launch (``RaggedBatchFeed``) and the replay; inside the graph run the topology build over the padded buffers
+    (deferred validation: device flags, no host sync), ``GraphNet.forward_device`` and the batched read-out with the DEVICE
+    ``graph_ptr``.  Slack and dummy rows only talk to dummies and belong to no graph, so the logits [G, classes] are those of
+    the eager call.  G is fixed per capture; ``matches(batch)`` says whether a batch fits, a call with one that does not raises
+    ValueError.  ``check()``: one host sync, raises IndexError when an edge list fed since the last check left its graph."""
+
+    def __init__(self, model: nn.Module, batch, edge_capacity: int, node_capacity: int):
+        if not isinstance(model, CombinedModel):
+            raise TypeError("CapturedRaggedBatchForward: a CombinedModel expected")
+        dev = require_gpu_param(next(model.parameters()), "CapturedRaggedBatchForward")
+        if model.training and _has_batchnorm(model):
+            # batch statistics span ALL rows: the dummy rows would enter them (eval mode normalises row by row)
+            raise NotImplementedError("CapturedRaggedBatchForward: a BatchNorm model must be in eval() mode")
+        self.model, self.device = model, dev
+        self.feed = RaggedBatchFeed(batch, edge_capacity, node_capacity, dev, with_labels=False, who="CapturedRaggedBatchForward")
+        self.edge_capacity, self.node_capacity, self.num_graphs = self.feed.edge_capacity, self.feed.node_capacity, self.feed.num_graphs
+        self._status = None
+        self.feed(batch)
+        feed = self.feed
+
+        def run():
+            topo = GraphTopology(feed.edge_index, feed.rows, device=dev, validate="deferred")  # never the cache
+            self._status = topo.status  # the capture's own flags: every replay rewrites them
+            return model.forward_batched_device(feed.x, feed.pos, topo, graph_ptr=feed.graph_ptr)
+        self._capture(run)
+
+    def matches(self, batch) -> bool:
+        return self.feed.matches(batch)
+
+    def __call__(self, batch) -> Tensor:
+        self.feed(batch)
+        self.graph.replay()
+        return self.out
+
+    def check(self) -> None:
+        self.feed.check(self._status)
 
 
 # --------------------------------------------------------------------------- a8 read-out
@@ -525,15 +641,25 @@ class CombinedModel(nn.Module):
         x = x.to(device=dev, dtype=torch.float32)
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
-        y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
-        od = self.graph_net.out_dim
-        gp = None
         if graph_ptr is None:
             if num_graphs is None or x.size(0) != num_graphs * self.num_nodes:
                 raise ValueError(f"expected num_graphs x {self.num_nodes} node rows (got {x.size(0)}); pass graph_ptr "
                                  f"for graphs of other sizes")
         else:
-            gp = graph_ptr.to(device=dev, dtype=torch.int64)
+            graph_ptr = graph_ptr.to(device=dev, dtype=torch.int64)
+        logits = self.forward_batched_device(x, pos, topo, num_graphs=num_graphs, graph_ptr=graph_ptr)
+        return logits if back == dev else logits.to(back)
+
+    def forward_batched_device(self, x, pos, topo: GraphTopology, num_graphs: int | None = None, graph_ptr: Tensor | None = None):
+        """``forward_batched`` behind its topology lookup: float32 ``x`` / ``pos`` on the model's device, a prepared topology and
+        either ``num_graphs`` (graph g owns rows ``[g * num_nodes, (g + 1) * num_nodes)``) or a DEVICE int64 ``graph_ptr``
+        [G + 1].  ``x`` may hold more rows than the graphs own (the padded buffers of a captured ragged-batch step: slack and
+        dummy rows behind ``graph_ptr[-1]``): the read-out takes rows through ``graph_ptr`` only.  No host synchronisation."""
+        dev = x.device
+        y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
+        od = self.graph_net.out_dim
+        gp = graph_ptr
+        if gp is not None:
             num_graphs = gp.numel() - 1
         fc1, fc2, fc3 = self.classifier.fc1, self.classifier.fc2, self.classifier.fc3
         if (READOUT_HIP and num_graphs >= 1 and y.dtype == torch.float32 and fc1.in_features == self.num_nodes * od
@@ -541,9 +667,8 @@ class CombinedModel(nn.Module):
                                                      fc3.out_features)):
             # the gather rule below fused into fc1's operand load, fc1 on MFMA, fc2 / fc3 from LDS (csrc/readout_batched.hip);
             # a shape the library does not take stays on the torch path
-            logits = Fn.readout_batched(y, gp, num_graphs, self.num_nodes, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
-                                        fc3.weight, fc3.bias)
-            return logits if back == dev else logits.to(back)
+            return Fn.readout_batched(y, gp, num_graphs, self.num_nodes, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                                      fc3.weight, fc3.bias)
         if gp is None:
             feats = y.view(num_graphs, -1)
         else:
@@ -552,5 +677,4 @@ class CombinedModel(nn.Module):
             valid = k[None, :] < size[:, None]                                   # [G, num_nodes]
             rows = (start[:, None] + k[None, :]).clamp_(max=max(y.size(0) - 1, 0))
             feats = (y[rows] * valid[..., None]).reshape(gp.numel() - 1, self.num_nodes * od)
-        logits = self.classifier(feats)
-        return logits if back == dev else logits.to(back)
+        return self.classifier(feats)

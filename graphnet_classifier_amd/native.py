@@ -55,6 +55,9 @@ _SIGNATURES = {
     "gnc_readout_batched_backward_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int64, c_void_p, c_int64,
                                                    c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnc_pad_graph_batch_supported": (c_int32, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_int32]),
+    "gnc_pad_graph_batch": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gnc_xty_small_max_rows": (c_int32, []),
     "gnc_xty_small_f32": (c_int32, [c_void_p, c_int32, c_void_p]),
     "gnc_agg_fixup_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int64,
@@ -823,6 +826,82 @@ def readout_batched_backward(grad_logits, y, graph_ptr, num_graphs: int, num_nod
                        4.0 * G * w1.numel()), "gnc_readout_batched_backward_f32")
     dw2, db2, dw3, db3, db1 = small.split([H2 * H1, H2, C * H2, C, H1])
     return dy, dw1, db1, dw2.view(H2, H1), db2, dw3.view(C, H2), db3
+
+
+# --------------------------------------------------------------------------- feed of a captured ragged mini-batch
+PAD_BATCH_MAX_GRAPHS = 64  # GNC_PAD_BATCH_MAX_GRAPHS: the offsets and labels travel in the kernel arguments
+
+
+def ragged_batch_layout(node_capacity: int, edge_capacity: int) -> tuple[int, int]:
+    """``(rows, dummies)`` of the buffers a captured ragged-batch step runs on: ``dummies = max(1, ceil(edge_capacity / 8))`` zero
+    nodes behind the ``node_capacity`` node slots (the unused edge slots are their self-loops, at most 8 each)."""
+    dummies = max(1, (int(edge_capacity) + 7) // 8)
+    return int(node_capacity) + dummies, dummies
+
+
+def pad_graph_batch_supported(num_graphs: int, num_nodes: int, num_edges: int, node_capacity: int, edge_capacity: int,
+                              fx: int = 3, fp: int = 2) -> bool:
+    return bool(load_library().gnc_pad_graph_batch_supported(int(num_graphs), int(num_nodes), int(num_edges), int(node_capacity),
+                                                             int(edge_capacity), int(fx), int(fp)))
+
+
+def _host_i64(values, count: int, what: str):
+    vals = [int(v) for v in (values.tolist() if isinstance(values, torch.Tensor) else values)]
+    if len(vals) != count:
+        raise ValueError(f"pad_graph_batch: {what} must hold {count} entries, got {len(vals)}")
+    return (c_int64 * count)(*vals)
+
+
+def pad_graph_batch(x: torch.Tensor, pos: torch.Tensor, edge_index: torch.Tensor, graph_ptr, edge_ptr, labels, node_capacity: int,
+                    edge_capacity: int, x_buf: torch.Tensor, pos_buf: torch.Tensor, ei_buf: torch.Tensor, graph_ptr_buf: torch.Tensor,
+                    labels_buf: torch.Tensor | None, flag: torch.Tensor) -> None:
+    """ONE launch (gnc_pad_graph_batch) that writes the input buffers of a captured ragged-batch step from a collated batch on the
+    device: ``x`` [N, Fx] / ``pos`` [N, Fp] float32, ``edge_index`` [2, E] int64 with shifted ids; ``graph_ptr`` / ``edge_ptr``
+    [G + 1] and ``labels`` [G] (None: not written) are HOST values and travel in the kernel arguments.  Buffers: ``x_buf`` /
+    ``pos_buf`` [rows, F] with ``rows`` from ``ragged_batch_layout`` (rows behind ``node_capacity`` stay untouched), ``ei_buf``
+    [2, edge_capacity] int64, ``graph_ptr_buf`` int64 [G + 1], ``labels_buf`` int64 [G], ``flag`` int32 [1] (sticky: set when an
+    edge leaves its graph's node range, never cleared here).  More than ``PAD_BATCH_MAX_GRAPHS`` graphs or a batch above the
+    capacities raises ValueError before any launch."""
+    _require_cuda(x, pos, edge_index, x_buf, pos_buf, ei_buf, graph_ptr_buf, labels_buf, flag)
+    if x.dtype != torch.float32 or pos.dtype != torch.float32 or edge_index.dtype != torch.int64:
+        raise TypeError("pad_graph_batch: float32 x / pos and int64 edge_index expected")
+    if edge_index.dim() != 2 or edge_index.size(0) != 2:
+        raise ValueError(f"edge_index must be [2, E], got {tuple(edge_index.shape)}")
+    n, e = int(x.size(0)), int(edge_index.size(1))
+    if pos.size(0) != n:
+        raise ValueError("pad_graph_batch: x and pos disagree on the node count")
+    fx, fp = x[0].numel() if n else x_buf[0].numel(), pos[0].numel() if n else pos_buf[0].numel()
+    G = int(graph_ptr_buf.numel()) - 1
+    M, C = int(node_capacity), int(edge_capacity)
+    if not pad_graph_batch_supported(G, n, e, M, C, fx, fp):
+        raise ValueError(f"pad_graph_batch: {G} graphs / {n} nodes / {e} edges do not fit {PAD_BATCH_MAX_GRAPHS} graphs / "
+                         f"{M} nodes / {C} edges")
+    rows, _ = ragged_batch_layout(M, C)
+    for buf, f, what in ((x_buf, fx, "x_buf"), (pos_buf, fp, "pos_buf")):
+        if buf.dtype != torch.float32 or not buf.is_contiguous() or buf.size(0) < rows or buf[0].numel() != f:
+            raise ValueError(f"pad_graph_batch: {what} must be contiguous float32 [>= {rows}, {f}]")
+    if ei_buf.dtype != torch.int64 or not ei_buf.is_contiguous() or tuple(ei_buf.shape) != (2, C):
+        raise ValueError(f"pad_graph_batch: ei_buf must be contiguous int64 [2, {C}]")
+    if graph_ptr_buf.dtype != torch.int64 or not graph_ptr_buf.is_contiguous() or G < 1:
+        raise ValueError("pad_graph_batch: graph_ptr_buf must be contiguous int64 [G + 1]")
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError("pad_graph_batch: flag must be one int32")
+    if (labels is None) != (labels_buf is None):
+        raise ValueError("pad_graph_batch: labels and labels_buf come together")
+    if labels_buf is not None and (labels_buf.dtype != torch.int64 or not labels_buf.is_contiguous() or labels_buf.numel() != G):
+        raise ValueError("pad_graph_batch: labels_buf must be contiguous int64 [G]")
+    x, pos = x.contiguous(), pos.contiguous()
+    if e and edge_index.stride(1) != 1:
+        edge_index = edge_index.contiguous()
+    gp, ep = _host_i64(graph_ptr, G + 1, "graph_ptr"), _host_i64(edge_ptr, G + 1, "edge_ptr")
+    lab = _host_i64(labels, G, "labels") if labels is not None else None
+    with torch.cuda.device(x_buf.device):
+        _check(_launch("pad_graph_batch", x_buf,
+                       lambda: load_library().gnc_pad_graph_batch(
+                           x.data_ptr(), fx, pos.data_ptr(), fp, edge_index.data_ptr(), max(int(edge_index.stride(0)), e), n, e, G,
+                           gp, ep, lab, M, C, x_buf.data_ptr(), pos_buf.data_ptr(), ei_buf.data_ptr(), graph_ptr_buf.data_ptr(),
+                           labels_buf.data_ptr() if labels_buf is not None else None, flag.data_ptr(), _stream(x_buf)),
+                       4.0 * (x_buf.numel() + pos_buf.numel()) + 8.0 * ei_buf.numel()), "gnc_pad_graph_batch")
 
 
 def dual_projection(x: torch.Tensor, wa: torch.Tensor, wb: torch.Tensor):

@@ -260,6 +260,15 @@ class CapturedTrainStep:
                     return mod.classifier(masked_readout_rows(y, mod.num_nodes, self.valid_nodes).flatten())
                 return mod.classifier(y[:n].flatten())
             fwd = forward if forward is not None else padded_forward
+        self._capture(model, criterion, fwd, loss_scale, capture_error_mode)
+
+    def _capture(self, model: nn.Module, criterion, fwd, loss_scale: float, capture_error_mode: str) -> None:
+        """The capture itself, over the input buffers ``self.x`` / ``self.pos`` / ``self.edge_index`` / ``self.label`` that the
+        constructor prepared: private leaf aliases, warm-up on a side stream, the recording, and the restore of everything the
+        warm-up and the recording stepped (see the class docstring)."""
+        optimizer = self.optimizer
+        fp = optimizer.fp
+        dev = fp.flat.device
         through = _Through(model, fwd)
         # private leaves over the parameters' storage (the flat buffer): see the class docstring
         wanted = dict(zip(fp.names, range(len(fp.names))))
@@ -373,6 +382,62 @@ class CapturedTrainStep:
             raise IndexError(f"edge_index has node ids outside [0, {self.num_nodes})")
 
 
+class CapturedRaggedBatchStep(CapturedTrainStep):
+    """One training step on ANY mini-batch of G graphs with at most ``node_capacity`` nodes and ``edge_capacity`` edges in all
+    (superpixel batches: a new region adjacency and new node counts every batch), captured once and replayed: the
+    ``node_capacity`` form of ``CapturedTrainStep`` extended to G graphs, on the same capture machinery.
+
+    A call is ONE feed launch (``GNN.RaggedBatchFeed``: x, pos, the edge list with its dummy tail, ``graph_ptr`` and the labels
+    go into the captured buffers; the host offsets and labels travel in the kernel arguments) and the replay.  Inside the
+    graph, in order: the topology build over the padded buffers (deferred validation: device flags, no host sync),
+    ``GraphNet.forward_device``, the batched read-out with the DEVICE ``graph_ptr``, mean cross-entropy over the G graphs,
+    backward, the fused Adam, and the add into ``loss_sum``.  Slack rows ``[N, node_capacity)`` belong to no graph and the
+    dummies only talk to dummies, so both contribute exact zeros to the logits and to every gradient.
+
+    G is fixed per capture.  ``matches(batch)``: same G and feature widths, ``N <= node_capacity``, ``E <= edge_capacity``; a
+    call with a batch that does not match raises ValueError.  ``check()`` reads the feed's sticky flag and the last build's
+    status in one sync, clears the flag and raises the reference's IndexError.  BatchNorm layers: NotImplementedError (the dummy
+    rows would enter the batch statistics)."""
+
+    def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, batch: GraphBatch, labels, loss_sum: torch.Tensor, *,
+                 edge_capacity: int, node_capacity: int, loss_scale: float = 1.0, capture_error_mode: str = "global"):
+        from .GNN import CombinedModel, RaggedBatchFeed
+        from .topology import GraphTopology
+        dev = require_gpu_param(next(model.parameters()), "CapturedRaggedBatchStep")
+        if not isinstance(model, CombinedModel):
+            raise TypeError("CapturedRaggedBatchStep: a CombinedModel expected")
+        if any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
+            raise NotImplementedError("CapturedRaggedBatchStep: not with BatchNorm layers (norm_type='BatchNorm1d')")
+        self.optimizer = optimizer
+        self.loss_sum = loss_sum
+        self.collective_outside = _world(optimizer.fp.reducer.group) > 1
+        self.feed = feed = RaggedBatchFeed(batch, edge_capacity, node_capacity, dev, with_labels=True, who="CapturedRaggedBatchStep")
+        self.edge_capacity, self.node_capacity, self.num_graphs = feed.edge_capacity, feed.node_capacity, feed.num_graphs
+        self.x, self.pos, self.edge_index, self.label = feed.x, feed.pos, feed.edge_index, feed.labels
+        self._status = None
+        feed(batch, labels)
+
+        def forward(mod, xx, pp, ee):
+            topo = GraphTopology(ee, feed.rows, device=dev, validate="deferred")  # never the cache: built in every step
+            self._status = topo.status  # the capture's own flags: every replay rewrites them
+            return mod.forward_batched_device(xx, pp, topo, graph_ptr=feed.graph_ptr)
+        self._capture(model, criterion, forward, loss_scale, capture_error_mode)
+
+    @property
+    def num_nodes(self) -> int:
+        return self.feed.num_nodes
+
+    def matches(self, batch) -> bool:
+        return self.feed.matches(batch)
+
+    def __call__(self, batch, labels) -> None:
+        self.feed(batch, labels)
+        self.replay()
+
+    def check(self) -> None:
+        self.feed.check(self._status)
+
+
 # --------------------------------------------------------------------------- the run's side effects
 class RunJournal:
     """Everything the reference's train() writes or prints besides checkpoints: the timestamped
@@ -449,6 +514,59 @@ class CheckpointShelf:
         return self._write("final_model.pth")
 
 
+class _RaggedBatchCaptures:
+    """When a ragged mini-batch gets a capture, shared by the training loop and ``evaluate`` / ``predict``: ``get(batch, previous)``
+    returns the capture object that serves ``batch``, or None for a batch that runs eagerly.
+
+    A capture is made for a batch with the graph count and feature widths of the batch before it but ANOTHER topology
+    (superpixel graphs), on a ``CombinedModel`` without BatchNorm layers and with at most ``native.PAD_BATCH_MAX_GRAPHS`` graphs.
+    Capacities come from ``padded_capacity`` (edges in steps of 256, nodes in steps of 32) and only grow.  A batch that outgrows
+    the capture is captured again - the old object's ``check()`` runs first, its flags would be lost with it - at most
+    ``limit`` captures in all; after that the capture stays for every batch that fits and an oversize batch runs eagerly on
+    its own.  A batch with another graph count (a short last batch) runs eagerly."""
+
+    def __init__(self, model, make, limit: int):
+        from .GNN import CombinedModel
+        self.make, self.limit = make, limit  # make(batch, *args, edge_capacity=, node_capacity=) -> the capture object
+        self.allowed = (isinstance(model, CombinedModel)
+                        and not any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()))
+        self.current = None
+        self.captures = 0
+        self.edge_capacity = self.node_capacity = 0
+
+    def get(self, batch, previous, *args):
+        """``previous``: ``(x, pos, edge_index, graph_ptr)`` of the last batch that ran eagerly, or None; ``args`` go to ``make``
+        behind the batch (the labels of a training step)."""
+        cur = self.current
+        if cur is not None and cur.matches(batch):
+            return cur
+        widths = (tuple(batch.x.shape[1:]), tuple(batch.pos.shape[1:]))
+        if cur is not None:  # outgrown: same graph count and widths, above a capacity
+            eligible = batch.num_graphs == cur.num_graphs and widths == cur.feed.feature_shapes
+            need_nodes, need_edges = batch.num_nodes, batch.num_edges
+        else:
+            eligible = (previous is not None and previous[3].numel() == batch.graph_ptr.numel()
+                        and (tuple(previous[0].shape[1:]), tuple(previous[1].shape[1:])) == widths
+                        and not (previous[0].shape == batch.x.shape and torch.equal(previous[3], batch.graph_ptr)
+                                 and _same_topology(previous[2], batch.edge_index)))
+            if eligible:
+                need_nodes = max(int(previous[0].size(0)), batch.num_nodes)
+                need_edges = max(int(previous[2].size(1)), batch.num_edges)
+        if not (self.allowed and eligible and batch.num_graphs <= native.PAD_BATCH_MAX_GRAPHS and self.captures < self.limit):
+            return None
+        if cur is not None:
+            cur.check()
+        self.edge_capacity = padded_capacity(need_edges, self.edge_capacity)
+        self.node_capacity = padded_capacity(need_nodes, self.node_capacity, 32)
+        self.current = self.make(batch, *args, edge_capacity=self.edge_capacity, node_capacity=self.node_capacity)
+        self.captures += 1
+        return self.current
+
+    def check(self) -> None:
+        if self.current is not None:
+            self.current.check()
+
+
 class _SampleStepper:
     """Runs one optimizer step per sample: eagerly, or - once two consecutive samples have shared a topology - as a
     replay of the captured step."""
@@ -464,6 +582,11 @@ class _SampleStepper:
         self.captured_batch: CapturedTrainStep | None = None  # mini-batches (GraphBatch samples)
         self._previous_batch = None
         self.batched = False
+        self.capture_ragged_batches = capture  # ragged mini-batches (superpixel graphs): CapturedRaggedBatchStep
+        self.ragged = _RaggedBatchCaptures(
+            model, lambda batch, labels, **capacities: CapturedRaggedBatchStep(model, optimizer, criterion, batch, labels, loss_sum,
+                                                                               **capacities),
+            self.MAX_PADDED_CAPTURES)  # a counter of their own
 
     MAX_PADDED_CAPTURES = 4  # a dataset whose edge counts keep outgrowing the capacity goes back to eager steps
 
@@ -505,6 +628,7 @@ class _SampleStepper:
     def check(self) -> None:
         if self.padded is not None:
             self.padded.check()
+        self.ragged.check()
 
     def _batch_forward(self, batch):
         """``forward(model, x, pos, edge_index) -> logits [G, C]`` of a mini-batch: the ``num_graphs`` form for graphs of exactly
@@ -519,7 +643,8 @@ class _SampleStepper:
     def _step_batch(self, batch, labels) -> None:
         """One optimizer step on a mini-batch (``synthetic.GraphBatch``, labels [B]): mean cross-entropy over the batch.  A
         replay of the captured step when this batch has the topology of the one before it (pixel / patch graphs of one size:
-        every full batch), an eager step otherwise (a short last batch; superpixel graphs, whose topology changes)."""
+        every full batch); a replay of the captured ragged-batch step when it has the graph count of the one before it but
+        another topology (superpixel graphs); an eager step otherwise (a short last batch, the first batch of a kind)."""
         dev = self.device
         self.batched = True
         sample = (batch.x, batch.pos, batch.edge_index)
@@ -534,6 +659,11 @@ class _SampleStepper:
                     and self.captured_batch.matches(sample)):
                 self.captured_batch(sample, labels)
                 return
+            if self.capture_ragged_batches:
+                step = self.ragged.get(batch, self._previous_batch, labels)
+                if step is not None:
+                    step(batch, labels)
+                    return
             self._previous_batch = sample + (batch.graph_ptr,)
         x, pos = batch.x.to(dev, non_blocking=True), batch.pos.to(dev, non_blocking=True)
         logits = self._batch_forward(batch)(self.model, x, pos, batch.edge_index)
@@ -564,7 +694,8 @@ class _SampleStepper:
         self.loss_sum += loss.detach().double()                                                # :44, without the per-sample sync
 
 
-def train(model, dataset, epochs, patience=5, output_path='weights', start_weights=None, *, capture: bool = True, lr: float = 1e-3):
+def train(model, dataset, epochs, patience=5, output_path='weights', start_weights=None, *, capture: bool = True, lr: float = 1e-3,
+          capture_ragged_batches: bool = False):
     """utils/train_model.py:8-81 (same positional arguments, files and log lines).  Returns a dict with the per-epoch
     average losses (the reference returns None; nothing in it reads the return value).
 
@@ -573,8 +704,14 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     model without ``ragged_readout``, otherwise ``graph_ptr``); the loss is ``CrossEntropyLoss()``'s mean over the batch
     (:38 on a batched input, as the reference's image-MLP path with ``batch_size=8``, main.py:13-29) and the epoch average is
     taken over steps (:47).  When consecutive full batches share one topology (pixel / patch graphs of one size) the step is
-    captured once and replayed; a short last batch runs eagerly, and so does every batch whose topology changes (superpixel
-    graphs): captured steps over ragged batches are not built.  ``"batched"`` in the returned dict says which form ran."""
+    captured once and replayed (``"captured"`` in the returned dict).  When consecutive batches share only their graph count
+    (superpixel graphs: another region adjacency and other node counts in every batch) the step can be captured over padded buffers
+    (``CapturedRaggedBatchStep``; ``"captured_ragged_batch"``) and every such batch is ONE feed launch and the replay: for a
+    ``CombinedModel`` without BatchNorm layers and at most 64 graphs per batch, at capacities from ``padded_capacity`` (edges in
+    steps of 256, nodes in steps of 32) that only grow, with at most ``MAX_PADDED_CAPTURES`` re-captures, after which a batch
+    above the capacities runs eagerly on its own.  This form is used with ``capture_ragged_batches=True`` only: the eager
+    ragged-batch step has not been timed against it on an MI355X yet (``tools/latency_ragged_batch.py`` does that), and the
+    default follows the measurement.  A short last batch always runs eagerly.  ``"batched"`` in the returned dict says which form ran."""
     if start_weights:
         model.load_state_dict(torch.load(start_weights, map_location="cpu"))           # :14-15
     dev = require_gpu_param(next(model.parameters()), "train")
@@ -587,6 +724,7 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     # this loop steps one rank's model on its own samples: with a multi-rank process group up, a captured step would
     # record (or, under gloo, host-stage) a collective per sample that nothing here asked for
     stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1)
+    stepper.capture_ragged_batches = stepper.capture and capture_ragged_batches
     history = []
     # Belt and braces: the loop runs on a side stream, so that the eager steps in front of a capture never touch the
     # legacy default stream.  The capture itself no longer depends on it (CapturedTrainStep differentiates private
@@ -620,10 +758,36 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
             "captured": stepper.captured is not None or stepper.captured_batch is not None, "batched": stepper.batched,
             "captured_any_topology": stepper.padded is not None,
             "captured_ragged": stepper.padded is not None and stepper.padded.node_capacity is not None,
+            "captured_ragged_batch": stepper.ragged.current is not None,
             "optimizer": optimizer}
 
 
 # --------------------------------------------------------------------------- evaluation
+class _BatchScorer:
+    """Logits of loader items for ``evaluate`` / ``predict``: ragged mini-batches replay a ``CapturedRaggedBatchForward`` under
+    the rule of the training loop (``_RaggedBatchCaptures``); same-topology batches and single graphs go through
+    ``_logits_of`` as they always did."""
+
+    def __init__(self, model, dev, capture: bool):
+        from .GNN import CapturedRaggedBatchForward
+        self.model, self.dev, self.capture = model, dev, capture
+        self.ragged = _RaggedBatchCaptures(
+            model, lambda batch, **capacities: CapturedRaggedBatchForward(model, batch, **capacities),
+            _SampleStepper.MAX_PADDED_CAPTURES)
+        self._previous = None
+
+    def __call__(self, sample):
+        if self.capture and isinstance(sample, GraphBatch):
+            forward = self.ragged.get(sample, self._previous)
+            if forward is not None:
+                return forward(sample).clone()  # the capture's output buffer is rewritten by the next replay
+            self._previous = (sample.x, sample.pos, sample.edge_index, sample.graph_ptr)
+        return _logits_of(self.model, sample, self.dev)
+
+    def check(self) -> None:
+        self.ragged.check()
+
+
 def _logits_of(model, sample, dev):
     """Logits [B, C] of one loader item: a ``GraphBatch`` through ``forward_batched``, an ``(x, pos, edge_index)`` graph through
     ``model(sample)`` (one row)."""
@@ -641,29 +805,36 @@ def _logits_of(model, sample, dev):
     return logits.unsqueeze(0) if logits.dim() == 1 else logits
 
 
-def predict(model, loader):
+def predict(model, loader, *, capture: bool = True):
     """``(logits [n, C], probabilities [n, C])`` of every sample of ``loader`` in loader order, on the model's device - the pair
     ``utils/inference.py:68-71`` returns per image (softmax over the classes).  ``loader`` yields ``(sample, label)`` with a
-    single graph or a ``GraphBatch`` (``GraphImageFolder.loader(shuffle=False, batch_size=...)``); labels are not read."""
+    single graph or a ``GraphBatch`` (``GraphImageFolder.loader(shuffle=False, batch_size=...)``); labels are not read.
+    ``capture``: ragged mini-batches (superpixel graphs) replay a captured forward (``_BatchScorer``); an edge list that leaves
+    its graph raises IndexError at the end."""
     dev = require_gpu_param(next(model.parameters()), "predict")
     with torch.no_grad():
-        rows = [_logits_of(model, sample, dev) for sample, _ in loader]
+        score = _BatchScorer(model, dev, capture)
+        rows = [score(sample) for sample, _ in loader]
         if not rows:
             raise ValueError("predict: the loader yielded nothing")
         logits = torch.cat(rows)
+        score.check()
         return logits, torch.softmax(logits, dim=-1)
 
 
-def evaluate(model, loader):
+def evaluate(model, loader, *, capture: bool = True):
     """Scores ``model`` on every sample of ``loader`` (either loader form) under ``no_grad``: ``{"loss": mean cross-entropy over
     the samples, "accuracy", "confusion": int64 [C, C] with rows = true class and columns = predicted class, "count"}``.
-    Loss and confusion matrix are accumulated on the device (integer scatter-adds, float64 loss) and read ONCE at the end."""
+    Loss and confusion matrix are accumulated on the device (integer scatter-adds, float64 loss) and read ONCE at the end.
+    ``capture``: ragged mini-batches (superpixel graphs) replay a captured forward (``_BatchScorer``); an edge list that leaves
+    its graph raises IndexError at the end."""
     dev = require_gpu_param(next(model.parameters()), "evaluate")
     loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
     confusion, count = None, 0
     with torch.no_grad():
+        score = _BatchScorer(model, dev, capture)
         for sample, label in loader:
-            logits = _logits_of(model, sample, dev)
+            logits = score(sample)
             labels = torch.as_tensor(label).to(dev, non_blocking=True).reshape(-1)
             if confusion is None:
                 classes = logits.size(1)
@@ -674,6 +845,7 @@ def evaluate(model, loader):
         if confusion is None:
             raise ValueError("evaluate: the loader yielded nothing")
         stats = torch.cat([loss_sum, confusion.double()]).cpu()  # the one host read
+        score.check()
     confusion = stats[1:].round().to(torch.int64).view(classes, classes)
     return {"loss": float(stats[0]) / count, "accuracy": float(confusion.diagonal().sum()) / count, "confusion": confusion,
             "count": count}

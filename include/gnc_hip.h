@@ -558,6 +558,34 @@ int gnc_readout_batched_backward_f32(const float* grad_logits, const float* y, c
                                      const float* h2, float* dw1, float* small_grads, float* dy, float* workspace,
                                      int64_t workspace_floats, void* stream);
 
+/* ---- feed of a captured ragged mini-batch step ---------------------------------------------------
+ * gnc_pad_graph_batch  ONE launch that writes every input buffer of a hipGraph captured over fixed capacities from a collated
+ *                      block-diagonal batch: x [num_nodes, fx], pos [num_nodes, fp] (contiguous), edge_index [2, num_edges] int64
+ *                      with ids already shifted (row stride ld_edge_index), and the HOST arrays graph_ptr / edge_ptr
+ *                      [num_graphs + 1] and labels [num_graphs] (NULL with labels_buf NULL: none), which travel by value in the
+ *                      kernel arguments - no host-to-device copy.  With M = node_capacity, C = edge_capacity and
+ *                      D = max(1, ceil(C / 8)) dummy nodes:
+ *                        x_buf [M + D, fx]: rows [0, N) = x, rows [N, M) = 0, rows [M, M + D) NOT written (the caller keeps them
+ *                        zero); pos_buf likewise; ei_buf [2, C]: columns [0, E) = edge_index, column k >= E = (M + k % D,
+ *                        M + k % D); graph_ptr_buf int64 [G + 1]; labels_buf int64 [G].
+ *                      `flag` (device int32) is STICKY: 1 is stored when an end of an edge of graph g (edge_ptr says which) lies
+ *                      outside [graph_ptr[g], graph_ptr[g + 1]); the kernel never clears it.  Ids are copied as given and not
+ *                      dereferenced.  Sources need element alignment only (4 B floats, 8 B ids); 16-byte accesses are used
+ *                      where the pointers allow.  Stream-ordered, no host synchronisation, a kernel node under stream capture.
+ *                      Served: 1 <= num_graphs <= GNC_PAD_BATCH_MAX_GRAPHS (the 4 KB kernel-argument segment bounds it),
+ *                      num_nodes <= M, num_edges <= C, M + D < 2^31; the query answers on the host without a device, the
+ *                      launcher returns GNC_ERR_UNSUPPORTED outside the set before anything is launched.  Added without an ABI
+ *                      bump: a library without these symbols fails the symbol lookup of the binding.
+ */
+#define GNC_PAD_BATCH_MAX_GRAPHS 64
+int32_t gnc_pad_graph_batch_supported(int64_t num_graphs, int64_t num_nodes, int64_t num_edges, int64_t node_capacity,
+                                      int64_t edge_capacity, int32_t fx, int32_t fp);
+int gnc_pad_graph_batch(const float* x, int32_t fx, const float* pos, int32_t fp, const int64_t* edge_index,
+                        int64_t ld_edge_index, int64_t num_nodes, int64_t num_edges, int64_t num_graphs,
+                        const int64_t* graph_ptr, const int64_t* edge_ptr, const int64_t* labels, int64_t node_capacity,
+                        int64_t edge_capacity, float* x_buf, float* pos_buf, int64_t* ei_buf, int64_t* graph_ptr_buf,
+                        int64_t* labels_buf, int32_t* flag, void* stream);
+
 /* ---- graph construction on the device ---------------------------
  * Inputs: an already resized uint8 RGB image [H, W, C] in HBM.  Outputs: the tensors
  * utils/dataloader.py:49-51 builds (x, pos float32; edge_index int64 [2, E] row-major), in the

@@ -1,0 +1,240 @@
+"""GPU: captured steps over RAGGED mini-batches - ``GNN.CapturedRaggedBatchForward``, ``train.CapturedRaggedBatchStep`` and their
+automatic use in ``train()`` / ``evaluate()`` / ``predict()`` - against the eager ``forward_batched(graph_ptr=...)`` path.  Model:
+``graphnet_kwargs(32, 1)``, ``num_nodes = 12``, ``ragged_readout``; batches of 3 graphs with 9, 12 or 16 nodes each."""
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+from tests._util import max_abs
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SHAPES = ((3, 3), (3, 4), (4, 4))
+M, C = 64, 256
+# larger -> smaller -> larger: 48 / 37 / 27 / 30 / 44 / 48 nodes
+SEEDS = (208, 12, 207, 103, 41, 217)
+
+
+def _batch(seed, G=3):
+    from graphnet_classifier_amd import synthetic
+    return synthetic.superpixel_like_graphs(G, seed, shapes=SHAPES)
+
+
+def _oversize():
+    """3 graphs, 75 nodes: the captures' G, above their node capacity."""
+    from graphnet_classifier_amd import synthetic
+    return synthetic.superpixel_like_graphs(3, 5, shapes=((5, 5),))
+
+
+def _model(num_nodes=12, norm_type=None):
+    from graphnet_classifier_amd import synthetic
+    from graphnet_classifier_amd.GNN import CombinedModel, GraphNet
+    torch.manual_seed(99)
+    kw = synthetic.graphnet_kwargs(32, 1)
+    if norm_type is not None:
+        kw["norm_type"] = norm_type
+    m = CombinedModel(GraphNet(**kw), num_nodes=num_nodes, classes=2)
+    m.ragged_readout = True
+    return m
+
+
+def _eager_logits(m, b):
+    with torch.no_grad():
+        return m.forward_batched(b.x.to(DEV), b.pos.to(DEV), b.edge_index.to(DEV), graph_ptr=b.graph_ptr).clone()
+
+
+# --------------------------------------------------------------------------- CapturedRaggedBatchForward
+@pytest.fixture(scope="module")
+def forward_setup():
+    from graphnet_classifier_amd.GNN import CapturedRaggedBatchForward
+    m = _model()
+    batches = [_batch(s) for s in SEEDS]
+    sizes = [b.num_nodes for b in batches]
+    assert sizes[0] > sizes[1] > sizes[2] < sizes[3] < sizes[4] < sizes[5]
+    eager = [_eager_logits(m, b) for b in batches]  # computed once, shared, never modified
+    cap = CapturedRaggedBatchForward(m, batches[0], edge_capacity=C, node_capacity=M)
+    return m, batches, eager, cap
+
+
+def test_captured_forward_serves_six_different_batches(forward_setup):
+    m, batches, eager, cap = forward_setup
+    for b, ref in zip(batches, eager):
+        assert cap.matches(b)
+        out = cap(b.to(DEV))
+        assert out.shape == ref.shape == (3, 2)
+        err = max_abs(out, ref)
+        print(f"{b.num_nodes} nodes / {b.num_edges} edges: max |captured - eager| = {err:.3e}")
+        assert err <= 1e-5
+    cap.check()
+
+
+def test_captured_forward_takes_host_batches_too(forward_setup):
+    m, batches, eager, cap = forward_setup
+    assert max_abs(cap(batches[3]), eager[3]) <= 1e-5
+
+
+def test_replaying_a_then_b_then_a_gives_a_bit_for_bit(forward_setup):
+    m, batches, eager, cap = forward_setup
+    a, b = batches[0].to(DEV), batches[2].to(DEV)
+    first = cap(a).clone()
+    other = cap(b).clone()
+    again = cap(a).clone()
+    assert torch.equal(first, again) and not torch.equal(first, other)
+    cap.check()
+
+
+def test_a_bad_edge_list_is_reported_after_a_clean_batch_and_the_capture_lives_on(forward_setup):
+    m, batches, eager, cap = forward_setup
+    cap.check()  # clean so far
+    bad = batches[1].to(DEV)
+    bad.edge_index = bad.edge_index.clone()
+    bad.edge_index[1, int(bad.edge_ptr[1]) + 2] = int(bad.graph_ptr[2])  # an edge of graph 1 into graph 2: in range for the build
+    cap(bad)
+    cap(batches[2].to(DEV))  # a clean batch afterwards: the flag is sticky
+    with pytest.raises(IndexError):
+        cap.check()
+    cap.check()  # cleared by the check that raised
+    assert max_abs(cap(batches[4].to(DEV)), eager[4]) <= 1e-5
+    cap.check()
+
+
+def test_forward_rejects_what_does_not_fit(forward_setup):
+    from graphnet_classifier_amd.GNN import CapturedRaggedBatchForward
+    m, batches, eager, cap = forward_setup
+    assert not cap.matches(_batch(5, G=2)) and not cap.matches(_oversize())  # another G; above node_capacity
+    with pytest.raises(ValueError):
+        cap(_batch(5, G=2).to(DEV))
+    with pytest.raises(ValueError):
+        cap(_oversize().to(DEV))
+    with pytest.raises(ValueError):
+        CapturedRaggedBatchForward(m, batches[0], edge_capacity=C, node_capacity=32)  # 48 nodes
+
+
+# --------------------------------------------------------------------------- CapturedRaggedBatchStep
+def test_captured_step_on_a_second_smaller_batch():
+    from graphnet_classifier_amd.train import CapturedRaggedBatchStep, FlatParameters, FusedAdam
+    crit = torch.nn.CrossEntropyLoss()
+    first, second = _batch(208), _batch(207)  # 48 nodes (16, 16, 16), then 27 nodes (9, 9, 9)
+    labels1, labels2 = torch.tensor([0, 1, 1]), torch.tensor([1, 0, 1])
+    # the eager step's loss and gradients on the second batch
+    e = _model()
+    eopt = FusedAdam(FlatParameters(e))
+    loss = crit(e.forward_batched(second.x.to(DEV), second.pos.to(DEV), second.edge_index.to(DEV), graph_ptr=second.graph_ptr),
+                labels2.to(DEV))
+    eopt.zero_grad()
+    loss.backward()
+    eopt.fp.reducer()
+    want = {n: v.clone() for n, v in zip(eopt.fp.names, eopt.fp.reducer.views)}
+
+    m = _model()
+    opt = FusedAdam(FlatParameters(m))
+    loss_sum = torch.zeros((), dtype=torch.float64, device=DEV)
+    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    step = CapturedRaggedBatchStep(m, opt, crit, first.to(DEV), labels1, loss_sum, edge_capacity=C, node_capacity=M)
+    torch.cuda.synchronize()
+    assert float(loss_sum.item()) == 0.0  # constructing it does not train
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, before[k]), k
+    assert int(opt.step_count.item()) == 0
+    assert step.matches(first) and step.matches(second)
+    assert not step.matches(_oversize()) and not step.matches(_batch(5, G=2))  # above node_capacity; another G
+
+    step(second.to(DEV), labels2)
+    step.check()
+    torch.cuda.synchronize()
+    got = dict(zip(opt.fp.names, opt.fp.reducer.views))
+    err = abs(float(loss_sum.item()) - float(loss.item()))
+    print(f"loss: captured {float(loss_sum.item()):.8f} eager {float(loss.item()):.8f} diff {err:.3e}")
+    assert err <= 1e-5
+    assert set(got) == set(want)
+    for k, r in want.items():
+        tol = 2e-5 + 1e-4 * float(r.abs().max())
+        gerr = max_abs(got[k], r)
+        print(f"grad {k}: err {gerr:.3e} tol {tol:.3e}")
+        assert got[k].shape == r.shape and gerr <= tol, f"{k} err {gerr:.3e} > {tol:.3e}"
+    od = m.graph_net.out_dim
+    dw1 = got["classifier.fc1.weight"]
+    assert not dw1[:, 9 * od:].any() and bool(dw1[:, :9 * od].any())  # every graph has 9 nodes: columns behind them are exact zeros
+    assert any(not torch.equal(before[k], v) for k, v in m.state_dict().items()) and int(opt.step_count.item()) == 1
+
+    with pytest.raises(ValueError):
+        step(_oversize().to(DEV), torch.zeros(3, dtype=torch.long))  # oversize
+    with pytest.raises(ValueError):
+        step(_batch(5, G=2).to(DEV), torch.zeros(2, dtype=torch.long))  # another G
+    assert int(opt.step_count.item()) == 1  # neither stepped
+
+
+def test_batchnorm_model_is_refused():
+    from graphnet_classifier_amd.train import CapturedRaggedBatchStep, FlatParameters, FusedAdam
+    m = _model(norm_type="BatchNorm1d")
+    opt = FusedAdam(FlatParameters(m))
+    with pytest.raises(NotImplementedError):
+        CapturedRaggedBatchStep(m, opt, torch.nn.CrossEntropyLoss(), _batch(208).to(DEV), torch.tensor([0, 1, 1]),
+                                torch.zeros((), dtype=torch.float64, device=DEV), edge_capacity=C, node_capacity=M)
+
+
+# --------------------------------------------------------------------------- end to end
+def _folder(root, side=48, count=10):
+    """The smooth-image folder of tests/test_gpu_minibatch_training.py: low-frequency colour fields, which keep about
+    ``n_segments`` SLIC segments, a few more or less per image; 2 classes."""
+    rng = np.random.default_rng(2024)
+    for k in range(count):
+        yy, xx = np.mgrid[0:side, 0:side]
+        f = rng.uniform(0.5, 2.5, size=(3, 2)) * (2 * np.pi / side)
+        ph = rng.uniform(0, 2 * np.pi, size=(3, 2))
+        img = np.stack([127 + 60 * np.sin(f[c, 0] * yy + ph[c, 0]) + 60 * np.sin(f[c, 1] * xx + ph[c, 1]) for c in range(3)],
+                       axis=-1).astype(np.uint8)
+        c = k % 2
+        mask = ((yy - side * (0.3 + 0.04 * k)) ** 2 + (xx - side * 0.5) ** 2 < (side * (0.2 + 0.02 * k)) ** 2) if c == 0 \
+            else ((xx // (2 + k // 2)) % 2 == 0)
+        img[mask] = (img[mask] // 4 + np.array([190, 40 + 15 * k, 60], dtype=np.uint8)).astype(np.uint8)
+        d = root / f"class{c}"
+        d.mkdir(parents=True, exist_ok=True)
+        Image.fromarray(img).save(d / f"img{k:02d}.png")
+    return str(root)
+
+
+@pytest.fixture(scope="module")
+def superpixel_folder(tmp_path_factory):
+    from graphnet_classifier_amd.dataset import GraphImageFolder
+    ds = GraphImageFolder(_folder(tmp_path_factory.mktemp("data")), resize_value=48, method="superpixel", n_segments=30)
+    counts = sorted(int(g[0].size(0)) for g, _ in ds.loader(shuffle=False))
+    assert len(set(counts)) > 1
+    return ds, counts[len(counts) // 2]  # some graphs smaller, some larger than the read-out's num_nodes
+
+
+def test_superpixel_minibatch_training_captured_equals_eager(superpixel_folder, tmp_path):
+    from graphnet_classifier_amd.train import train
+    ds, num_nodes = superpixel_folder
+    out = {}
+    for capture in (False, True):
+        m = _model(num_nodes)
+        torch.manual_seed(3)  # the same shuffled batches in both runs
+        r = train(m, ds.loader(shuffle=True, batch_size=3), 2, patience=5, output_path=str(tmp_path / str(capture)), capture=capture,
+                  capture_ragged_batches=True)  # not the default until the step has been timed against the eager one
+        assert r["batched"] is True and r["captured"] is False and r["captured_ragged_batch"] is capture
+        out[capture] = ({k: v.detach().cpu().clone() for k, v in m.state_dict().items()}, r["avg_loss"])
+    (sd_c, loss_c), (sd_e, loss_e) = out[True], out[False]
+    print("avg_loss captured", loss_c, "eager", loss_e)
+    assert len(loss_c) == len(loss_e) == 2
+    for a, b in zip(loss_c, loss_e):
+        assert abs(a - b) <= 1e-5 * max(1.0, abs(b))
+    close = np.mean([float(((sd_c[k].double() - sd_e[k].double()).abs() < 2e-5).float().mean()) for k in sd_e])
+    worst = max(max_abs(sd_c[k], sd_e[k]) for k in sd_e)
+    print(f"final parameters: worst {worst:.3e}, fraction within 2e-5: {close:.4f}")
+    assert close >= 0.97
+
+
+def test_evaluate_and_predict_captured_equal_eager(superpixel_folder):
+    from graphnet_classifier_amd.train import evaluate, predict
+    ds, num_nodes = superpixel_folder
+    m = _model(num_nodes)
+    loader = ds.loader(shuffle=False, batch_size=3)
+    ev_c, ev_e = evaluate(m, loader, capture=True), evaluate(m, loader, capture=False)
+    assert ev_c["count"] == ev_e["count"] == 10 and torch.equal(ev_c["confusion"], ev_e["confusion"])
+    assert abs(ev_c["loss"] - ev_e["loss"]) <= 1e-5
+    (logits_c, prob_c), (logits_e, prob_e) = predict(m, loader, capture=True), predict(m, loader, capture=False)
+    assert logits_c.shape == logits_e.shape == (10, 2)
+    print(f"predict: max |captured - eager| = {max_abs(logits_c, logits_e):.3e}")
+    assert max_abs(logits_c, logits_e) <= 1e-5 and max_abs(prob_c, prob_e) <= 1e-5
