@@ -32,7 +32,7 @@ __device__ __forceinline__ float activate(float x, int act, float p) {
     case GNC_ACT_SILU: return x / (1.f + expf(-x));
     case GNC_ACT_GELU: return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f));
     case GNC_ACT_LEAKY_RELU: return x < 0.f ? x * p : x;
-    case GNC_ACT_ELU: return x > 0.f ? x : p * (expf(x) - 1.f);
+    case GNC_ACT_ELU: return x > 0.f ? x : p * expm1f(x);  // expf(x) - 1 loses every digit near 0 (-1e-8 -> 0)
     default: return x;
   }
 }

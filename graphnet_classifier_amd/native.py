@@ -1251,24 +1251,35 @@ def colsum_pair(g: torch.Tensor, y: torch.Tensor):
 
 
 # --------------------------------------------------------------------------- activations other than ReLU: backward pieces
-def activation(z: torch.Tensor, name: str, param: float = 0.0) -> torch.Tensor:
-    """act(z) elementwise (gnc_activation_f32)."""
+def _rows_out(out: torch.Tensor | None, like: torch.Tensor, what: str) -> torch.Tensor:
+    """The [rows, width] fp32 result tensor of a row-wise kernel: a fresh one, or the caller's (any row stride)."""
+    if out is None:
+        return torch.empty(like.size(0), like.size(1), dtype=torch.float32, device=like.device)
+    if (out.shape != like.shape or out.dtype != torch.float32 or out.device != like.device or (out.size(1) > 1 and out.stride(1) != 1)
+            or (out.size(0) > 1 and out.stride(0) < out.size(1))):
+        raise ValueError(f"{what}: out must be a float32 [rows, width] tensor with unit column stride on the input's device")
+    return out
+
+
+def activation(z: torch.Tensor, name: str, param: float = 0.0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """act(z) elementwise (gnc_activation_f32); ``out`` may be a column slice of a wider tensor."""
     lib = load_library()
     _require_cuda(z)
     z = _rowmajor(z)
-    out = torch.empty(z.size(0), z.size(1), dtype=torch.float32, device=z.device)
+    out = _rows_out(out, z, "activation")
     with torch.cuda.device(z.device):
         _check(lib.gnc_activation_f32(z.data_ptr(), _ld(z), z.size(0), z.size(1), ACTIVATIONS[name], param, out.data_ptr(), _ld(out),
                                       _stream(z)), "gnc_activation_f32")
     return out
 
 
-def activation_backward(z: torch.Tensor, grad_act: torch.Tensor, name: str, param: float = 0.0) -> torch.Tensor:
-    """grad_act * act'(z) (gnc_activation_backward_f32)."""
+def activation_backward(z: torch.Tensor, grad_act: torch.Tensor, name: str, param: float = 0.0,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """grad_act * act'(z) (gnc_activation_backward_f32); ``out`` may be a column slice of a wider tensor."""
     lib = load_library()
     _require_cuda(z, grad_act)
     z, grad_act = _rowmajor(z), _rowmajor(grad_act)
-    out = torch.empty(z.size(0), z.size(1), dtype=torch.float32, device=z.device)
+    out = _rows_out(out, z, "activation_backward")
     with torch.cuda.device(z.device):
         _check(lib.gnc_activation_backward_f32(z.data_ptr(), _ld(z), grad_act.data_ptr(), _ld(grad_act), z.size(0), z.size(1),
                                                ACTIVATIONS[name], param, out.data_ptr(), _ld(out), _stream(z)),
@@ -1276,13 +1287,14 @@ def activation_backward(z: torch.Tensor, grad_act: torch.Tensor, name: str, para
     return out
 
 
-def layer_norm_backward(y: torch.Tensor, gamma: torch.Tensor, grad_out: torch.Tensor, eps: float):
-    """(grad_y, y_hat) of out = LayerNorm(y) * gamma + beta (gnc_layer_norm_backward_f32)."""
+def layer_norm_backward(y: torch.Tensor, gamma: torch.Tensor, grad_out: torch.Tensor, eps: float, out=None):
+    """(grad_y, y_hat) of out = LayerNorm(y) * gamma + beta (gnc_layer_norm_backward_f32); ``out`` = (grad_y, y_hat) to write
+    into, each possibly a column slice of a wider tensor."""
     lib = load_library()
     _require_cuda(y, gamma, grad_out)
     y, grad_out = _rowmajor(y), _rowmajor(grad_out)
-    gy = torch.empty(y.size(0), y.size(1), dtype=torch.float32, device=y.device)
-    yhat = torch.empty_like(gy)
+    gy = _rows_out(out[0] if out is not None else None, y, "layer_norm_backward")
+    yhat = _rows_out(out[1] if out is not None else None, y, "layer_norm_backward")
     with torch.cuda.device(y.device):
         _check(lib.gnc_layer_norm_backward_f32(y.data_ptr(), _ld(y), gamma.contiguous().data_ptr(), grad_out.data_ptr(), _ld(grad_out),
                                                y.size(0), y.size(1), eps, gy.data_ptr(), _ld(gy), yhat.data_ptr(), _ld(yhat),

@@ -7,8 +7,13 @@ layers, LayerNorm or none, the residual, optional ``None`` biases, operands that
 ``build_backward(name, rows)`` adds ``grad_out`` and float64 autograd.  Row counts are not part of a case: the tests derive
 them from the device (``derived_rows``).  Results are read-only and shared between the tests that need them.
 
-ReLU kinks: a hidden pre-activation within ``KINK`` of zero in float64 may come out on the other side in fp32 (the rounding
-of such a sum is about 1e-6), which moves a gradient by a whole weight column.  ``build_backward`` decides those rows from the
+The family ``generic`` holds the descriptions only the generic kernel (mlp_fused_kernel<HT, OT>, csrc/mlp_fused.hip) serves:
+every multi-layer launch with an activation other than ReLU, and the ReLU descriptions all specialised kernels decline
+(tests/test_gpu_mlp_generic.py).  ``activate`` applies the named activation through the same torch.nn.functional call in
+float64 and float32.
+
+ReLU kinks (LeakyReLU has the same one): a hidden pre-activation within ``KINK`` of zero in float64 may come out on the other
+side in fp32 (the rounding of such a sum is about 1e-6), which moves a gradient by a whole weight column.  ``build_backward`` decides those rows from the
 float64 forward alone and sets their ``grad_out`` rows to zero: a zero output-gradient row contributes exactly nothing to
 dz, dx, the weight gradients and the LayerNorm sums whichever branch a kernel takes, so every output is compared in full."""
 from __future__ import annotations
@@ -32,6 +37,7 @@ LN_SUM_FP32_CPU_AT_LOOP = 2.56e-3
 LN_SUM_BAR_LOOP = 3 * LN_SUM_FP32_CPU_AT_LOOP
 KINK = 1e-5       # |z| below which a hidden pre-activation counts as a ReLU kink
 KINK_SHARE = 0.01  # at most this share of the rows of a backward case may be marked
+KINKED = ("ReLU", "LeakyReLU")  # activations whose derivative jumps at 0; the others are smooth and mark nothing
 NODES = 2003      # rows of a gathered table
 LN_EPS = 1e-5
 
@@ -51,7 +57,7 @@ MI355X_ROWS = derived_rows(128 * 256, 256)  # first 32,769, loop 65,829, bwd 16,
 @dataclass(frozen=True)
 class Case:
     name: str
-    family: str            # stream (65..128) | resident (<= 64) | stream16 (129..256) | split1 | split2
+    family: str            # stream (65..128) | resident (<= 64) | stream16 (129..256) | split1 | split2 | generic
     segs: tuple            # ((width, None | "src" | "dst", mode), ...) in concat order
     dims: tuple            # out width of every Linear
     ln: bool = True
@@ -60,6 +66,8 @@ class Case:
     sliced: bool = False   # tables and weights are column slices of wider tensors (ld > width)
     shared: bool = False   # the gathered segments read one table
     k6: bool = False       # the [rows, 3] table is the edge features of (pos, src, dst): the K6 prologue computes it
+    activation: str = "ReLU"  # nn.<Name> between the Linear layers
+    act_param: float = 0.0    # LeakyReLU's negative slope, ELU's alpha
 
     @property
     def in_dim(self) -> int:
@@ -175,12 +183,132 @@ BWD_CASES = _bwd_cases()
 BWD_BY_NAME = {c.name: c for c, _ in BWD_CASES}
 
 
+# ------------------------------------------------------------------------------------------------ the generic kernel
+ACT_PARAM = {"Tanh": 0.0, "Sigmoid": 0.0, "SiLU": 0.0, "GELU": 0.0, "LeakyReLU": 0.01, "ELU": 1.0}
+GENERIC_WIDTH_CLASSES = ((20, 32), (48, 64), (100, 128), (200, 256))  # accumulator tiles WT = 1, 2, 4, 8
+PADDED_WIDTHS = (20, 48, 100, 200)  # hidden lanes beyond the width carry act(0): 0.5 with Sigmoid
+
+
+def generic_tiles(case: Case) -> tuple:
+    """(HT, OT) of the mlp_fused_kernel instance that the dispatch switch of gnc_mlp_forward_f32 picks for a case."""
+    tiles = lambda w: next(t for t in (1, 2, 4, 8) if w <= 32 * t)  # noqa: E731  (tiles_for, csrc/mlp_device.h)
+    t, od = tiles(case.dims[0]), case.dims[-1]
+    if od > 32:
+        t = max(t, tiles(od))
+    return (t, 1 if (od <= 32 and t > 1) else t)
+
+
+def generic_lds_bytes(wt: int, layers: int) -> int:
+    """lds_bytes(WT, L) of csrc/mlp_fused.hip: the weight chunk, the four waves' row tiles, the parameter rows."""
+    return ((wt * 32 + 128) * 68 + (layers + 2) * wt * 32) * 4
+
+
+def generic_loop_rows(cu: int, wt: int, layers: int = 3) -> int:
+    """More 128-row tiles than the generic kernel's persistent grid has workgroups, the last tile ragged: the grid is
+    CU x per_cu with per_cu = min(3, 160 KiB / lds_bytes(WT, L)), as in launch() of csrc/mlp_fused.hip."""
+    per_cu = max(1, min(3, (160 * 1024) // generic_lds_bytes(wt, layers)))
+    return 128 * cu * per_cu + 128 + 37
+
+
+def _generic_cases():
+    out = []
+
+    def add(name, act, **kw):
+        out.append(Case(name=name, family="generic", activation=act, act_param=ACT_PARAM.get(act, 0.0), **kw))
+
+    # the model's launch shapes, six per width; every activation meets every width class, Sigmoid and GELU every padded width
+    table = {
+        20: (("plain", "Sigmoid"), ("edge_wsplit", "GELU"), ("node", "Tanh"), ("decoder", "SiLU"), ("concat_edge", "ELU"),
+             ("encoder3", "LeakyReLU")),
+        32: (("plain", "ELU"), ("edge_wsplit", "Sigmoid"), ("node", "LeakyReLU"), ("decoder5", "GELU"), ("concat_edge", "SiLU"),
+             ("decoder", "Tanh")),
+        48: (("plain", "GELU"), ("edge_wsplit", "Sigmoid"), ("node", "SiLU"), ("decoder", "ELU"), ("concat_edge", "Tanh"),
+             ("decoder5", "LeakyReLU")),
+        64: (("encoder3", "Tanh"), ("edge_wsplit", "ELU"), ("node", "GELU"), ("decoder", "Sigmoid"), ("concat_edge", "LeakyReLU"),
+             ("plain", "SiLU")),
+        100: (("plain", "Sigmoid"), ("edge_wsplit", "GELU"), ("node", "ELU"), ("decoder", "Tanh"), ("concat_edge", "SiLU"),
+              ("encoder3", "LeakyReLU")),
+        128: (("plain", "Tanh"), ("edge_wsplit", "SiLU"), ("node", "Sigmoid"), ("decoder", "GELU"), ("concat_edge", "ELU"),
+              ("decoder5", "LeakyReLU")),
+        200: (("plain", "GELU"), ("edge_wsplit", "Sigmoid"), ("node", "LeakyReLU"), ("decoder", "SiLU"), ("concat_edge", "Tanh"),
+              ("encoder3", "ELU")),
+        256: (("plain", "LeakyReLU"), ("edge_wsplit", "Tanh"), ("node", "SiLU"), ("decoder5", "ELU"), ("concat_edge", "GELU"),
+              ("decoder", "Sigmoid")),
+    }
+    for d, pairs in table.items():
+        for shape, act in pairs:
+            add(f"generic_{shape}_{d}_{act}", act, **_shape(shape, d))
+    add("generic_sliced_node_100_GELU", "GELU", **dict(_shape("node", 100), sliced=True))
+    add("generic_nobias_100_Sigmoid", "Sigmoid", **_plain(100, (100, 100, 100), nobias=(0, 2)))
+    add("generic_L2_48_SiLU", "SiLU", **_shape("plain", 48, layers=2))
+    add("generic_L4_200_Tanh", "Tanh", **_shape("plain", 200, layers=4))
+    # ReLU descriptions that every specialised kernel declines (the catch-all role).  A hidden width that is no multiple of 4
+    # puts the second MATMUL segment of a [x | agg] launch on weight column 30 / 50 / 70 / 150: both streaming kernels want
+    # wcol % 4 == 0.  The weights-resident kernel serves up to 64 features and a narrow output (<= 32) on plain shapes only;
+    # the column-split kernel serves 65..128 features and a residual only with an output width that is a multiple of 4.
+    for d in (30, 50):
+        add(f"generic_relu_narrow_node_{d}_5", "ReLU", segs=((d, None, SEG_MATMUL), (d, None, SEG_MATMUL)), dims=(d, d, 5), ln=False)
+    for d in (70, 150):
+        add(f"generic_relu_node_{d}", "ReLU", **_shape("node", d))
+    add("generic_relu_concat_edge_70", "ReLU", **_shape("concat_edge", 70))
+    return tuple(out)
+
+
+GENERIC_CASES = _generic_cases()
+GENERIC_BY_NAME = {c.name: c for c in GENERIC_CASES}
+assert len(GENERIC_BY_NAME) == len(GENERIC_CASES) and not set(GENERIC_BY_NAME) & set(BY_NAME)
+# two shapes per width class also run with more tiles than the grid: wide-output and narrow-output instance where both exist
+GENERIC_LOOP = ("generic_plain_20_Sigmoid", "generic_concat_edge_32_SiLU", "generic_edge_wsplit_48_Sigmoid", "generic_decoder_48_ELU",
+                "generic_plain_100_Sigmoid", "generic_decoder_128_GELU", "generic_edge_wsplit_200_Sigmoid", "generic_decoder5_256_ELU")
+
+
+def generic_rows(case: Case, small_batch_rows: int, cu: int) -> dict:
+    """Row counts of a generic case by key: ``small`` for all, ``gloop`` for the cases of GENERIC_LOOP."""
+    rows = {"small": derived_rows(small_batch_rows, cu)["small"]}
+    if case.name in GENERIC_LOOP:
+        rows["gloop"] = generic_loop_rows(cu, max(generic_tiles(case)), len(case.dims))
+    return rows
+
+
+def _generic_bwd_cases():
+    """The backward through functional.fused_mlp (layer by layer on csrc/elementwise.hip): plain, node, concat_edge (gathered,
+    shared table, residual) and decoder.  Widths 20, 48 and 200 are a width class each and run six activations (two shapes
+    twice); 100 and 128 share theirs."""
+    table = {
+        20: (("plain", "Sigmoid"), ("node", "GELU"), ("concat_edge", "Tanh"), ("decoder", "SiLU"), ("plain", "LeakyReLU"), ("node", "ELU")),
+        48: (("plain", "GELU"), ("node", "Sigmoid"), ("concat_edge", "LeakyReLU"), ("decoder", "ELU"), ("plain", "Tanh"), ("node", "SiLU")),
+        100: (("plain", "GELU"), ("node", "Sigmoid"), ("concat_edge", "ELU"), ("decoder", "LeakyReLU")),
+        128: (("plain", "SiLU"), ("node", "Tanh"), ("concat_edge", "Sigmoid"), ("decoder", "GELU")),
+        200: (("plain", "Sigmoid"), ("node", "GELU"), ("concat_edge", "SiLU"), ("decoder", "Tanh"), ("plain", "ELU"), ("node", "LeakyReLU")),
+    }
+    return tuple(Case(name=f"gbwd_{shape}_{d}_{act}", family="generic", activation=act, act_param=ACT_PARAM[act], **_shape(shape, d))
+                 for d, pairs in table.items() for shape, act in pairs)
+
+
+GENERIC_BWD_CASES = _generic_bwd_cases()
+GENERIC_BWD_BY_NAME = {c.name: c for c in GENERIC_BWD_CASES}
+GENERIC_BWD_KEYS = ("small", "bwd")  # bwd = 64 x CU + 37 rows: more rows than layer_norm_backward_kernel has waves (16 blocks per
+# CU x 4 waves), and at width >= 64 more elements than activation_kernel has threads (16 x 256 per CU)
+
+
 # ------------------------------------------------------------------------------------------------ float64 definitions
 def _D(x):
     return x.double().cpu()
 
 
-def forward_def(rows, modes, ws, bs, ln, residual):
+def activate(z, activation: str = "ReLU", act_param: float = 0.0):
+    """nn.<activation> in the dtype of ``z``: one torch.nn.functional call serves float64 and float32."""
+    F = torch.nn.functional
+    if activation == "ReLU":
+        return torch.relu(z)
+    if activation == "LeakyReLU":
+        return F.leaky_relu(z, act_param)
+    if activation == "ELU":
+        return F.elu(z, act_param)
+    return {"Tanh": torch.tanh, "Sigmoid": torch.sigmoid, "SiLU": F.silu, "GELU": F.gelu}[activation](z)
+
+
+def forward_def(rows, modes, ws, bs, ln, residual, activation: str = "ReLU", act_param: float = 0.0):
     """The definition of gnc_mlp_forward_f32 on already gathered rows, in the dtype of its arguments (float64 for the
     reference, float32 for the host check): returns (out, hidden post-activations, hidden pre-activations, pre-LayerNorm)."""
     x = torch.cat([r for r, m in zip(rows, modes) if m == SEG_MATMUL], dim=1)
@@ -193,7 +321,7 @@ def forward_def(rows, modes, ws, bs, ln, residual):
     acts, pre = [], []
     for w, b in zip(ws[1:], bs[1:]):
         pre.append(z)
-        z = torch.relu(z)
+        z = activate(z, activation, act_param)
         acts.append(z)
         z = z @ w.t()
         if b is not None:
@@ -289,11 +417,14 @@ def evaluate(c: dict, dtype):
     ln = (c["ln"][0].to(dtype), c["ln"][1].to(dtype), c["ln"][2]) if c["ln"] is not None else None
     return forward_def(rows, case.modes, [view(w).to(dtype) for w in c["ws"]],
                        [b.to(dtype) if b is not None else None for b in c["bs"]], ln,
-                       rows[case.res] if case.res is not None else None)
+                       rows[case.res] if case.res is not None else None, case.activation, case.act_param)
 
 
 def _case_of(name: str) -> Case:
-    return BY_NAME[name] if name in BY_NAME else BWD_BY_NAME[name]
+    for table in (BY_NAME, BWD_BY_NAME, GENERIC_BY_NAME, GENERIC_BWD_BY_NAME):
+        if name in table:
+            return table[name]
+    raise KeyError(name)
 
 
 @functools.lru_cache(maxsize=2)
@@ -316,7 +447,8 @@ def autograd(c: dict, dtype, grad_out) -> dict:
     ws = [leaf(view(w)) for w in c["ws"]]
     bs = [leaf(b) if b is not None else None for b in c["bs"]]
     ln = (leaf(c["ln"][0]), leaf(c["ln"][1]), c["ln"][2]) if c["ln"] else None
-    out, _, pre, pre_ln = forward_def(rows, case.modes, ws, bs, ln, rows[case.res] if case.res is not None else None)
+    out, _, pre, pre_ln = forward_def(rows, case.modes, ws, bs, ln, rows[case.res] if case.res is not None else None,
+                                      case.activation, case.act_param)
     z0 = pre[0] if pre else pre_ln
     z0.retain_grad()
     out.backward(grad_out.to(dtype))
@@ -325,13 +457,34 @@ def autograd(c: dict, dtype, grad_out) -> dict:
             "dgamma": ln[0].grad if ln else None, "dbeta": ln[1].grad if ln else None}
 
 
+def table_gradients(c: dict, grads: dict, grad_out) -> list:
+    """Per segment the gradient of its TABLE from ``grads`` (of ``autograd``), in the dtype of ``grads``: the rows of ``dx`` for
+    a row-ordered segment, summed per table row for a gathered one (over both segments where they share a table: those entries
+    are one tensor).  The residual path is taken out of its segment: it belongs to the residual's own gradient, ``grad_out``."""
+    case, out, by_table, off = c["case"], [], {}, 0
+    for s, (w, ix, _) in enumerate(case.segs):
+        g = grads["dx"][:, off:off + w].clone()
+        off += w
+        if s == case.res:
+            g -= grad_out.to(g.dtype)
+        if ix is not None:
+            g = torch.zeros(NODES, w, dtype=g.dtype).index_add_(0, c["index"][ix].long(), g)
+            key = id(c["tables"][s][0])
+            if key in by_table:
+                by_table[key] += g
+                g = by_table[key]
+            by_table[key] = g
+        out.append(g)
+    return out
+
+
 @functools.lru_cache(maxsize=2)
 def build_backward(name: str, rows: int) -> dict:
-    """``build`` + ``marked`` (rows with a hidden pre-activation within KINK of zero in float64), ``grad_out`` with those rows
-    zeroed, and float64 autograd on it (``grads``)."""
+    """``build`` + ``marked`` (rows with a hidden pre-activation within KINK of zero in float64; none for an activation without
+    a kink), ``grad_out`` with those rows zeroed, and float64 autograd on it (``grads``)."""
     c = dict(build(name, rows))
     marked = torch.zeros(rows, dtype=torch.bool)
-    for z in c["pre"]:
+    for z in c["pre"] if c["case"].activation in KINKED else ():
         marked |= (z.abs() < KINK).any(dim=1)
     g = c["grad_out"].clone()
     g[marked] = 0.0
