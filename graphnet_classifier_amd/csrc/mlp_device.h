@@ -202,11 +202,26 @@ __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// the eight bf16 of a packed plane widened back to fp32, from the packed registers themselves: the low half of a dword by
+// << 16, the high half by & 0xffff0000 (16 instructions per K-group where widening element by element made hipcc round
+// every element a second time on its own: 8 more conversions and 8 more shifts per residual)
+__device__ __forceinline__ f32x8 widen_bf16x8(bf16x8 p) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 u = __builtin_bit_cast(u32x4, p);
+  const u32x4 lo = u << 16, hi = u & 0xffff0000u;
+  return f32x8{__uint_as_float(lo.x), __uint_as_float(hi.x), __uint_as_float(lo.y), __uint_as_float(hi.y),
+               __uint_as_float(lo.z), __uint_as_float(hi.z), __uint_as_float(lo.w), __uint_as_float(hi.w)};
+}
+
+// 12 v_cvt_pk_bf16_f32 (RNE), 8 shifts, 8 ANDs, 16 v_sub_f32 per K-group; the planes are the roundings of the same values
+// and the residuals the same fp32 subtractions as in the element-wise form (PACKED = false: 28 conversions, 16 shifts, 16
+// subtractions, the same bits - kept for the one instance named at mlp_resident_kernel's SPK)
+template <bool PACKED = true>
 __device__ __forceinline__ bf16x8x3 split3_bf16(f32x8 x) {
-  const bf16x8 a = __builtin_convertvector(x, bf16x8);  // v_cvt_pk_bf16_f32 (RNE)
-  const f32x8 r1 = x - __builtin_convertvector(a, f32x8);
+  const bf16x8 a = __builtin_convertvector(x, bf16x8);
+  const f32x8 r1 = x - (PACKED ? widen_bf16x8(a) : __builtin_convertvector(a, f32x8));
   const bf16x8 b = __builtin_convertvector(r1, bf16x8);
-  const f32x8 r2 = r1 - __builtin_convertvector(b, f32x8);
+  const f32x8 r2 = r1 - (PACKED ? widen_bf16x8(b) : __builtin_convertvector(b, f32x8));
   return {a, b, __builtin_convertvector(r2, bf16x8)};
 }
 
@@ -263,23 +278,24 @@ __device__ __forceinline__ void mma_group_split(f32x16 (&acc)[TO], const bf16x8x
 }
 
 // the 8 features of K-group kg of row i from the wave's fp32 LDS tile, split
+template <bool PACKED = true>
 __device__ __forceinline__ bf16x8x3 split_lds_group(const float* abuf, int kg, int i, int h) {
   const f32x4 lo = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * kg + 4 * h);
   const f32x4 hi = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * kg + 8 + 4 * h);
-  return split3_bf16(f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w});
+  return split3_bf16<PACKED>(f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w});
 }
 
 // split form of mma_chunk_from_lds: kc16 K-groups of the staged tile (columns beyond the segment width are zeros)
-template <int T>
+template <int T, bool PACKED = true>
 __device__ __forceinline__ void mma_chunk_from_lds_split(f32x16 (&acc)[T], const float* abuf, const __bf16* wsp, int kc16,
                                                          int i, int h) {
 #pragma unroll
   for (int kg = 0; kg < 4; ++kg)
-    if (kg < kc16) mma_group_split<T>(acc, split_lds_group(abuf, kg, i, h), wsp, kg, i, h);
+    if (kg < kc16) mma_group_split<T>(acc, split_lds_group<PACKED>(abuf, kg, i, h), wsp, kg, i, h);
 }
 
 // split form of mma_chunk_from_regs (one 64-column chunk, the input being the previous layer's accumulators)
-template <int TI, int TO>
+template <int TI, int TO, bool PACKED = true>
 __device__ __forceinline__ void mma_chunk_from_regs_split(f32x16 (&dst)[TO], const f32x16 (&src)[TI], const __bf16* wsp,
                                                           int in_dim, int i, int h) {
 #pragma unroll
@@ -289,7 +305,7 @@ __device__ __forceinline__ void mma_chunk_from_regs_split(f32x16 (&dst)[TO], con
       const f32x16& s = src[ts < TI ? ts : 0];
       const int r0 = 8 * (kg & 1);
       const f32x8 x = {s[r0 + 0], s[r0 + 1], s[r0 + 2], s[r0 + 3], s[r0 + 4], s[r0 + 5], s[r0 + 6], s[r0 + 7]};
-      mma_group_split<TO>(dst, split3_bf16(x), wsp, kg, i, h);
+      mma_group_split<TO>(dst, split3_bf16<PACKED>(x), wsp, kg, i, h);
     }
   }
 }

@@ -114,6 +114,12 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
                 "split shapes");
   // split instances: chunks [0, nf32) fp32, the rest split
   constexpr int nf32 = SPLIT == 1 ? 0 : NMM;
+  // SPK: the tile loop splits with the packed widening (mlp_device.h, 44 vector instructions per K-group instead of 60).
+  // One instance keeps the element-wise form (the same bits): the general-width W-split edge processor with the fused
+  // aggregation.  With fewer registers tied up in the split, hipcc puts weight fragments of its interleaved first Linear
+  // into registers of the gathered rows, and its wait-count pass, which joins that loop with the branch that requests
+  // those rows up front, then drains (`s_waitcnt vmcnt(0)`) in the middle of the loop (tools/check_isa.py, budget 2).
+  constexpr bool SPK = !(SPLIT == 1 && NADD == 2 && AGG && !FULL && !SAVE);
   __bf16* const wsp = reinterpret_cast<__bf16*>(lds + nf32 * CH);
   auto wsplit = [&](int chunk) -> const __bf16* { return wsp + (chunk - nf32) * 3 * SPLANE; };
   constexpr int PSTRIDE = WT * 32;
@@ -371,7 +377,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
               const __bf16* wch = wsplit(s);
 #pragma unroll
               for (int kg = 0; kg < 4; ++kg) {
-                mma_group_split<HT>(hid, split_lds_group(abuf, kg, i, h), wch, kg, i, h);
+                mma_group_split<HT>(hid, split_lds_group<SPK>(abuf, kg, i, h), wch, kg, i, h);
 #pragma unroll
                 for (int g = 2 * kg; g < 2 * kg + 2; ++g) {
                   const uint32_t oa = (uint32_t)na + cola, ob = (uint32_t)nb + colb;
@@ -427,7 +433,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       PROBE(7);  // issue of the next rows' loads
       if (!interleaved) {
         if constexpr (SPLIT == 1 && DUAL) {}  // both products below, from one split of the rows
-        else if constexpr (SPLIT == 1) mma_chunk_from_lds_split<HT>(hid, abuf, wsplit(s), (sv[s].width + 15) >> 4, i, h);
+        else if constexpr (SPLIT == 1) mma_chunk_from_lds_split<HT, SPK>(hid, abuf, wsplit(s), (sv[s].width + 15) >> 4, i, h);
         else mma_chunk_from_lds<HT>(hid, abuf, wres + s * CH, (sv[s].width + 7) >> 3, i, h);
       }
       if constexpr (RESREG) if (s == NMM - 1) {
@@ -494,7 +500,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       for (int l = 1; l < L - 1; ++l) {
         f32x16 nxt[HT];
         init_bias<HT>(nxt, pbuf + l * PSTRIDE, h);
-        if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, HT>(nxt, hid, wsplit(NMM + l - 1), FULL ? KC : d.in_dim[l], i, h);
+        if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, HT, SPK>(nxt, hid, wsplit(NMM + l - 1), FULL ? KC : d.in_dim[l], i, h);
         else mma_chunk_from_regs<HT, HT>(nxt, hid, wres + (NMM + l - 1) * CH, 0, FULL ? KC : d.in_dim[l], i, h);
         relu_tiles<HT>(nxt);
         if constexpr (SAVE) save_rows(nxt, l);
@@ -505,7 +511,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       // ---------------------------------------------------------------- last Linear, LayerNorm
       f32x16 o[OT];
       init_bias<OT>(o, pbuf + (L - 1) * PSTRIDE, h);
-      if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, OT>(o, hid, wsplit(NMM + L - 2), FULL ? KC : d.in_dim[L - 1], i, h);
+      if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, OT, SPK>(o, hid, wsplit(NMM + L - 2), FULL ? KC : d.in_dim[L - 1], i, h);
       else mma_chunk_from_regs<HT, OT>(o, hid, wres + (NMM + L - 2) * CH, 0, FULL ? KC : d.in_dim[L - 1], i, h);
       PROBE(4);  // last Linear
       if (FULL || d.ln_gamma) layer_norm_tiles<OT>(o, pbuf + L * PSTRIDE, pbuf + (L + 1) * PSTRIDE, out_dim, d.ln_eps, h);

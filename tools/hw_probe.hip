@@ -272,6 +272,101 @@ static void run_read(size_t bytes, int blocks_per_cu) {
   hipFree(out);
 }
 
+// The bf16 matrix instruction of the split class (mlp_device.h) beside the split's own vector work, SAME wave: after every
+// v_mfma_f32_32x32x16_bf16 (two accumulator chains alternating, as the kernel's two output tiles do) KV independent vector
+// instructions of the split's kinds in turn (v_cvt_pk_bf16_f32, v_lshlrev_b32, v_and_b32, v_sub_f32: inputs loop-invariant,
+// eight result registers, no chain between them) and, with LDSR, one ds_read_b128 (a weight fragment).  The MFMA holds the
+// pipe for 32 cycles: a slot that stays near 32 cycles per wave on the SIMD means the vector work hid in the MFMA's shadow,
+// a slot near 32 + 4 KV means it did not.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+template <int KV, bool LDSR>
+__global__ __launch_bounds__(512) void interleave_bf16(float* out, unsigned long long* cyc, int iters, float a0) {
+  __shared__ f32x4 lds[1024];
+  for (int k = threadIdx.x; k < 1024; k += blockDim.x) lds[k] = f32x4{a0 * k, a0, a0, a0};
+  __syncthreads();
+  f32x16 acc[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  const unsigned w = 0x3c003c00u + (threadIdx.x & 63);
+  const u32x4 a = {w, w, w, w}, b = {w + 1, w, w + 1, w};
+  const float xa = a0 + threadIdx.x * 1e-6f, xb = a0 * 3.f;
+  const unsigned ua = __float_as_uint(xa);
+  unsigned y[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x4 lv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  const unsigned laddr = (threadIdx.x & 63) * 16;
+  const unsigned long long t0 = __builtin_readcyclecounter();
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[k & 1]) : "v"(a), "v"(b));
+      if (LDSR) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(lv[k & 1]) : "v"(laddr), "n"(k * 1024));
+#pragma unroll
+      for (int v = 0; v < KV; ++v) {
+        const int kind = v & 3, r = (k * KV + v) & 7;
+        if (kind == 0) asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(y[r]) : "v"(xa), "v"(xb));
+        else if (kind == 1) asm volatile("v_lshlrev_b32 %0, 16, %1" : "=v"(y[r]) : "v"(ua));
+        else if (kind == 2) asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(y[r]) : "v"(ua));
+        else asm volatile("v_sub_f32 %0, %1, %2" : "=v"(y[r]) : "v"(xa), "v"(xb));
+      }
+    }
+    if (LDSR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  float s = lv[0].x + lv[1].y;
+#pragma unroll
+  for (int v = 0; v < 8; ++v) s += __uint_as_float(y[v]);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += acc[t][r];
+  if ((threadIdx.x & 63) == 0 && blockIdx.x == 0) cyc[threadIdx.x >> 6] = t1 - t0;
+  if (s == 123.456f) out[0] = s;
+}
+
+template <int KV, bool LDSR>
+static void run_interleave_bf16(int iters, int waves) {
+  float* out;
+  unsigned long long *cyc, h[8];
+  hipMalloc(&out, 4);
+  hipMalloc(&cyc, 64);
+  hipEvent_t e0, e1;
+  hipEventCreate(&e0);
+  hipEventCreate(&e1);
+  interleave_bf16<KV, LDSR><<<256, waves * 64>>>(out, cyc, iters, 1e-3f);
+  hipDeviceSynchronize();
+  hipEventRecord(e0);
+  interleave_bf16<KV, LDSR><<<256, waves * 64>>>(out, cyc, iters, 1e-3f);
+  hipEventRecord(e1);
+  hipEventSynchronize(e1);
+  float ms;
+  hipEventElapsedTime(&ms, e0, e1);
+  hipMemcpy(h, cyc, 64, hipMemcpyDeviceToHost);
+  // cycles_per_slot: one wave's counter over its own slots; per SIMD a slot of each resident wave passes in that time
+  printf("{\"probe\": \"interleave_bf16\", \"mfma\": \"v_mfma_f32_32x32x16_bf16\", \"waves_per_simd\": %d, \"valu_per_mfma\": %d, "
+         "\"ds_read_b128_per_mfma\": %d, \"cycles_per_slot\": %.1f, \"cycles_per_slot_per_wave_on_simd\": %.1f, \"ns_per_slot\": %.2f}\n",
+         waves / 4, KV, LDSR ? 1 : 0, (double)h[0] / (iters * 8.0), (double)h[0] / (iters * 8.0) / (waves / 4),
+         ms * 1e6 / (iters * 8.0));
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  hipFree(out);
+  hipFree(cyc);
+}
+
+template <bool LDSR>
+static void run_interleave_bf16_all(int iters) {
+  for (int waves = 4; waves <= 8; waves += 4) {
+    run_interleave_bf16<0, LDSR>(iters, waves);
+    run_interleave_bf16<2, LDSR>(iters, waves);
+    run_interleave_bf16<4, LDSR>(iters, waves);
+    run_interleave_bf16<6, LDSR>(iters, waves);
+    run_interleave_bf16<8, LDSR>(iters, waves);
+    run_interleave_bf16<12, LDSR>(iters, waves);
+  }
+}
+
 template <int NACC>
 static void run(int waves_per_cu, int iters) {
   float* out;
@@ -312,6 +407,11 @@ int main(int argc, char** argv) {
     run_read<8, true>(bytes, 4);
     run_read<4, true>(bytes, 16);
     run_read<8, false>(bytes, 8);
+    return 0;
+  }
+  if (argc > 1 && argv[1][0] == 'b') {  // `hw_probe b`: only the bf16 MFMA beside the split's vector work
+    run_interleave_bf16_all<false>(20000);
+    run_interleave_bf16_all<true>(20000);
     return 0;
   }
   const int iters = argc > 1 ? atoi(argv[1]) : 100000;  // ~0.1 s of MFMA per launch
