@@ -310,6 +310,133 @@ __device__ __forceinline__ void mma_chunk_from_regs_split(f32x16 (&dst)[TO], con
   }
 }
 
+// ---- the split path, software-pipelined one K-group ahead --------------------------------------------------------
+// The bf16 MFMA leaves its own wave about four vector issue slots (hw_probe b), so the 44 vector instructions
+// that split K-group kg + 1 and the reads of its weight fragments are placed BETWEEN the MFMAs of K-group kg instead of
+// in a block in front of their own MFMAs.  The arithmetic is the unpipelined form's: every accumulator sees the same MFMAs
+// in the same order on the same operands; only the place of the instructions in the stream differs.  The pipelined forms
+// take the number of K-groups as a compile-time constant (NKG), so the look-ahead is resolved at compile time and reads
+// exactly the fragments and LDS row groups the unpipelined form reads.
+template <int TO>
+struct wfrag3 {
+  bf16x8 w0[TO], w1[TO], w2[TO];
+};
+
+template <int TO>
+__device__ __forceinline__ wfrag3<TO> read_group_frags(const __bf16* wsp, int kg, int i, int h) {
+  wfrag3<TO> w;  // read in the order the MFMAs of mma_group_frags first need them
+#pragma unroll
+  for (int t = 0; t < TO; ++t) w.w0[t] = *reinterpret_cast<const bf16x8*>(wsp + (32 * t + i) * SLDW + 16 * kg + 8 * h);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) w.w1[t] = *reinterpret_cast<const bf16x8*>(wsp + (32 * t + i) * SLDW + 16 * kg + 8 * h + SPLANE);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) w.w2[t] = *reinterpret_cast<const bf16x8*>(wsp + (32 * t + i) * SLDW + 16 * kg + 8 * h + 2 * SPLANE);
+  return w;
+}
+
+// the MFMAs of mma_group_split on fragments that are already in registers (same products, same order)
+template <int TO>
+__device__ __forceinline__ void mma_group_frags(f32x16 (&acc)[TO], const bf16x8x3& x, const wfrag3<TO>& w) {
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w.w0[t], x.p2, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w.w1[t], x.p1, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w.w2[t], x.p0, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w.w0[t], x.p1, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w.w1[t], x.p0, acc[t]);
+#pragma unroll
+  for (int t = 0; t < TO; ++t) acc[t] = mfma_bf16(w.w0[t], x.p0, acc[t]);
+}
+
+// Scheduling pins of one pipelined K-group (NM MFMAs): slot = one MFMA, one LDS read in the LAST NDS slots (a fragment is
+// in flight for at least NM - NDS + 1 MFMAs before its first use and ties up its registers no longer than that), then up
+// to VPS vector instructions; the fence keeps the next K-group's instructions out of this one's slots.
+template <int NM, int NDS, int VPS = 4>
+__device__ __forceinline__ void pin_group_slots() {
+#pragma unroll
+  for (int m = 0; m < NM; ++m) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     // MFMA
+    if (m >= NM - NDS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+    __builtin_amdgcn_sched_group_barrier(0x002, VPS, 0);             // VALU
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// the 8 features of K-group kg of the previous layer's accumulators (see the K-group layout above)
+template <int TI>
+__device__ __forceinline__ f32x8 regs_group(const f32x16 (&src)[TI], int kg) {
+  const f32x16& s = src[(kg >> 1) < TI ? (kg >> 1) : 0];
+  const int r0 = 8 * (kg & 1);
+  return f32x8{s[r0 + 0], s[r0 + 1], s[r0 + 2], s[r0 + 3], s[r0 + 4], s[r0 + 5], s[r0 + 6], s[r0 + 7]};
+}
+
+// pipelined mma_chunk_from_regs_split for a compile-time input width of 16 * NKG (<= 32 * TI)
+template <int TI, int TO, int NKG>
+__device__ __forceinline__ void mma_chunk_from_regs_split_pipe(f32x16 (&dst)[TO], const f32x16 (&src)[TI], const __bf16* wsp,
+                                                               int i, int h) {
+  static_assert(NKG >= 1 && NKG <= 4 && NKG <= 2 * TI, "K-groups of one 64-column chunk held by the input tiles");
+  bf16x8x3 x = split3_bf16(regs_group<TI>(src, 0));
+  wfrag3<TO> w = read_group_frags<TO>(wsp, 0, i, h);
+#pragma unroll
+  for (int kg = 0; kg < NKG; ++kg) {
+    bf16x8x3 xn = x;
+    wfrag3<TO> wn = w;
+    if (kg + 1 < NKG) {
+      wn = read_group_frags<TO>(wsp, kg + 1, i, h);
+      xn = split3_bf16(regs_group<TI>(src, kg + 1));
+    }
+    mma_group_frags<TO>(dst, x, w);
+    if (kg + 1 < NKG) pin_group_slots<6 * TO, 3 * TO>();
+    x = xn;
+    w = wn;
+  }
+}
+
+// the raw fp32 row group of K-group kg of row i from the wave's LDS tile
+__device__ __forceinline__ f32x8 lds_group(const float* abuf, int kg, int i, int h) {
+  const f32x4 lo = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * kg + 4 * h);
+  const f32x4 hi = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 16 * kg + 8 + 4 * h);
+  return f32x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+}
+
+// pipelined mma_chunk_from_lds_split for a compile-time count of K-groups.  The fp32 row group travels two K-groups ahead of
+// its MFMAs (its LDS round trip must be over before its split can start), the split and the weight fragments one.
+// `with_group(kg)` is called behind the MFMAs of K-group kg: instructions of the caller that are to ride along with them (the
+// W-split edge processor's gather requests); they share the K-group's scheduling region, and the last one is fenced too.
+struct no_group_work {
+  __device__ __forceinline__ void operator()(int) const {}
+};
+template <int T, int NKG, class WithGroup = no_group_work>
+__device__ __forceinline__ void mma_chunk_from_lds_split_pipe(f32x16 (&acc)[T], const float* abuf, const __bf16* wsp, int i, int h,
+                                                              WithGroup with_group = WithGroup()) {
+  static_assert(NKG >= 1 && NKG <= 4, "K-groups of one staged 64-column tile");
+  f32x8 r = lds_group(abuf, NKG > 1 ? 1 : 0, i, h);  // rows of K-group 1 (NKG == 1: unused)
+  bf16x8x3 x = split3_bf16(lds_group(abuf, 0, i, h));
+  wfrag3<T> w = read_group_frags<T>(wsp, 0, i, h);
+#pragma unroll
+  for (int kg = 0; kg < NKG; ++kg) {
+    bf16x8x3 xn = x;
+    wfrag3<T> wn = w;
+    f32x8 rn = r;
+    if (kg + 1 < NKG) {
+      if (kg + 2 < NKG) rn = lds_group(abuf, kg + 2, i, h);
+      wn = read_group_frags<T>(wsp, kg + 1, i, h);
+      xn = split3_bf16(r);
+    }
+    mma_group_frags<T>(acc, x, w);
+    with_group(kg);
+    if (kg + 2 < NKG) pin_group_slots<6 * T, (3 * T + 2 < 6 * T ? 3 * T + 2 : 6 * T)>();
+    else if (kg + 1 < NKG) pin_group_slots<6 * T, 3 * T>();
+    else if constexpr (!__is_same(WithGroup, no_group_work)) __builtin_amdgcn_sched_barrier(0);
+    x = xn;
+    w = wn;
+    r = rn;
+  }
+}
+
 // x(lane) + x(lane ^ 32) in every lane, on the VALU: gfx950's v_permlane32_swap exchanges the upper half of
 // one register with the lower half of another (no LDS round trip like ds_bpermute / __shfl_xor).
 __device__ __forceinline__ float add_halves(float x) {

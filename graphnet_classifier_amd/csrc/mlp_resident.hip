@@ -120,6 +120,14 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   // into registers of the gathered rows, and its wait-count pass, which joins that loop with the branch that requests
   // those rows up front, then drains (`s_waitcnt vmcnt(0)`) in the middle of the loop (tools/check_isa.py, budget 2).
   constexpr bool SPK = !(SPLIT == 1 && NADD == 2 && AGG && !FULL && !SAVE);
+  // PIPE: the split Linears run software-pipelined one K-group ahead (mlp_device.h: the split and the weight fragments of
+  // K-group kg + 1 between the MFMAs of kg).  The pipelined forms want the K-group count at compile time, so they serve the
+  // instances whose hidden width is 64 by the launcher's own tests: FULL, the encoders (class 2, one MATMUL step: hidden64),
+  // and the plain class-1 stacks (the decoder: hidden64).  The general-width W-split edge processor keeps the unpipelined
+  // form, and so do the node processors (class 2, two MATMUL steps) and the projections (DUAL and its single-Linear twin):
+  // their launches measured no faster with it.  A first Linear with Linears behind it is pipelined
+  // when its staged segment is 64 wide (tested per launch).
+  constexpr bool PIPE = SPLIT != 0 && SPK && !DUAL && (FULL || (SPLIT == 2 && NMM == 1) || (SPLIT == 1 && NADD == 0));
   __bf16* const wsp = reinterpret_cast<__bf16*>(lds + nf32 * CH);
   auto wsplit = [&](int chunk) -> const __bf16* { return wsp + (chunk - nf32) * 3 * SPLANE; };
   constexpr int PSTRIDE = WT * 32;
@@ -375,9 +383,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
             int na = __shfl(rba, rs, 64), nb = __shfl(rbb, rs, 64);
             if constexpr (SPLIT == 1) {  // two pieces of each table per 16-k group
               const __bf16* wch = wsplit(s);
-#pragma unroll
-              for (int kg = 0; kg < 4; ++kg) {
-                mma_group_split<HT>(hid, split_lds_group<SPK>(abuf, kg, i, h), wch, kg, i, h);
+              // one K-group's gather requests: two pieces of each table
+              auto request = [&](int kg) {
 #pragma unroll
                 for (int g = 2 * kg; g < 2 * kg + 2; ++g) {
                   const uint32_t oa = (uint32_t)na + cola, ob = (uint32_t)nb + colb;
@@ -387,6 +394,15 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
                   }
                   addA[g] = window_load(wa, oa);
                   addB[g] = window_load(wb, ob);
+                }
+              };
+              if constexpr (PIPE) {  // the staged segment is 64 wide here: four K-groups, kg's requests riding along with its MFMAs
+                mma_chunk_from_lds_split_pipe<HT, 4>(hid, abuf, wch, i, h, request);
+              } else {
+#pragma unroll
+                for (int kg = 0; kg < 4; ++kg) {
+                  mma_group_split<HT>(hid, split_lds_group<SPK>(abuf, kg, i, h), wch, kg, i, h);
+                  request(kg);
                 }
               }
             } else {
@@ -433,7 +449,12 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       PROBE(7);  // issue of the next rows' loads
       if (!interleaved) {
         if constexpr (SPLIT == 1 && DUAL) {}  // both products below, from one split of the rows
-        else if constexpr (SPLIT == 1) mma_chunk_from_lds_split<HT, SPK>(hid, abuf, wsplit(s), (sv[s].width + 15) >> 4, i, h);
+        else if constexpr (SPLIT == 1) {
+          const int kc16 = (sv[s].width + 15) >> 4;
+          // (a lone Linear - the single projection - stays as it is, like its DUAL twin)
+          if (PIPE && kc16 == 4 && L > 1) mma_chunk_from_lds_split_pipe<HT, 4>(hid, abuf, wsplit(s), i, h);
+          else mma_chunk_from_lds_split<HT, SPK>(hid, abuf, wsplit(s), kc16, i, h);
+        }
         else mma_chunk_from_lds<HT>(hid, abuf, wres + s * CH, (sv[s].width + 7) >> 3, i, h);
       }
       if constexpr (RESREG) if (s == NMM - 1) {
@@ -463,6 +484,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       init_bias<HT>(hidb, pbuf, h);  // (no bias: zeros)
       if constexpr (SPLIT == 1) {  // a K-group's rows are split once and feed both matrices' six products
         const int kc16 = (sv[0].width + 15) >> 4;
+        // (not pipelined: with the split of K-group kg + 1 between its 24 MFMAs the launch measured no faster)
 #pragma unroll
         for (int kg = 0; kg < 4; ++kg)
           if (kg < kc16) {
@@ -500,7 +522,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       for (int l = 1; l < L - 1; ++l) {
         f32x16 nxt[HT];
         init_bias<HT>(nxt, pbuf + l * PSTRIDE, h);
-        if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, HT, SPK>(nxt, hid, wsplit(NMM + l - 1), FULL ? KC : d.in_dim[l], i, h);
+        if constexpr (PIPE) mma_chunk_from_regs_split_pipe<HT, HT, 4>(nxt, hid, wsplit(NMM + l - 1), i, h);
+        else if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, HT, SPK>(nxt, hid, wsplit(NMM + l - 1), FULL ? KC : d.in_dim[l], i, h);
         else mma_chunk_from_regs<HT, HT>(nxt, hid, wres + (NMM + l - 1) * CH, 0, FULL ? KC : d.in_dim[l], i, h);
         relu_tiles<HT>(nxt);
         if constexpr (SAVE) save_rows(nxt, l);
@@ -511,7 +534,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       // ---------------------------------------------------------------- last Linear, LayerNorm
       f32x16 o[OT];
       init_bias<OT>(o, pbuf + (L - 1) * PSTRIDE, h);
-      if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, OT, SPK>(o, hid, wsplit(NMM + L - 2), FULL ? KC : d.in_dim[L - 1], i, h);
+      if constexpr (PIPE) mma_chunk_from_regs_split_pipe<HT, OT, 4>(o, hid, wsplit(NMM + L - 2), i, h);
+      else if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, OT, SPK>(o, hid, wsplit(NMM + L - 2), FULL ? KC : d.in_dim[L - 1], i, h);
       else mma_chunk_from_regs<HT, OT>(o, hid, wres + (NMM + L - 2) * CH, 0, FULL ? KC : d.in_dim[L - 1], i, h);
       PROBE(4);  // last Linear
       if (FULL || d.ln_gamma) layer_norm_tiles<OT>(o, pbuf + L * PSTRIDE, pbuf + (L + 1) * PSTRIDE, out_dim, d.ln_eps, h);
