@@ -9,6 +9,10 @@ by torchvision's ``ImageFolder`` rules and yields ``((x, pos, edge_index), label
 ``GraphImageFolder.loader()`` is the fast way through an epoch: the same samples in the same order as that
 ``DataLoader`` (and the same draws from the global RNG), with decoding on a host thread pool and the resize and the
 graph builds of a chunk of images run as batched launches (``image_to_graph.graphs_from_images``).
+
+``ImageTensorFolder(dataset_path, resize_value)`` is the image side of the reference's MLP baseline (``main.py:13-18``:
+``ImageFolder`` + ``Resize`` + ``ToTensor``): ``(float32 [3, R, R], label)`` per image, and ``.loader(batch_size=8)`` yields the
+mini-batches of ``DataLoader(ds, batch_size=8, shuffle=True)`` as ``(float32 [B, 3, R, R] on the device, labels [B])``.
 """
 from __future__ import annotations
 
@@ -192,4 +196,55 @@ class GraphFolderLoader:
                 for b in groups[c]:
                     yield (I2G.collate_graphs(graphs[at:at + len(b)]),
                            torch.tensor([samples[i][1] for i in b], dtype=torch.long))
+                    at += len(b)
+
+
+class ImageTensorFolder(Dataset):
+    """``ImageFolder(root, transform=Compose([Resize((R, R)), ToTensor()]))`` of the reference's ``main.py:13-17`` without
+    torchvision: the same classes, samples and order, the same pixel values (Pillow's BILINEAR resize and the division by 255
+    run on the device, ``image_to_graph.tensors_from_images``)."""
+
+    def __init__(self, dataset_path='dataset', resize_value=128):
+        self.dataset_path = dataset_path
+        self.classes, self.class_to_idx = find_classes(dataset_path)
+        self.samples = make_dataset(dataset_path, self.class_to_idx)
+        self.targets = [t for _, t in self.samples]
+        self.resize_value = resize_value
+
+    def __len__(self):
+        return len(self.samples)
+
+    def __getitem__(self, idx):
+        path, label = self.samples[idx]
+        return I2G.tensors_from_images([load_rgb(path)], self.resize_value)[0], label
+
+    def loader(self, batch_size: int = 8, shuffle: bool = True, drop_last: bool = False, chunk: int = 64, workers: int | None = None):
+        """Iterable for ``train(mlp, ds.loader(), epochs)``; every iteration is one epoch of ``(images float32 [B, 3, R, R] on the
+        device, labels int64 [B])``, the batches being those of ``DataLoader(self, batch_size=batch_size, shuffle=shuffle,
+        drop_last=drop_last)`` under the same global RNG state; without ``drop_last`` the last batch may be shorter."""
+        return TensorFolderLoader(self, shuffle, chunk, workers, batch_size, drop_last)
+
+
+class TensorFolderLoader(GraphFolderLoader):
+    """Epochs over an ``ImageTensorFolder``: the index batches and the decode pipeline of ``GraphFolderLoader``, then resize and
+    conversion of a chunk of whole mini-batches in two batched launches."""
+
+    def __iter__(self):
+        samples = self.dataset.samples
+        batches = self.index_batches()
+        per = max(1, self.chunk // self.batch_size)
+        groups = [batches[i:i + per] for i in range(0, len(batches), per)]
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            def decode(group):
+                return [pool.submit(load_rgb, samples[i][0]) for b in group for i in b]
+
+            pending = decode(groups[0]) if groups else []
+            for c, group in enumerate(groups):
+                images = [f.result() for f in pending]
+                pending = decode(groups[c + 1]) if c + 1 < len(groups) else []
+                tensors = I2G.tensors_from_images(images, self.dataset.resize_value)
+                del images
+                at = 0
+                for b in group:
+                    yield tensors[at:at + len(b)], torch.tensor([samples[i][1] for i in b], dtype=torch.long)
                     at += len(b)

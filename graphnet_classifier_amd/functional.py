@@ -9,6 +9,9 @@ reference's only caller that needs gradients is ``utils/train_model.py:41``
   forward of the widths <= 64 kernels keeps the hidden layers' post-activations for it, the wider ones
   recompute the forward of each tile from the inputs (``GNC_TORCH_BACKWARD=1`` switches to a PyTorch-ROCm
   recompute for A/B runs; nothing here ever runs on the CPU);
+* an MLP over ONE wide table (the image-MLP baseline: 49152 inputs, 8 rows) runs its first Linear on the split-K kernels K16 and
+  the rest of its chain as an ordinary fused-MLP call, tied together by ``_WideFirstMLP`` (``GNC_NO_WIDE_LINEAR=1`` keeps the
+  row-tiled kernels everywhere, for A/B runs);
 * batch normalisation over table rows (``norm_type='BatchNorm1d'``) runs on the K14 kernels both ways.
 """
 from __future__ import annotations
@@ -292,6 +295,59 @@ def _layerwise_mlp_backward_hip(meta: _MlpMeta, args, need, grad_out):
     return tuple(grads)
 
 
+class _WideFirstMLP(torch.autograd.Function):
+    """A fused-MLP call over ONE wide row-ordered table: the first Linear + activation on K16 (csrc/wide_linear.hip), the remaining
+    Linears + LayerNorm as an ordinary fused-MLP launch over its output; the backward of that launch supplies the gradient of the
+    first Linear's output (its ``need_dx``), from which K16 forms dW0 and db0.  The table itself gets no gradient (it is data: the
+    route is not taken when it wants one).  args = x, weights[L], biases[L], (gamma, beta if LN)."""
+
+    @staticmethod
+    def forward(ctx, meta: _MlpMeta, x, *params):
+        l = meta.num_linear
+        weights, biases = list(params[:l]), list(params[l:2 * l])
+        ln = (params[2 * l], params[2 * l + 1], meta.ln_eps) if meta.has_ln else None
+        training = meta.training and any(ctx.needs_input_grad)
+        relu = meta.activation == "ReLU"
+        a0, z0 = native.wide_linear_forward(x, weights[0], biases[0], meta.activation, meta.act_param, want_z=training and not relu)
+        acts = [] if training else None
+        out = native.mlp_forward([(a0, None)], weights[1:], biases[1:], ln=ln, activation=meta.activation, act_param=meta.act_param,
+                                 rows=meta.rows, save_act=acts, save_need_dx=True)
+        ctx.meta = meta
+        ctx.n_acts = len(acts) if acts else 0
+        if training:
+            ctx.save_for_backward(x, *params, a0, a0 if relu else z0, *(acts or []))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        meta, saved = ctx.meta, ctx.saved_tensors
+        l = meta.num_linear
+        acts = list(saved[len(saved) - ctx.n_acts:]) if ctx.n_acts else None
+        x, params, a0, az = saved[0], saved[1:len(saved) - ctx.n_acts - 2], saved[-ctx.n_acts - 2], saved[-ctx.n_acts - 1]
+        need = ctx.needs_input_grad[2:]
+        # the rest of the chain, as the fused-MLP call over a0 that the forward made: argument order a0, W1.., b1.., (gamma, beta)
+        rest = _MlpMeta((None,), l - 1, meta.activation, meta.act_param, meta.ln_eps, meta.has_ln, False, meta.rows)
+        rest_args = (a0,) + tuple(params[1:l]) + tuple(params[l + 1:2 * l]) + tuple(params[2 * l:])
+        rest_need = (True,) + tuple(need[1:l]) + tuple(need[l + 1:2 * l]) + tuple(need[2 * l:])
+        g = _fused_mlp_backward_hip(rest, rest_args, rest_need, grad_out, acts)
+        if g is None:  # an activation other than ReLU, or a single Linear behind the first: layer by layer, still on this library
+            g = _layerwise_mlp_backward_hip(rest, rest_args, rest_need, grad_out)
+        dw0 = db0 = None
+        if need[0] or need[l]:
+            dw0, db0 = native.wide_linear_backward(g[0], az, x, meta.activation, meta.act_param)
+        return (None, None, dw0 if need[0] else None) + tuple(g[1:l]) + (db0 if need[l] else None,) + tuple(g[l:])
+
+
+def wide_linear_route(segments, weights, biases, ln, activation, residual, rows) -> bool:
+    """Does this fused-MLP call run its first Linear on K16?  One plain table that wants no gradient, and the library's own
+    decision (native.wide_linear_serves) about everything else.  ``GNC_NO_WIDE_LINEAR=1`` (read on every call) says no."""
+    if len(segments) != 1 or residual is not None or os.environ.get("GNC_NO_WIDE_LINEAR") is not None or not HIP_BACKWARD:
+        return False
+    if segments[0][0].requires_grad and torch.is_grad_enabled():
+        return False  # K16 does not form the gradient of its input
+    return native.wide_linear_serves(segments, weights, biases, ln, activation, residual, rows)
+
+
 def fused_mlp(segments, weights, biases, ln=None, activation: str = "ReLU", act_param: float = 0.0, residual=None,
               rows: int | None = None) -> torch.Tensor:
     """segments: list of (table fp32 [*, w], index int32 [rows] | None); see native.mlp_forward."""
@@ -301,6 +357,8 @@ def fused_mlp(segments, weights, biases, ln=None, activation: str = "ReLU", act_
         rows = indices[0].numel() if indices[0] is not None else tables[0].size(0)
     meta = _MlpMeta(indices, len(weights), activation, float(act_param), float(ln[2]) if ln is not None else 0.0,
                     ln is not None, residual is not None, int(rows))
+    if wide_linear_route(segments, weights, biases, ln, activation, residual, rows):
+        return _WideFirstMLP.apply(meta, tables[0], *weights, *biases, *((ln[0], ln[1]) if ln is not None else ()))
     args = list(tables) + list(weights) + list(biases)
     if ln is not None:
         args += [ln[0], ln[1]]

@@ -391,6 +391,16 @@ def collate_graphs(graphs):
     return GraphBatch(x, pos, edge_index + shift, graph_ptr, edge_ptr)
 
 
+def tensors_from_images(images_u8, resize_value: int = 128) -> torch.Tensor:
+    """torchvision's ``Compose([Resize((R, R)), ToTensor()])`` (main.py:13-16 of the reference) for a batch of decoded uint8 RGB
+    images ``[H_i, W_i, 3]`` of any sizes: float32 ``[B, 3, R, R]`` on the device, values in [0, 1].  ``Resize`` on a PIL image is
+    Pillow's BILINEAR ``Image.resize`` (``resize`` here, byte for byte), ``ToTensor`` is ``permute(2, 0, 1).float().div(255)``
+    (``native.u8_hwc_to_f32_chw``, bit for bit): two batched enqueues, no host synchronisation."""
+    if len(images_u8) == 0:
+        raise ValueError("tensors_from_images: empty list of images")
+    return native.u8_hwc_to_f32_chw(resize(list(images_u8), (resize_value, resize_value), "bilinear"))
+
+
 METHODS = ("pixel", "patch", "superpixel")
 
 

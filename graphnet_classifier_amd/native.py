@@ -106,6 +106,13 @@ _SIGNATURES = {
     "gnc_resize_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "gnc_resize_rgb_u8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    "gnc_u8_hwc_to_f32_chw": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "gnc_wide_linear_supported": (c_int32, [c_void_p, c_void_p]),
+    "gnc_wide_linear_workspace_floats": (c_int64, [c_int64, c_int64, c_int32, c_int32]),
+    "gnc_wide_linear_forward_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_float,
+                                              c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "gnc_wide_linear_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32,
+                                               c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnc_colsum_pair_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
     "gnc_reduce_partials_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnc_activation_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_float, c_void_p, c_int64, c_void_p]),
@@ -177,6 +184,11 @@ class XtyJob(Structure):
 class ReadoutBatchedPlan(Structure):
     _fields_ = [(name, c_int64) for name in ("f_slices", "f_slice_len", "tail_rows", "small_parts", "dw1_parts", "dw1_graph_range",
                                               "dy_groups", "forward_workspace_floats", "backward_workspace_floats")]
+
+
+class WideLinearPlan(Structure):
+    _fields_ = [(name, c_int64) for name in ("k_slices", "k_slice_len", "dw_parts", "dw_row_range", "forward_workspace_floats",
+                                              "backward_workspace_floats")]
 
 
 GNC_XTY_MAX_JOBS = 8
@@ -826,6 +838,101 @@ def readout_batched_backward(grad_logits, y, graph_ptr, num_graphs: int, num_nod
                        4.0 * G * w1.numel()), "gnc_readout_batched_backward_f32")
     dw2, db2, dw3, db3, db1 = small.split([H2 * H1, H2, C * H2, C, H1])
     return dy, dw1, db1, dw2.view(H2, H1), db2, dw3.view(C, H2), db3
+
+
+# --------------------------------------------------------------------------- K16: split-K first Linear of a wide-input MLP
+def wide_linear_plan_of(desc: MlpDesc) -> dict | None:
+    """The library's decision for running the first Linear of this fused-MLP description on K16 (host only, no GPU needed): None
+    when the description stays on the row-tiled kernels, otherwise the split of K in the forward, the row ranges of the
+    backward and the workspace sizes in floats."""
+    plan = WideLinearPlan()
+    if not load_library().gnc_wide_linear_supported(ctypes.byref(desc), ctypes.byref(plan)):
+        return None
+    return {name: int(getattr(plan, name)) for name, _ in WideLinearPlan._fields_}
+
+
+def wide_linear_serves(segments, weights, biases, ln, activation: str, residual, rows: int | None) -> bool:
+    """Does K16 take the first Linear of this fused-MLP call?  The structure of the call is looked at here (one table in row
+    order in front of at least two Linears - everything a description cannot say otherwise), every size by the library's own
+    decision."""
+    if len(segments) != 1 or segments[0][1] is not None or residual is not None or len(weights) < 2 or activation not in ACTIVATIONS:
+        return False
+    table, w0 = segments[0][0], weights[0]
+    if table.dim() != 2 or table.dtype != torch.float32 or not table.is_cuda:
+        return False
+    rows = _rows_of(segments, rows)
+    lib = load_library()
+    if rows != table.size(0) or lib.gnc_wide_linear_workspace_floats(rows, w0.size(1), w0.size(0), 0) < 0:
+        return False  # (the size question alone first: it needs no description, and no call of the graph model gets past it)
+    table, w0 = _rowmajor(table), _rowmajor(w0.detach())
+    desc = make_mlp_desc([(table, None, table.size(1), SEG_MATMUL, 0)], [w0] + [w.detach() for w in weights[1:]], list(biases), ln,
+                         activation, 0.0, None, table, rows)
+    return lib.gnc_wide_linear_supported(ctypes.byref(desc), None) == 1
+
+
+def wide_linear_forward(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, activation: str = "ReLU", act_param: float = 0.0,
+                        want_z: bool = False):
+    """(a0, z0): a0 = act(x w^T + bias) [rows, H] on K16 (gnc_wide_linear_forward_f32: partial products per slice of K, then the
+    tail that sums them in ascending order); z0 = the pre-activation when ``want_z`` (the backward of an activation other than
+    ReLU reads it), else None.  ``x`` and ``w`` are read where they lie: any row pitch, any alignment."""
+    lib = load_library()
+    _require_cuda(x, w, bias)
+    x, w = _rowmajor(x), _rowmajor(w.detach())
+    rows, K, H, dev = x.size(0), x.size(1), w.size(0), x.device
+    if w.size(1) != K:
+        raise ValueError(f"wide_linear_forward: x has {K} columns, the weight {w.size(1)}")
+    n_ws = lib.gnc_wide_linear_workspace_floats(rows, K, H, 0)
+    if n_ws < 0:
+        raise RuntimeError("wide_linear_forward: shape outside the kernel's set (ask wide_linear_serves first)")
+    a0 = torch.empty(rows, H, dtype=torch.float32, device=dev)
+    z0 = torch.empty(rows, H, dtype=torch.float32, device=dev) if want_z else None
+    ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+    b = bias.detach().contiguous() if bias is not None else None
+    with torch.cuda.device(dev):
+        _check(_launch(f"wide_linear_forward_in{K}_h{H}", x,
+                       lambda: lib.gnc_wide_linear_forward_f32(
+                           x.data_ptr(), _ld(x), rows, K, w.data_ptr(), _ld(w), b.data_ptr() if b is not None else None, H,
+                           ACTIVATIONS[activation], float(act_param), a0.data_ptr(), H, z0.data_ptr() if want_z else None, H,
+                           ws.data_ptr(), ws.numel(), _stream(x)), 2.0 * rows * K * H), "gnc_wide_linear_forward_f32")
+    return a0, z0
+
+
+def wide_linear_backward(grad_a0: torch.Tensor, az: torch.Tensor, x: torch.Tensor, activation: str = "ReLU", act_param: float = 0.0):
+    """(dW [H, K], db [H]) of ``wide_linear_forward`` from the gradient of its output: ``az`` is the forward's a0 for ReLU and its
+    z0 for every other activation.  The gradient of ``x`` is not formed."""
+    lib = load_library()
+    _require_cuda(grad_a0, az, x)
+    g, az, x = _rowmajor(grad_a0), _rowmajor(az), _rowmajor(x)
+    rows, K, H, dev = x.size(0), x.size(1), g.size(1), x.device
+    n_ws = lib.gnc_wide_linear_workspace_floats(rows, K, H, 1)
+    if n_ws < 0 or g.size(0) != rows or az.shape != g.shape:
+        raise RuntimeError("wide_linear_backward: shape outside the kernel's set or operands that do not match")
+    dw = torch.empty(H, K, dtype=torch.float32, device=dev)
+    db = torch.empty(H, dtype=torch.float32, device=dev)
+    ws = torch.empty(n_ws, dtype=torch.float32, device=dev) if n_ws > 0 else None
+    with torch.cuda.device(dev):
+        _check(_launch(f"wide_linear_backward_in{K}_h{H}", x,
+                       lambda: lib.gnc_wide_linear_backward_f32(
+                           g.data_ptr(), _ld(g), az.data_ptr(), _ld(az), x.data_ptr(), _ld(x), rows, K, H, ACTIVATIONS[activation],
+                           float(act_param), dw.data_ptr(), db.data_ptr(), ws.data_ptr() if ws is not None else None, n_ws,
+                           _stream(x)), 2.0 * rows * K * H), "gnc_wide_linear_backward_f32")
+    return dw, db
+
+
+def u8_hwc_to_f32_chw(img: torch.Tensor) -> torch.Tensor:
+    """torchvision's ``ToTensor`` for a batch of uint8 images [B, H, W, C] on the device: float32 [B, C, H, W] = value / 255 (a true
+    division: bit for bit ``img.permute(0, 3, 1, 2).float().div(255)``), one launch."""
+    _require_cuda(img)
+    if img.dtype != torch.uint8 or img.dim() != 4:
+        raise TypeError(f"u8_hwc_to_f32_chw: expected uint8 [B, H, W, C], got {img.dtype} {tuple(img.shape)}")
+    img = img.contiguous()
+    B, H, W, C = img.shape
+    out = torch.empty(B, C, H, W, dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        _check(_launch("u8_hwc_to_f32_chw", img,
+                       lambda: load_library().gnc_u8_hwc_to_f32_chw(img.data_ptr(), B, H, W, C, out.data_ptr(), _stream(img))),
+               "gnc_u8_hwc_to_f32_chw")
+    return out
 
 
 # --------------------------------------------------------------------------- feed of a captured ragged mini-batch

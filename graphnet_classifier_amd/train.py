@@ -17,6 +17,8 @@ dataset order (:35-45), average training loss per epoch, early stopping on it (:
 * a loader that yields ``(synthetic.GraphBatch, labels [B])`` (``GraphImageFolder.loader(batch_size=B)``) is stepped once per
   mini-batch through ``CombinedModel.forward_batched`` - mean cross-entropy over the batch, captured when consecutive full
   batches share a topology; ``evaluate`` / ``predict`` score a model over either loader form;
+* a loader that yields plain tensor batches (``ImageTensorFolder.loader(batch_size=8)``: the reference's image-MLP baseline) is
+  stepped once per batch through ``model(x)``, captured when two consecutive batches share their shape (``CapturedTensorStep``);
 * the run's side effects live in three small objects: ``RunJournal`` (the log file and the console lines),
   ``PlateauStopper`` (best loss so far, epochs without improvement) and ``CheckpointShelf`` (the ``.pth`` files).
 
@@ -438,6 +440,37 @@ class CapturedRaggedBatchStep(CapturedTrainStep):
         self.feed.check(self._status)
 
 
+class CapturedTensorStep(CapturedTrainStep):
+    """One training step on a plain tensor batch (the reference's image-MLP path, main.py:21-29: ``mod(x)`` on float32
+    ``[B, 3, R, R]``, mean cross-entropy over the B labels), captured once and replayed, on the capture machinery of
+    ``CapturedTrainStep``: ONE input buffer of the sample's shape and dtype, one label buffer.  Everything runs on a single
+    stream.  ``matches(sample, label)``: same shapes and dtype (a short last batch does not match and runs eagerly)."""
+
+    def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, sample: torch.Tensor, label, loss_sum: torch.Tensor, *,
+                 loss_scale: float = 1.0, capture_error_mode: str = "global"):
+        dev = require_gpu_param(next(model.parameters()), "CapturedTensorStep")
+        self.optimizer = optimizer
+        self.loss_sum = loss_sum
+        self.collective_outside = _world(optimizer.fp.reducer.group) > 1
+        self.edge_capacity = self.node_capacity = None
+        self.x = sample.to(dev).clone()
+        self.pos = self.edge_index = None
+        self.label = torch.as_tensor(label).to(dev).clone()
+        self._capture(model, criterion, lambda mod, xx, pp, ee: mod(xx), loss_scale, capture_error_mode)
+
+    def matches(self, sample, label=None) -> bool:
+        return (isinstance(sample, torch.Tensor) and sample.shape == self.x.shape and sample.dtype == self.x.dtype
+                and (label is None or torch.as_tensor(label).shape == self.label.shape))
+
+    def __call__(self, sample, label) -> None:
+        self.x.copy_(sample, non_blocking=True)
+        self.label.copy_(torch.as_tensor(label), non_blocking=True)
+        self.replay()
+
+    def check(self) -> None:
+        pass
+
+
 # --------------------------------------------------------------------------- the run's side effects
 class RunJournal:
     """Everything the reference's train() writes or prints besides checkpoints: the timestamped
@@ -581,6 +614,8 @@ class _SampleStepper:
         self._previous = None
         self.captured_batch: CapturedTrainStep | None = None  # mini-batches (GraphBatch samples)
         self._previous_batch = None
+        self.captured_tensor: CapturedTensorStep | None = None  # plain tensor samples (the image-MLP baseline)
+        self._previous_tensor = None
         self.batched = False
         self.capture_ragged_batches = capture  # ragged mini-batches (superpixel graphs): CapturedRaggedBatchStep
         self.ragged = _RaggedBatchCaptures(
@@ -623,6 +658,23 @@ class _SampleStepper:
             self.padded(sample, label)
             return True
         self._previous = sample
+        return False
+
+    def _try_replay_tensor(self, sample: torch.Tensor, label) -> bool:
+        """A plain tensor sample: captured once two consecutive samples share shape and dtype (and label shape), replayed while
+        they keep doing so; anything else (the first sample, a short last batch) is left to the eager step.  Only this package's
+        ``MLP`` is captured: its forward is a function of the input buffer and the parameters alone, on the device, which is what
+        a replay repeats - an arbitrary module may read host state or copy from the host in its forward and keeps the eager step."""
+        from .MLP import MLP
+        if not isinstance(self.model, MLP):
+            return False
+        key = (sample.shape, sample.dtype, torch.as_tensor(label).shape)
+        if self.captured_tensor is None and key == self._previous_tensor:
+            self.captured_tensor = CapturedTensorStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum)
+        if self.captured_tensor is not None and self.captured_tensor.matches(sample, label):
+            self.captured_tensor(sample, label)
+            return True
+        self._previous_tensor = key
         return False
 
     def check(self) -> None:
@@ -679,6 +731,8 @@ class _SampleStepper:
             return self._step_batch(sample, label)
         is_graph = isinstance(sample, (tuple, list)) and len(sample) == 3
         if self.capture and is_graph and self._try_replay(sample, label):
+            return
+        if self.capture and isinstance(sample, torch.Tensor) and self._try_replay_tensor(sample, label):
             return
         if is_graph:
             # edge_index stays where it is: a host tensor is looked up in the topology cache by content, so equal
@@ -759,6 +813,7 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
             "captured_any_topology": stepper.padded is not None,
             "captured_ragged": stepper.padded is not None and stepper.padded.node_capacity is not None,
             "captured_ragged_batch": stepper.ragged.current is not None,
+            "captured_tensor": stepper.captured_tensor is not None,
             "optimizer": optimizer}
 
 

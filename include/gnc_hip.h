@@ -660,6 +660,48 @@ size_t gnc_resize_workspace_bytes(int32_t B, int32_t in_h, int32_t in_w, int32_t
 int gnc_resize_rgb_u8(const uint8_t* src, const int64_t* table, int32_t B, int32_t in_h, int32_t in_w, int32_t out_h,
                       int32_t out_w, int32_t filter, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* gnc_u8_hwc_to_f32_chw  torchvision's ToTensor for B uint8 images [B, H, W, C] on the device: out [B, C, H, W] float32 with
+ *                      out[b, c, y, x] = float(img[b, y, x, c]) / 255 (a correctly rounded division: bit for bit what
+ *                      `t.permute(2, 0, 1).float().div(255)` gives).  B, C <= 65535.  Stream-ordered, a kernel node under stream
+ *                      capture.  Added without an ABI bump: a library without this symbol fails the symbol lookup of the binding.
+ */
+int gnc_u8_hwc_to_f32_chw(const uint8_t* img, int32_t B, int32_t H, int32_t W, int32_t C, float* out, void* stream);
+
+/* ---- K16: split-K first Linear of an MLP over a wide input (csrc/wide_linear.hip) ----------------
+ * a0 = act(x W^T + bias) for x [rows, K] (row pitch ld_x >= K, any alignment: rows that are not 16-B aligned are read with dword
+ * loads), W [H, K] as nn.Linear stores it (row pitch ld_w >= K, any alignment), bias [H] or NULL, activation one of GNC_ACT_*.
+ * Forward, two launches: partial products of [16 rows] x [all H outputs] x [one slice of K] on fp32 MFMA into `workspace`
+ * ([k_slices, rows, H padded to 16]), then a tail launch that sums the slices in ascending order, adds the bias, stores the
+ * pre-activation into z0 (when not NULL: the backward of an activation other than ReLU reads it) and the activation into a0.
+ * Backward, from grad_a0 [rows, H]: dz0 = grad_a0 * act'(.), where `az` is a0 for GNC_ACT_RELU and z0 for every other activation;
+ * dw [H, K] contiguous = dz0^T x, db [H] = column sums of dz0.  Row ranges (dw_parts of dw_row_range rows) are summed in ascending
+ * order through `workspace` (backward_workspace_floats floats, 16-B aligned; may be NULL when that is 0).  The gradient of x is not
+ * formed.  No atomics, no persistent counter, no memset: results are bitwise reproducible and every launch is a kernel node under
+ * stream capture.
+ *
+ * Served: 1 <= rows <= 512 (the batch sizes timed against the row-tiled kernels; larger batches stay with those), 1024 <= K <= 2^26,
+ * 1 <= H <= 256.  gnc_wide_linear_supported answers on the host (no device needed)
+ * for a fused-MLP description, from the same decision the launchers read: 1 when the description is ONE row-ordered matmul segment
+ * (no index, no additive segment, no residual, no aggregation or edge-feature prologue, no save_act) in front of at least two
+ * Linears and its rows, in_dim[0], out_dim[0] are in the set; `plan` (may be NULL) receives the split.  The caller then runs the
+ * first Linear here and the remaining Linears + norm as an ordinary description over a0.  gnc_wide_linear_workspace_floats: floats
+ * of the forward (backward != 0: backward) workspace, -1 outside the set.  The launchers return GNC_ERR_UNSUPPORTED outside the
+ * set before anything is launched.  Added without an ABI bump: a library without these symbols fails the symbol lookup of the
+ * binding. */
+typedef struct gnc_wide_linear_plan {
+  int64_t k_slices, k_slice_len;    /* forward: slices of K and their length (a multiple of 32); the last one may be shorter */
+  int64_t dw_parts, dw_row_range;   /* backward: ranges of rows behind dw / db and their length (a multiple of 16)          */
+  int64_t forward_workspace_floats, backward_workspace_floats;
+} gnc_wide_linear_plan_t;
+int32_t gnc_wide_linear_supported(const gnc_mlp_desc_t* desc, gnc_wide_linear_plan_t* plan);
+int64_t gnc_wide_linear_workspace_floats(int64_t rows, int64_t K, int32_t H, int32_t backward);
+int gnc_wide_linear_forward_f32(const float* x, int64_t ld_x, int64_t rows, int64_t K, const float* w, int64_t ld_w,
+                                const float* bias, int32_t H, int32_t activation, float act_param, float* a0, int64_t ld_a,
+                                float* z0, int64_t ld_z, float* workspace, int64_t workspace_floats, void* stream);
+int gnc_wide_linear_backward_f32(const float* grad_a0, int64_t ld_grad, const float* az, int64_t ld_az, const float* x,
+                                 int64_t ld_x, int64_t rows, int64_t K, int32_t H, int32_t activation, float act_param, float* dw,
+                                 float* db, float* workspace, int64_t workspace_floats, void* stream);
+
 /* ---- fused Adam over flat buffers -------------------------------
  * Replaces `optimizer.step()` of utils/train_model.py:42 for `optim.Adam(model.parameters(), lr=1e-3)` (:9):
  * every parameter is a view of `param` [n], every gradient a view of `grad` [n]; one launch updates all of them
