@@ -799,6 +799,40 @@ __device__ __forceinline__ void hidden_window_store_s(f32x4 v, uint32_t byte_off
     asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" : : "v"(v), "v"(byte_off), "s"(w), "s"(soff) : "memory");
 }
 
+// Tables below 4 GiB with two tiles of slack (the fixed-width instances of the weights-resident kernel; its launcher tests
+// (rows + 64) * ld * 4 < 2^32): ONE loop-invariant window over the whole table serves every tile, and the tile's first row is
+// a 32-bit byte offset - no 64-bit row arithmetic and no per-piece descriptors in the tile loop.  Full tiles carry the piece
+// offset in the SGPR offset field as load_tile_rows does; the last tile carries it in the VGPR offset, which the bounds check
+// sees: rows past the end read as 0 and are never stored (the slack keeps their offsets from wrapping).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_window(const float* base, int rows, int ld) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)((uint32_t)rows * (uint32_t)(ld * 4)), 0x00020000);
+}
+
+template <int PIECES = 8>
+__device__ __forceinline__ void load_tile_rows_w(f32x4 (&pre)[PIECES], __amdgpu_buffer_rsrc_t w, int ld, int row0, int rows, uint32_t lane_off) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const uint32_t voff = lane_off + (uint32_t)row0 * (uint32_t)(ld * 4);
+  if (row0 + 4 * PIECES <= rows) {
+#pragma unroll
+    for (int p = 0; p < PIECES; ++p) pre[p] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(w, voff, p * 16 * ld, 0));
+  } else {
+#pragma unroll
+    for (int p = 0; p < PIECES; ++p) pre[p] = window_load(w, voff + (uint32_t)(p * 16 * ld));
+  }
+}
+
+template <bool NT = false, int PIECES = 8>
+__device__ __forceinline__ void store_tile_rows_w(const f32x4 (&v)[PIECES], __amdgpu_buffer_rsrc_t w, int ld, int row0, int rows, uint32_t lane_off) {
+  const uint32_t voff = lane_off + (uint32_t)row0 * (uint32_t)(ld * 4);
+  if (row0 + 4 * PIECES <= rows) {
+#pragma unroll
+    for (int p = 0; p < PIECES; ++p) hidden_window_store_s<NT>(v[p], voff, w, (uint32_t)(p * 16 * ld));
+  } else {
+#pragma unroll
+    for (int p = 0; p < PIECES; ++p) hidden_window_store(v[p], voff + (uint32_t)(p * 16 * ld), w);  // (default policy, as before)
+  }
+}
+
 // one output row group (declared below)
 __device__ __forceinline__ void store_row_piece(float* rowp, int col, f32x4 v, bool row_ok, int out_dim, bool vec_out);
 

@@ -83,7 +83,10 @@ constexpr int RNT = RWAVES * 64;
 // flag, not a run-time test: the mere presence of the branch cost the inference forward 1.3 % at c3 (same-box A/B).
 // FULL: every width of the launch is exactly 64 (segments, hidden layers, output), three Linear layers, LayerNorm, vector
 // output rows - the c3 edge processor.  The general instance keeps ~40 loop-invariant lane masks (feature / column < width)
-// and the dimensions themselves alive across the tile loop; here they are compile-time constants.
+// and the dimensions themselves alive across the tile loop; here they are compile-time constants.  The plain stacks of c3
+// (one MATMUL step, no ADD segments, no residual) have the same treatment: the encoders, whose only segment is the 3-column
+// one of EF = 1 / EF = 2 (one fp32 k-group), and the same stack on a 64-wide segment.  The decoder (one output tile, no
+// LayerNorm, scalar rows out) keeps the general instance.
 // EF = 1: K6 as the prologue (gnc_mlp_desc_t.ef_pos): the rows of the only segment are computed from the positions of the
 // edge's endpoints (two coalesced id loads one tile ahead, two 8-B gathers per row and tile) instead of being read.
 // DUAL: TWO single-Linear projections of the same rows in one launch (the W-split's node-side products x Ws^T and x Wd^T,
@@ -109,6 +112,15 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int WT = HT > OT ? HT : OT;
   constexpr int CH = WT * 32 * LDSW;  // floats per resident weight chunk
+  static_assert(!FULL || OT == 2, "fixed widths: 64 out");
+  static_assert(!FULL || NADD == 2 || (NMM == 1 && !RESREG && !AGG && !SAVE && !DUAL), "fixed-width plain stacks");
+  constexpr int SEGW = EF != 0 ? 3 : KC;  // FULL: the width of every segment
+  // W32: the FULL inference instances (the training instance keeps its schedule).  By the launcher's tests every row-ordered
+  // table (segment, output) is below 4 GiB with two tiles of slack, so ONE window over the whole table and 32-bit row offsets
+  // serve every tile (mlp_device.h: load_tile_rows_w), and the two ADD segments are gathered.  The MATMUL segment of a RESREG
+  // launch is the residual's table, so it is row-ordered.
+  constexpr bool W32 = FULL && !SAVE;
+  constexpr bool GADD = W32 && NADD == 2;
   static_assert(SPLIT == 0 || (HT == 2 && SPLIT == 1 && NMM == 1 && ((NADD == 2 && RESREG && !DUAL) || (NADD == 0 && !RESREG))) ||
                     (HT == 2 && OT == 2 && SPLIT == 2 && NADD == 0 && !DUAL),
                 "split shapes");
@@ -195,8 +207,12 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
 
   SegView sv[NS];
 #pragma unroll
-  for (int s = 0; s < NS; ++s) sv[s] = {d.seg[s].ptr, d.seg[s].index, d.seg[s].ld, FULL ? KC : d.seg[s].width,
+  for (int s = 0; s < NS; ++s) sv[s] = {d.seg[s].ptr, (W32 && RESREG && s == NMM - 1) ? nullptr : d.seg[s].index, d.seg[s].ld, FULL ? SEGW : d.seg[s].width,
                                           (uint32_t)(d.seg[s].table_rows * d.seg[s].ld * 4)};  // launcher: < 4 GiB
+  if constexpr (GADD) {
+    __builtin_assume(sv[NMM].index != nullptr);
+    __builtin_assume(sv[NMM + 1].index != nullptr);
+  }
 
   // ---- per-wave pipeline -----------------------------------------------------------------------
   const int total_waves = (int)gridDim.x * RWAVES;
@@ -220,7 +236,9 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   auto load_rows = [&](f32x4 (&pre)[NP], const SegView& s, int wt, uint32_t off) {
     const int col = c4 * 4 < s.ld ? c4 * 4 : 0;
     if (s.index == nullptr) {
-      load_tile_rows(pre, s.ptr, s.ld, (int64_t)wt * RPW, rows, (uint32_t)(rs * s.ld + col) * 4u);
+      if constexpr (W32)  // (a prefetch past the last tile is clamped to the tile behind it: reads zeros, offsets stay inside the slack)
+        load_tile_rows_w(pre, table_window(s.ptr, rows, s.ld), s.ld, (wt < num_wtiles ? wt : num_wtiles) * RPW, rows, (uint32_t)(rs * s.ld + col) * 4u);
+      else load_tile_rows(pre, s.ptr, s.ld, (int64_t)wt * RPW, rows, (uint32_t)(rs * s.ld + col) * 4u);
     } else {
       const __amdgpu_buffer_rsrc_t w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s.ptr), 0, (int)s.bytes, 0x00020000);
       const uint32_t row_bytes = off * (uint32_t)(s.ld * 4);  // byte offset of this lane's tile row, once per tile
@@ -369,7 +387,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
         offs[s + 1 < NMM ? s + 1 : 0] = row_offset(nwt, sv[s + 1 < NMM ? s + 1 : 0]);
       } else {
         if constexpr (NADD > 0) {
-          if (sv[s].width == KC && sv[NMM].index && sv[NMM + 1].index) {
+          if (GADD || (sv[s].width == KC && sv[NMM].index && sv[NMM + 1].index)) {
             // Gathered ADD rows requested from INSIDE the first Linear's MFMA loop: LDS / VMEM / scalar
             // instructions of a wave ride in the shadow of its own MFMAs (tools/hw_probe.hip: up to ~4 per MFMA for
             // free), whereas issued in front of the loop they crawl at ~1 per 37 cycles whenever the SIMD mate
@@ -617,20 +635,23 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
           const f32x4 v = *reinterpret_cast<const f32x4*>(abuf + (p * 4 + rs) * LDSW + col_out);
-          if ((keep_rows >> (p * 4 + rs)) & 1u) hidden_window_store<true>(v, out_lane_off, row_window(d.out, row0 + 4 * p, rows, d.ld_out));
+          if ((keep_rows >> (p * 4 + rs)) & 1u)
+            hidden_window_store<true>(v, out_lane_off + (uint32_t)(row0 + 4 * p) * (uint32_t)(d.ld_out * 4), table_window(d.out, rows, d.ld_out));
         }
       }
     } else {
       f32x4 outv[NP];
 #pragma unroll
       for (int p = 0; p < NP; ++p) outv[p] = *reinterpret_cast<const f32x4*>(abuf + (p * 4 + rs) * LDSW + col_out);
-      if (!RESREG && d.residual) {  // rows this tile has just read: L2 hits; rows past the end read as 0
+      if ((!FULL || NADD != 0) && !RESREG && d.residual) {  // rows this tile has just read: L2 hits; rows past the end read as 0
         f32x4 rv[NP];
         load_tile_rows(rv, d.residual, d.ld_residual, row0, rows, res_lane_off);
 #pragma unroll
         for (int p = 0; p < NP; ++p) outv[p] += rv[p];
       }
-      if (vec_out) {  // rows past the end are dropped by the window's bounds check
+      if constexpr (W32) {  // one window over the whole table; rows past the end are dropped by its bounds check
+        store_tile_rows_w<true>(outv, table_window(d.out, rows, d.ld_out), d.ld_out, row0, rows, out_lane_off);
+      } else if (vec_out) {  // rows past the end are dropped by the window's bounds check
         if (col_out < out_dim) {
           if (row0 + RPW <= rows) {
             uint32_t r0b;
@@ -713,7 +734,8 @@ int launch_cls(int split, const gnc_mlp_desc_t& d, int total_chunks, size_t smem
   if constexpr (HT == 2 && NMM == 1 && NADD == 0 && !RESREG && !AGG && !SAVE && !FULL && EF == 0) {
     if (split == 1) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 1>(d, total_chunks, smem, stream);
   }
-  if constexpr (HT == 2 && OT == 2 && NADD == 0 && !AGG && !FULL && ((NMM == 1 && !RESREG) || (NMM == 2 && EF == 0))) {
+  // (FULL: the encoders; a fixed-width stack on a 64-wide segment is no class-2 shape)
+  if constexpr (HT == 2 && OT == 2 && NADD == 0 && !AGG && (!FULL || EF != 0) && ((NMM == 1 && !RESREG) || (NMM == 2 && EF == 0))) {
     if (split == 2) return launch<HT, OT, NMM, NADD, RESREG, AGG, SAVE, FULL, EF, false, 2>(d, total_chunks, smem, stream);
   }
   if (split) return GNC_ERR_UNSUPPORTED;  // a class without its instance: never taken (the launcher's tests below)
@@ -861,16 +883,31 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
   // every width exactly 64, three Linear layers, LayerNorm, whole 16-B output rows: the FULL instances (c3's edge processor)
   static const bool no_full = getenv("GNC_MLP_NO_FULL64") != nullptr;  // A/B switch
   bool full64 = !no_full && L == 3 && od == KC && d.ln_gamma && d.ld_out % 4 == 0 && al16(d.out);
-  for (int s = 0; s < d.num_segments; ++s) full64 = full64 && d.seg[s].width == KC;
+  // (the encoders' only segment is 3 wide by the tests above: computed K6 rows, or the [rows, 3] table)
+  for (int s = 0; s < d.num_segments; ++s) full64 = full64 && (d.seg[s].width == KC || d.ef_pos || n3);
   for (int l = 0; l < L; ++l) full64 = full64 && d.out_dim[l] == KC && (l == 0 || d.in_dim[l] == KC);
+  // The inference instances among them (full32) address every row-ordered table through one 32-bit window with two tiles of
+  // slack and gather their ADD segments; the training instance keeps the 64-bit row paths and needs neither.
+  auto fits32 = [&](int64_t ld) { return (d.rows + 2 * RPW) * ld * 4 <= 0xffffffffll; };
+  bool win32 = fits32(d.ld_out);
+  for (int s = 0; s < d.num_segments; ++s) {
+    const gnc_mlp_segment_t& g = d.seg[s];
+    if (!g.index && !(s == 0 && (d.ef_pos || n3))) win32 = win32 && fits32(g.ld);
+    if (g.mode == GNC_SEG_ADD && !g.index) win32 = false;
+  }
+  const bool full32 = full64 && win32;
+  // the plain stacks (one MATMUL step, no ADD segments, no residual): the encoders and the same stack on a 64-wide segment
+  const bool plain64 = full32 && T == 2 && nmm == 1 && nadd == 0 && !d.residual;
   if (d.ef_pos) {
     *launched = true;
     if (probe_only) return GNC_OK;
+    if (plain64) return launch_cls<2, 2, 1, 0, false, false, false, true, 1>(split, d, total_chunks, smem, stream);
     return launch_cls<2, 2, 1, 0, false, false, false, false, 1>(split, d, total_chunks, smem, stream);
   }
   if (n3) {
     *launched = true;
     if (probe_only) return GNC_OK;
+    if (plain64) return launch_cls<2, 2, 1, 0, false, false, false, true, 2>(split, d, total_chunks, smem, stream);
     return launch_cls<2, 2, 1, 0, false, false, false, false, 2>(split, d, total_chunks, smem, stream);
   }
   if (d.save_act[0]) {
@@ -894,11 +931,11 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
   if (d.agg_out) {  // fused aggregation epilogue: the W-split edge processor shape only
     if (!(nadd == 2 && nmm == 1 && resreg && !narrow_out && d.agg_index && d.agg_fix && d.ld_agg >= od)) return GNC_OK;
     // aggregate-only (gnc_mlp_forward_agg_only_f32): the FULL instance only (c3's edge processor, either class)
-    if (agg_only && !(T == 2 && full64)) return GNC_OK;
+    if (agg_only && !(T == 2 && full32)) return GNC_OK;
     *launched = true;
     if (probe_only) return GNC_OK;
     if (agg_only) return launch_cls<2, 2, 1, 2, true, true, false, true, 0, true>(split, d, total_chunks, smem, stream);
-    if (T == 2 && full64) return launch_cls<2, 2, 1, 2, true, true, false, true>(split, d, total_chunks, smem, stream);
+    if (T == 2 && full32) return launch_cls<2, 2, 1, 2, true, true, false, true>(split, d, total_chunks, smem, stream);
     return T == 2 ? launch_cls<2, 2, 1, 2, true, true>(split, d, total_chunks, smem, stream)
                   : launch<1, 1, 1, 2, true, true>(d, total_chunks, smem, stream);
   }
@@ -921,6 +958,7 @@ int gnc_mlp::launch_resident(const gnc_mlp_desc_t& d, int T, bool narrow_out, hi
     *launched = true;
     if (nadd == 2) return resreg ? launch_cls<2, 2, 1, 2, true>(split, d, total_chunks, smem, stream)
                                  : launch<2, 2, 1, 2, false>(d, total_chunks, smem, stream);
+    if (nmm == 1 && plain64) return launch_cls<2, 2, 1, 0, false, false, false, true>(split, d, total_chunks, smem, stream);
     if (nmm == 1) return resreg ? launch<2, 2, 1, 0, true>(d, total_chunks, smem, stream)
                                 : launch_cls<2, 2, 1, 0, false>(split, d, total_chunks, smem, stream);
     if (nmm == 2) return resreg ? launch_cls<2, 2, 2, 0, true>(split, d, total_chunks, smem, stream)

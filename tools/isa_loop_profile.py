@@ -92,6 +92,10 @@ def main():
     nops = sum(int(args or 0) + 1 for _, op, args, _ in body if op == "s_nop")
     print(f"{found.split('(')[0]}: {len(ins)} instructions, main loop {len(body)} (0x{main_loop[0]:x}..0x{main_loop[1]:x})")
     print("  mix:", dict(sorted(hist.items(), key=lambda kv: -kv[1])), "| s_nop wait states:", nops)
+    # the vector instructions that carry no arithmetic of the result: spill restores, selects, compares
+    detail = collections.Counter(k for _, op, _, _ in body for k in ("v_readlane", "v_writelane", "v_cndmask", "v_cmp") if op.startswith(k))
+    print("  vector detail:", ", ".join(f"{k} {detail[k]}" for k in ("v_readlane", "v_writelane", "v_cndmask", "v_cmp")),
+          f"| s_nop instructions {hist['s_nop']} | vector (valu, no mfma) {hist['valu']}")
     inner = [l for l in loops if main_loop[0] <= l[0] and l[1] <= main_loop[1] and l != main_loop]
     print(f"  inner loops: {len(inner)}")
     if a.waits:
