@@ -326,7 +326,8 @@ class CapturedForward:
     hold ``node_capacity`` node slots in front of the dummies (and at least the read-out's ``num_nodes`` rows); the slots
     behind a sample's own nodes are isolated zero-feature nodes, and inside the graph the read-out takes rows
     ``[0, num_nodes)`` and zeroes those at or behind a device-side count that every call writes in front of the replay -
-    the rule of ``CombinedModel.ragged_readout``.
+    the rule of ``CombinedModel.ragged_readout``.  A pooled ``CombinedModel`` (``readout="mean"`` ...) pools rows
+    ``[0, count)`` instead: its ``graph_ptr`` is the device buffer ``[0, count]`` that holds the count.
     """
 
     def __init__(self, model: nn.Module, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int | None = None,
@@ -336,6 +337,7 @@ class CapturedForward:
         self.model, self.device = model, dev
         self.edge_capacity, self.num_nodes = edge_capacity, int(x.size(0))
         self.node_capacity = node_capacity
+        pooled = isinstance(model, CombinedModel) and model.pooled  # its read-out takes the graph's rows through a device graph_ptr
         if node_capacity is not None:
             if edge_capacity is None:
                 raise ValueError("CapturedForward: node_capacity requires edge_capacity")
@@ -348,8 +350,12 @@ class CapturedForward:
             self.pos = pos.to(device=dev, dtype=torch.float32).clone()
             self.topo = get_topology(edge_index, self.x.size(0), dev)  # host sync happens here, outside the capture
 
+            whole = torch.tensor([0, self.num_nodes], dtype=torch.int64, device=dev) if pooled else None
+
             def run():
                 y = gnet.forward_device(self.x, self.pos, self.topo)
+                if pooled:
+                    return model.readout_logits(y, whole)[0]
                 return model.classifier(y.flatten()) if isinstance(model, CombinedModel) else y
         else:
             n, e = self.num_nodes, int(edge_index.size(1))
@@ -360,7 +366,7 @@ class CapturedForward:
                 raise NotImplementedError("CapturedForward(edge_capacity=...): a BatchNorm model must be in eval() mode")
             dummies = max(1, (edge_capacity + 7) // 8)
             slots = n if node_capacity is None else node_capacity  # node slots in front of the dummies
-            rows = slots + dummies if node_capacity is None else max(slots + dummies, model.num_nodes)
+            rows = slots + dummies if node_capacity is None or pooled else max(slots + dummies, model.num_nodes)
             self.x = torch.zeros(rows, *x.shape[1:], dtype=torch.float32, device=dev)
             self.pos = torch.zeros(rows, *pos.shape[1:], dtype=torch.float32, device=dev)
             self._tail = slots + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies
@@ -371,12 +377,17 @@ class CapturedForward:
             self.topo, self._status = None, None
             self._range_flag = torch.zeros((), dtype=torch.bool, device=dev)
             self._filled = n                                                        # rows of x / pos that hold a sample
-            self.valid_nodes = torch.full((), n, dtype=torch.int64, device=dev)    # read inside the graph (node_capacity form)
+            # [0, n]: a pooled read-out's graph_ptr; its second entry is the node count every call writes in front of the replay
+            # (node_capacity form).  ONE persistent buffer read inside the graph: nothing is concatenated in there.
+            self._graph_ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
+            self.valid_nodes = self._graph_ptr[1]
 
             def run():
                 topo = GraphTopology(self.edge_index, rows, device=dev, validate="deferred")  # never the cache
                 self._status = topo.status  # the capture's own flags: every replay rewrites them
                 y = gnet.forward_device(self.x, self.pos, topo)
+                if pooled:  # rows [0, valid_nodes): the slots behind them and the dummies are outside the graph
+                    return model.readout_logits(y, self._graph_ptr)[0]
                 if node_capacity is not None:
                     return model.classifier(masked_readout_rows(y, model.num_nodes, self.valid_nodes).flatten())
                 y = y[:n]
@@ -597,18 +608,71 @@ class LinearClassifier(nn.Module):
 
 
 class CombinedModel(nn.Module):
-    def __init__(self, graph_net: GraphNet | None = None, num_nodes: int = 128 * 128, classes: int = 2):
-        """models/GNN.py:327-332."""
+    READOUTS = ("flatten", "mean", "max", "sum", "hybrid")
+
+    def __init__(self, graph_net: GraphNet | None = None, num_nodes: int = 128 * 128, classes: int = 2, *, readout: str = "flatten"):
+        """models/GNN.py:327-332.  ``readout="flatten"`` is the reference's model: ``fc1`` over the ``num_nodes * out_dim`` flattened
+        node outputs.  ``"mean"`` / ``"max"`` / ``"sum"`` / ``"hybrid"``: a global pooling read-out (the one the reference's write-up
+        describes; K17) hands ONE vector per graph - ``out_dim`` wide, ``3 * out_dim`` for ``hybrid`` = [mean | max | sum] - to the
+        same three-layer classifier.  It is permutation invariant and defined for every node count; ``num_nodes`` is kept but
+        sizes nothing.  Same ``state_dict`` keys either way; ``readout`` is not stored in it."""
         super().__init__()
+        if readout not in self.READOUTS:
+            raise ValueError(f"CombinedModel: readout {readout!r} is not one of {self.READOUTS}")
         self.graph_net = graph_net if graph_net is not None else GraphNet()
         self.num_nodes = num_nodes
-        in_features = num_nodes * self.graph_net.out_dim
+        self.readout = readout
+        if readout == "flatten":
+            in_features = num_nodes * self.graph_net.out_dim
+        else:
+            in_features = (3 if readout == "hybrid" else 1) * self.graph_net.out_dim
         self.classifier = LinearClassifier(in_features=in_features, classes=classes)
-        # True: ``forward`` accepts a graph of any node count N and feeds fc1 rows [0, min(N, num_nodes)) of the GraphNet
-        # output, the rest of the vector zero (forward_batched(graph_ptr=...)'s rule; the reference's read-out is only
-        # defined for N == num_nodes).  A plain attribute, not a constructor argument and not in the state_dict.
-        self.ragged_readout = False
+        # True: ``forward`` accepts a graph of any node count N.  On the flatten model (off by default; a plain attribute, not a
+        # constructor argument and not in the state_dict) it feeds fc1 rows [0, min(N, num_nodes)) of the GraphNet output, the rest
+        # of the vector zero (forward_batched(graph_ptr=...)'s rule; the reference's read-out is only defined for
+        # N == num_nodes).  A pooled model accepts any node count by construction and answers True.
+        self.ragged_readout = readout != "flatten"
         self.to(next(self.graph_net.parameters()).device)
+
+    @property
+    def pooled(self) -> bool:
+        return self.readout != "flatten"
+
+    def readout_logits(self, y: Tensor, graph_ptr: Tensor | None, num_graphs: int | None = None) -> Tensor:
+        """The read-out behind the GraphNet: logits [G, classes] from the node outputs ``y`` [rows, out_dim] and a DEVICE int64
+        ``graph_ptr`` [G + 1] (``None`` on the flatten model: ``num_graphs`` graphs of exactly ``num_nodes`` rows).  Rows outside
+        the graphs are ignored and get zero gradient.  No host synchronisation: every caller - ``forward``, the batched forms, the
+        captured forwards and steps - comes through here with a pooled model."""
+        fc1, fc2, fc3 = self.classifier.fc1, self.classifier.fc2, self.classifier.fc3
+        od = self.graph_net.out_dim
+        gp = graph_ptr
+        if gp is not None:
+            num_graphs = gp.numel() - 1
+        if self.pooled:
+            feats = Fn.graph_pool(y, gp, self.readout)  # [G, F]
+            if num_graphs == 1:
+                return self.classifier(feats[0]).unsqueeze(0)  # the single-graph launch (csrc/readout.hip)
+            if READOUT_HIP and native.readout_batched_supported(num_graphs, feats.size(1), fc1.out_features, fc2.out_features,
+                                                                fc3.out_features):
+                # K13 over the pooled matrix: G "graphs" of one node with F outputs each
+                return Fn.readout_batched(feats, None, num_graphs, 1, fc1.weight, fc1.bias, fc2.weight, fc2.bias, fc3.weight, fc3.bias)
+            return self.classifier(feats)
+        if (READOUT_HIP and num_graphs >= 1 and y.dtype == torch.float32 and fc1.in_features == self.num_nodes * od
+                and native.readout_batched_supported(num_graphs, fc1.in_features, fc1.out_features, fc2.out_features,
+                                                     fc3.out_features)):
+            # the gather rule below fused into fc1's operand load, fc1 on MFMA, fc2 / fc3 from LDS (csrc/readout_batched.hip);
+            # a shape the library does not take stays on the torch path
+            return Fn.readout_batched(y, gp, num_graphs, self.num_nodes, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                                      fc3.weight, fc3.bias)
+        if gp is None:
+            feats = y.view(num_graphs, -1)
+        else:
+            start, size = gp[:-1], gp[1:] - gp[:-1]
+            k = torch.arange(self.num_nodes, device=y.device)
+            valid = k[None, :] < size[:, None]                                   # [G, num_nodes]
+            rows = (start[:, None] + k[None, :]).clamp_(max=max(y.size(0) - 1, 0))
+            feats = (y[rows] * valid[..., None]).reshape(gp.numel() - 1, self.num_nodes * od)
+        return self.classifier(feats)
 
     def forward(self, x, pos=None, edge_index=None):
         """models/GNN.py:334-341; accepts the (x, pos, edge_index) tuple; logits are 1-D [classes]."""
@@ -620,6 +684,9 @@ class CombinedModel(nn.Module):
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
         y = self.graph_net.forward_device(x, pos, topo)
+        if self.pooled:
+            logits = self.readout_logits(y, torch.arange(2, dtype=torch.int64, device=dev) * y.size(0))[0]  # [0, N], built on the device
+            return logits if back == dev else logits.to(back)
         if self.ragged_readout and y.size(0) != self.num_nodes:
             y = ragged_readout_rows(y, self.num_nodes)  # full num_nodes * out_dim length: dW1 keeps fc1.weight's layout
         logits = self.classifier(y.flatten())
@@ -655,26 +722,7 @@ class CombinedModel(nn.Module):
         either ``num_graphs`` (graph g owns rows ``[g * num_nodes, (g + 1) * num_nodes)``) or a DEVICE int64 ``graph_ptr``
         [G + 1].  ``x`` may hold more rows than the graphs own (the padded buffers of a captured ragged-batch step: slack and
         dummy rows behind ``graph_ptr[-1]``): the read-out takes rows through ``graph_ptr`` only.  No host synchronisation."""
-        dev = x.device
         y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
-        od = self.graph_net.out_dim
-        gp = graph_ptr
-        if gp is not None:
-            num_graphs = gp.numel() - 1
-        fc1, fc2, fc3 = self.classifier.fc1, self.classifier.fc2, self.classifier.fc3
-        if (READOUT_HIP and num_graphs >= 1 and y.dtype == torch.float32 and fc1.in_features == self.num_nodes * od
-                and native.readout_batched_supported(num_graphs, fc1.in_features, fc1.out_features, fc2.out_features,
-                                                     fc3.out_features)):
-            # the gather rule below fused into fc1's operand load, fc1 on MFMA, fc2 / fc3 from LDS (csrc/readout_batched.hip);
-            # a shape the library does not take stays on the torch path
-            return Fn.readout_batched(y, gp, num_graphs, self.num_nodes, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
-                                      fc3.weight, fc3.bias)
-        if gp is None:
-            feats = y.view(num_graphs, -1)
-        else:
-            start, size = gp[:-1], gp[1:] - gp[:-1]
-            k = torch.arange(self.num_nodes, device=dev)
-            valid = k[None, :] < size[:, None]                                   # [G, num_nodes]
-            rows = (start[:, None] + k[None, :]).clamp_(max=max(y.size(0) - 1, 0))
-            feats = (y[rows] * valid[..., None]).reshape(gp.numel() - 1, self.num_nodes * od)
-        return self.classifier(feats)
+        if self.pooled and graph_ptr is None:  # the num_graphs form: graph g owns rows [g * num_nodes, (g + 1) * num_nodes)
+            graph_ptr = torch.arange(num_graphs + 1, dtype=torch.int64, device=x.device) * self.num_nodes
+        return self.readout_logits(y, graph_ptr, num_graphs)

@@ -654,6 +654,35 @@ def readout_batched(y, graph_ptr, num_graphs, num_nodes, w1, b1, w2, b2, w3, b3)
     return _ReadoutBatched.apply(y, graph_ptr, int(num_graphs), int(num_nodes), w1, b1, w2, b2, w3, b3)
 
 
+class _GraphPool(torch.autograd.Function):
+    """Global pooling read-out over the graphs of a block-diagonal batch (csrc/pool_readout.hip, K17): one launch (two for a few
+    large graphs) forward, one streaming launch backward."""
+
+    @staticmethod
+    def forward(ctx, y, graph_ptr, modes):
+        out, argmax = native.graph_pool_forward(y, graph_ptr, modes)
+        ctx.save_for_backward(graph_ptr, *([argmax] if argmax is not None else []))
+        ctx.modes, ctx.rows = modes, y.size(0)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        graph_ptr, *rest = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return native.graph_pool_backward(grad, ctx.modes, rest[0] if rest else None, graph_ptr, ctx.rows), None, None
+
+
+def graph_pool(y: torch.Tensor, graph_ptr: torch.Tensor, mode: str) -> torch.Tensor:
+    """Permutation-invariant read-out: ``y`` [rows, C] float32 on the GPU, ``graph_ptr`` int64 [G + 1] on the same device (graph g
+    owns rows ``[graph_ptr[g], graph_ptr[g + 1])``; rows outside the graphs are ignored and receive zero gradient).  ``mode``
+    ``"mean"`` / ``"max"`` / ``"sum"`` -> [G, C]; ``"hybrid"`` -> ``cat([mean, max, sum], dim=1)`` [G, 3C] from one pass.  An empty
+    graph pools to zeros; the maximum's gradient goes to the lowest row that holds it."""
+    if mode not in native.POOL_MODES:
+        raise ValueError(f"graph_pool: mode {mode!r} is not one of {sorted(native.POOL_MODES)}")
+    return _GraphPool.apply(y, graph_ptr, native.POOL_MODES[mode])
+
+
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """[pos[dst]-pos[src], L1 norm] per edge (models/GNN.py:299-302).  ``pos`` is input data
     (utils/dataloader.py:50); gradients with respect to it are not provided."""

@@ -137,6 +137,11 @@ _SIGNATURES = {
                                             c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "gnc_bn_fold_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32,
                                   c_void_p, c_int64, c_void_p, c_void_p]),
+    "gnc_graph_pool_plan": (c_int32, [c_int64, c_int64, c_int64, c_void_p]),
+    "gnc_graph_pool_forward_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_int64, c_void_p, c_int64, c_void_p]),
+    "gnc_graph_pool_backward_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                              c_void_p]),
     "gnc_adam_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p]),
 }
@@ -184,6 +189,11 @@ class XtyJob(Structure):
 class ReadoutBatchedPlan(Structure):
     _fields_ = [(name, c_int64) for name in ("f_slices", "f_slice_len", "tail_rows", "small_parts", "dw1_parts", "dw1_graph_range",
                                               "dy_groups", "forward_workspace_floats", "backward_workspace_floats")]
+
+
+class GraphPoolPlan(Structure):
+    _fields_ = [(name, c_int64) for name in ("chunk_rows", "split", "slots", "vec", "col_lanes", "row_lanes", "col_tiles",
+                                              "workspace_floats")]
 
 
 class WideLinearPlan(Structure):
@@ -838,6 +848,85 @@ def readout_batched_backward(grad_logits, y, graph_ptr, num_graphs: int, num_nod
                        4.0 * G * w1.numel()), "gnc_readout_batched_backward_f32")
     dw2, db2, dw3, db3, db1 = small.split([H2 * H1, H2, C * H2, C, H1])
     return dy, dw1, db1, dw2.view(H2, H1), db2, dw3.view(C, H2), db3
+
+
+# --------------------------------------------------------------------------- K17: global pooling read-out
+POOL_SUM, POOL_MEAN, POOL_MAX = 1, 2, 4
+POOL_MODES = {"sum": POOL_SUM, "mean": POOL_MEAN, "max": POOL_MAX, "hybrid": POOL_SUM | POOL_MEAN | POOL_MAX}
+
+
+def graph_pool_plan(rows: int, width: int, num_graphs: int) -> dict | None:
+    """The library's decision for pooling ``num_graphs`` graphs out of ``rows`` rows of ``width`` columns (host only, no GPU
+    needed): None outside the served set, otherwise ``chunk_rows`` (the chunk length of the fixed summation order), ``split`` (0:
+    one workgroup per graph and column tile; 1: few large graphs, one workgroup per chunk and a merge launch), the workgroup's
+    tiling and ``workspace_floats``."""
+    plan = GraphPoolPlan()
+    if not load_library().gnc_graph_pool_plan(int(rows), int(width), int(num_graphs), ctypes.byref(plan)):
+        return None
+    return {name: int(getattr(plan, name)) for name, _ in GraphPoolPlan._fields_}
+
+
+def _pool_graph_ptr(graph_ptr: torch.Tensor, dev) -> torch.Tensor:
+    if graph_ptr.dtype != torch.int64 or graph_ptr.device != dev or graph_ptr.dim() != 1 or graph_ptr.numel() < 2:
+        raise ValueError("graph_pool: graph_ptr must be int64 [num_graphs + 1] (num_graphs >= 1) on the device of y")
+    return graph_ptr.contiguous()
+
+
+def graph_pool_forward(y: torch.Tensor, graph_ptr: torch.Tensor, modes: int):
+    """One pass over ``y`` [rows, C] (float32): for the graphs ``graph_ptr`` (DEVICE int64 [G + 1], never read on the host) names,
+    the outputs the ``POOL_*`` bits of ``modes`` ask for.  Returns ``(out, argmax)``: ``out`` [G, k C] holds the wanted blocks in
+    the order mean | max | sum (``hybrid``'s layout), ``argmax`` int32 [G, C] row indices into ``y`` (None without ``POOL_MAX``).
+    An empty graph pools to +0.0 / argmax -1; rows outside the graphs are ignored."""
+    lib = load_library()
+    _require_cuda(y, graph_ptr)
+    y = _rowmajor(y).contiguous()
+    dev, rows, C = y.device, y.size(0), y.size(1)
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    plan = graph_pool_plan(rows, C, G)
+    if plan is None or not modes or modes & ~(POOL_SUM | POOL_MEAN | POOL_MAX):
+        raise RuntimeError(f"graph_pool_forward: rows {rows} / width {C} / graphs {G} / modes {modes} outside the kernel's set")
+    order = [m for m in (POOL_MEAN, POOL_MAX, POOL_SUM) if modes & m]
+    out = torch.empty(G, len(order) * C, dtype=torch.float32, device=dev)
+    block = {m: out[:, k * C:(k + 1) * C] for k, m in enumerate(order)}
+    argmax = torch.empty(G, C, dtype=torch.int32, device=dev) if modes & POOL_MAX else None
+    ws = torch.empty(max(plan["workspace_floats"], 1), dtype=torch.float32, device=dev)
+    ptr = lambda m: block[m].data_ptr() if m in block else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _check(_launch("graph_pool_forward", y,
+                       lambda: lib.gnc_graph_pool_forward_f32(y.data_ptr(), rows, C, gp.data_ptr(), G, modes, ptr(POOL_SUM), ptr(POOL_MEAN),
+                                                              ptr(POOL_MAX), argmax.data_ptr() if argmax is not None else None,
+                                                              out.size(1), ws.data_ptr(), ws.numel(), _stream(y)),
+                       float(rows * C)), "gnc_graph_pool_forward_f32")
+    return out, argmax
+
+
+def graph_pool_backward(grad: torch.Tensor, modes: int, argmax: torch.Tensor | None, graph_ptr: torch.Tensor, rows: int):
+    """``dy`` [rows, C] of ``graph_pool_forward``: ``grad`` [G, k C] in the forward's block order (mean | max | sum).  Every row is
+    written; rows of no graph get exact zeros."""
+    lib = load_library()
+    _require_cuda(grad, graph_ptr)
+    grad = _rowmajor(grad).contiguous()
+    dev = grad.device
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    order = [m for m in (POOL_MEAN, POOL_MAX, POOL_SUM) if modes & m]
+    if not order or grad.size(0) != G or grad.size(1) % len(order):
+        raise ValueError(f"graph_pool_backward: grad {tuple(grad.shape)} does not hold {len(order)} blocks for {G} graphs")
+    C = grad.size(1) // len(order)
+    if modes & POOL_MAX and (argmax is None or argmax.shape != (G, C) or argmax.dtype != torch.int32 or not argmax.is_contiguous()):
+        raise ValueError("graph_pool_backward: argmax must be the forward's int32 [G, C]")
+    if graph_pool_plan(rows, C, G) is None:
+        raise RuntimeError(f"graph_pool_backward: rows {rows} / width {C} / graphs {G} outside the kernel's set")
+    dy = torch.empty(int(rows), C, dtype=torch.float32, device=dev)
+    block = {m: grad.data_ptr() + 4 * k * C for k, m in enumerate(order)}
+    with torch.cuda.device(dev):
+        _check(_launch("graph_pool_backward", grad,
+                       lambda: lib.gnc_graph_pool_backward_f32(block.get(POOL_SUM), block.get(POOL_MEAN), block.get(POOL_MAX), grad.size(1),
+                                                               argmax.data_ptr() if modes & POOL_MAX else None, gp.data_ptr(), G,
+                                                               int(rows), C, dy.data_ptr(), _stream(grad)),
+                       float(rows * C)), "gnc_graph_pool_backward_f32")
+    return dy
 
 
 # --------------------------------------------------------------------------- K16: split-K first Linear of a wide-input MLP

@@ -188,7 +188,9 @@ class CapturedTrainStep:
     the dummies (and at least the read-out's ``num_nodes`` rows); slots behind a sample's own nodes are isolated zero nodes,
     and the captured read-out takes rows ``[0, num_nodes)`` and zeroes those at or behind the device count ``valid_nodes``
     that every call writes in front of the replay (``GNN.masked_readout_rows``), so unused rows contribute exact zeros to
-    the logits and to every gradient, as the dummies do.  A custom ``forward`` reads ``valid_nodes`` itself."""
+    the logits and to every gradient, as the dummies do.  A pooled ``CombinedModel`` (``readout="mean"`` ...) pools rows
+    ``[0, valid_nodes)`` instead, through ``readout_logits`` with the device buffer ``[0, valid_nodes]`` as ``graph_ptr``.  A
+    custom ``forward`` reads ``valid_nodes`` itself."""
 
     def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, sample, label, loss_sum: torch.Tensor, *,
                  forward=None, loss_scale: float = 1.0, capture_error_mode: str = "global", edge_capacity: int | None = None,
@@ -211,6 +213,7 @@ class CapturedTrainStep:
         self.label = torch.as_tensor(label).to(dev).clone()
         self.loss_sum = loss_sum
         self.collective_outside = _world(fp.reducer.group) > 1
+        pooled = forward is None and bool(getattr(model, "pooled", False))  # a CombinedModel with a pooling read-out (K17)
         from .GNN import masked_readout_rows
         from .topology import GraphTopology, get_topology
         if edge_capacity is None:
@@ -240,8 +243,8 @@ class CapturedTrainStep:
             dummies = max(1, (edge_capacity + 7) // 8)
             slots = n if node_capacity is None else node_capacity  # node slots in front of the dummies
             rows = slots + dummies
-            if node_capacity is not None and hasattr(model, "num_nodes"):
-                rows = max(rows, int(model.num_nodes))  # the read-out takes rows [0, num_nodes)
+            if node_capacity is not None and hasattr(model, "num_nodes") and not pooled:
+                rows = max(rows, int(model.num_nodes))  # the flatten read-out takes rows [0, num_nodes)
             self.x = torch.zeros(rows, *x.shape[1:], dtype=torch.float32, device=dev)
             self.pos = torch.zeros(rows, *pos.shape[1:], dtype=torch.float32, device=dev)
             self._tail = slots + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies  # slot k's dummy self-loop
@@ -252,12 +255,17 @@ class CapturedTrainStep:
             self.topo, self._status = None, None
             self._range_flag = torch.zeros((), dtype=torch.bool, device=dev)
             self._filled = n                                                        # rows of x / pos that hold a sample
-            self.valid_nodes = torch.full((), n, dtype=torch.int64, device=dev)    # read inside the graph (node_capacity form)
+            # [0, n]: a pooled read-out's graph_ptr; its second entry is the node count every call writes in front of the replay
+            # (node_capacity form).  ONE persistent buffer read inside the graph: nothing is concatenated in there.
+            self._graph_ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
+            self.valid_nodes = self._graph_ptr[1]
 
             def padded_forward(mod, xx, pp, ee):
                 topo = GraphTopology(ee, xx.size(0), device=dev, validate="deferred")  # never the cache: built in every step
                 self._status = topo.status  # the capture's own flags: every replay rewrites them
                 y = mod.graph_net.forward_device(xx, pp, topo)
+                if pooled:  # graph_ptr = [0, valid_nodes]: slots behind the sample's nodes and the dummies get zero gradient
+                    return mod.readout_logits(y, self._graph_ptr)[0]
                 if node_capacity is not None:
                     return mod.classifier(masked_readout_rows(y, mod.num_nodes, self.valid_nodes).flatten())
                 return mod.classifier(y[:n].flatten())

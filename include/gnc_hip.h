@@ -586,6 +586,47 @@ int gnc_pad_graph_batch(const float* x, int32_t fx, const float* pos, int32_t fp
                         int64_t edge_capacity, float* x_buf, float* pos_buf, int64_t* ei_buf, int64_t* graph_ptr_buf,
                         int64_t* labels_buf, int32_t* flag, void* stream);
 
+/* ---- K17: global pooling read-out (csrc/pool_readout.hip) ----------------------------
+ * Per graph g of a block-diagonal batch - rows [graph_ptr[g], graph_ptr[g + 1]) of `y` [rows, C] (float32, contiguous) - the column
+ * sums, means (sum / float(n), a true fp32 division), maxima and the row index INTO y of each maximum.  `graph_ptr`: DEVICE int64
+ * [num_graphs + 1], non-decreasing, never read on the host; rows outside [graph_ptr[0], graph_ptr[G]) (the slack and dummy rows
+ * of a padded capture buffer) belong to no graph.  Offsets outside [0, rows] read as shorter or empty graphs, never outside y.
+ * `modes`: GNC_POOL_* bits; exactly the outputs it names are non-NULL (argmax comes with max): psum / pmean / pmax [G, C] with row
+ * pitch ld_out >= C (three column blocks of one [G, 3C] matrix, for instance), argmax int32 [G, C] contiguous.  Everything wanted
+ * comes from ONE pass over y.
+ *
+ * Rules: an empty graph gives +0.0 everywhere and argmax -1; ties of the maximum go to the LOWEST row, -0.0 == +0.0; a NaN makes
+ * its column's maximum NaN with argmax at the first NaN row and its sum NaN.  No atomics, no persistent counter, no memset: every
+ * launch is a kernel node under stream capture.  The summation order depends on the graph's OWN rows and on C alone (chunks of
+ * `chunk_rows` rows counted from the graph's first row, a fixed tree inside a chunk, ascending chunk order across): a graph pooled
+ * alone and inside any batch gives the same bits, as do two runs.
+ *
+ * gnc_graph_pool_plan (host only, no device needed; 1 = served: rows < 2^31, 1 <= C <= 2^20, num_graphs >= 1) says which of two
+ * regimes a launch takes, from rows / C / num_graphs alone - same bits either way: split == 0, one workgroup per (graph, column
+ * tile); split == 1 (few large graphs), one workgroup per (chunk, column tile) writes partials into `workspace`
+ * (`workspace_floats` floats, 4-B aligned, owned by the call) and a second launch folds them per graph in chunk order.
+ *
+ * Backward: dy [rows, C] contiguous, EVERY row written: dy[r, c] = dsum[g, c] + dmean[g, c] / float(n) + (argmax[g, c] == r ?
+ * dmax[g, c] : 0) for a row r of a graph g with n rows (the terms whose pointer is NULL left out; a lone term is copied bit for
+ * bit), exact zeros for rows of no graph.  dsum / dmean / dmax [G, C] share the row pitch ld_grad.  Added without an ABI bump: a
+ * library without these symbols fails the symbol lookup of the binding. */
+#define GNC_POOL_SUM 1
+#define GNC_POOL_MEAN 2
+#define GNC_POOL_MAX 4
+typedef struct gnc_graph_pool_plan {
+  int64_t chunk_rows;                              /* rows per chunk of the summation order                              */
+  int64_t split;                                   /* 0: one workgroup per (graph, column tile); 1: per (chunk, tile) + merge */
+  int64_t slots;                                   /* split: workspace slots = rows / chunk_rows + num_graphs            */
+  int64_t vec, col_lanes, row_lanes, col_tiles;    /* the workgroup's tiling of [rows] x [columns], a function of C alone */
+  int64_t workspace_floats;                        /* split: 3 * slots * C, otherwise 0                                  */
+} gnc_graph_pool_plan_t;
+int32_t gnc_graph_pool_plan(int64_t rows, int64_t C, int64_t num_graphs, gnc_graph_pool_plan_t* plan);
+int gnc_graph_pool_forward_f32(const float* y, int64_t rows, int64_t C, const int64_t* graph_ptr, int64_t num_graphs, int32_t modes,
+                               float* psum, float* pmean, float* pmax, int32_t* argmax, int64_t ld_out, float* workspace,
+                               int64_t workspace_floats, void* stream);
+int gnc_graph_pool_backward_f32(const float* dsum, const float* dmean, const float* dmax, int64_t ld_grad, const int32_t* argmax,
+                                const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, int64_t C, float* dy, void* stream);
+
 /* ---- graph construction on the device ---------------------------
  * Inputs: an already resized uint8 RGB image [H, W, C] in HBM.  Outputs: the tensors
  * utils/dataloader.py:49-51 builds (x, pos float32; edge_index int64 [2, E] row-major), in the
