@@ -60,6 +60,52 @@ def scatter_sum(src: Tensor, index: Tensor, dim: int = 0, dim_size: int | None =
     return out if out_device == dev else out.to(out_device)
 
 
+def _scatter_args(who: str, src: Tensor, index: Tensor, dim: int, dim_size: int | None):
+    """The argument handling ``scatter_sum`` has, for its mean / max siblings: (src [E, D] on the GPU, csr, dim_size, the device
+    the result goes back to, the device it is computed on)."""
+    if dim != 0:
+        raise NotImplementedError(f"fallback {who} currently supports dim=0 only")
+    if src.ndim == 1:
+        src = src.unsqueeze(-1)
+    if dim_size is None:
+        dim_size = int(index.max().item()) + 1 if index.numel() > 0 else 0
+    dev = src.device if src.is_cuda else default_device()
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: no GPU visible and no CPU fallback exists")
+    out_device = src.device
+    csr = get_destination_csr(index, dim_size, dev)
+    return src.to(device=dev, dtype=torch.float32), csr, dim_size, out_device, dev
+
+
+def scatter_mean(src: Tensor, index: Tensor, dim: int = 0, dim_size: int | None = None) -> Tensor:
+    """``scatter_sum``'s sibling (same signature, argument handling and errors): out[v] = mean of the ``src`` rows with
+    ``index == v`` - their sum in row order divided by their count - and +0.0 for a ``v`` without rows (K18)."""
+    src, csr, dim_size, out_device, dev = _scatter_args("scatter_mean", src, index, dim, dim_size)
+    out = Fn.segment_mean_csr(src, csr.rowptr, csr.perm, csr.col32 if src.requires_grad else None, dim_size)
+    return out if out_device == dev else out.to(out_device)
+
+
+def scatter_max(src: Tensor, index: Tensor, dim: int = 0, dim_size: int | None = None) -> tuple[Tensor, Tensor]:
+    """``(out, argmax)``: out[v] = column-wise maximum of the ``src`` rows with ``index == v``, +0.0 for a ``v`` without rows; a
+    NaN wins its column; ``-0.0 == +0.0``.  ``argmax`` [dim_size, D] int64 is the row of ``src`` that holds each maximum - the
+    LOWEST such row on a tie - and -1 for a ``v`` without rows (torch_scatter's ``scatter_max`` puts ``src.size(0)`` there
+    instead).  The gradient of a column goes to that row alone (K18)."""
+    src, csr, dim_size, out_device, dev = _scatter_args("scatter_max", src, index, dim, dim_size)
+    out, argmax = Fn.segment_max_csr(src, csr.rowptr, csr.perm, csr.col32 if src.requires_grad else None, dim_size,
+                                     return_argmax=True)
+    argmax = argmax.long()
+    return (out, argmax) if out_device == dev else (out.to(out_device), argmax.to(out_device))
+
+
+AGGREGATIONS = ("sum", "mean", "max")
+
+
+def _check_aggregation(aggregation, who: str) -> str:
+    if aggregation not in AGGREGATIONS:
+        raise ValueError(f"{who}: aggregation {aggregation!r} is not one of {AGGREGATIONS}")
+    return aggregation
+
+
 # --------------------------------------------------------------------------- a3 EdgeProcessor
 def _poison_if_deferred(topo: GraphTopology, out: Tensor) -> Tensor:
     """Deferred validation (topology.set_validation): the topology's out-of-range flags have not been read back, and the
@@ -121,9 +167,13 @@ class EdgeProcessor(nn.Module):
 # --------------------------------------------------------------------------- a2 NodeProcessor
 class NodeProcessor(nn.Module):
     def __init__(self, in_dim_node: int, in_dim_edge: int, hidden_dim: int = 128, hidden_layers: int = 2,
-                 activation: str = "ReLU", initializer: None | str = None, norm_type: None | str = "LayerNorm"):
-        """models/GNN.py:69-93."""
+                 activation: str = "ReLU", initializer: None | str = None, norm_type: None | str = "LayerNorm",
+                 aggregation: str = "sum"):
+        """models/GNN.py:69-93.  ``aggregation``: how the incoming edge latents of a node are reduced - ``"sum"`` (the reference's
+        code), ``"mean"`` (the reference's write-up) or ``"max"`` (K18).  A plain attribute: no parameter, no buffer, not in the
+        ``state_dict``."""
         super().__init__()
+        self.aggregation = _check_aggregation(aggregation, "NodeProcessor")
         self.node_processor = MLP(in_dim_node + in_dim_edge, in_dim_node, hidden_dim, hidden_layers, activation,
                                   initializer, norm_type)
 
@@ -133,14 +183,24 @@ class NodeProcessor(nn.Module):
         back = x.device
         x, edge_attr = (t.to(device=dev, dtype=torch.float32) for t in (x, edge_attr))
         topo = get_topology(edge_index, x.size(0), dev)
-        agg = Fn.scatter_sum_csr(edge_attr, topo.rowptr, topo.perm, topo.col32, topo.num_nodes)
+        agg = self._aggregate(edge_attr, topo, topo.perm, topo.col32)
         out = _poison_if_deferred(topo, self.node_processor.forward_segments([(x, None), (agg, None)], residual=x))
         return out if back == dev else out.to(back)
 
+    def _aggregate(self, edge_attr: Tensor, topo: GraphTopology, perm, dst_of_row, sums: Tensor | None = None) -> Tensor:
+        """The [N, De] aggregate of ``edge_attr`` by ``self.aggregation``.  ``sums``: the per-destination SUMS where the edge
+        launch's epilogue has formed them already (sum and mean; the max has no use for them)."""
+        if self.aggregation == "max":  # the winners' rows are kept only under autograd
+            return Fn.segment_max_csr(edge_attr, topo.rowptr, perm, dst_of_row, topo.num_nodes)
+        if sums is None:
+            sums = Fn.scatter_sum_csr(edge_attr, topo.rowptr, perm, dst_of_row, topo.num_nodes)
+        if self.aggregation == "mean":  # the sum machinery unchanged, then one launch over N rows: segment_mean_csr's bits
+            return Fn.div_by_degree(sums, topo.rowptr, inplace=True)
+        return sums
+
     def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor, agg: Tensor | None = None) -> Tensor:
         """``agg`` given: the per-destination sums already formed by the edge launch's epilogue."""
-        if agg is None:
-            agg = Fn.scatter_sum_csr(edge_attr, topo.rowptr, None, topo.dst_sorted, topo.num_nodes)
+        agg = self._aggregate(edge_attr, topo, None, topo.dst_sorted, agg)
         return self.node_processor.forward_segments([(x, None), (agg, None)], residual=x)
 
 
@@ -178,8 +238,10 @@ class MetaLayer(nn.Module):
         if self.edge_model is not None:
             # let the edge launch form the node model's aggregate in its epilogue; with autograd on the
             # W-split Function returns both outputs and folds the aggregate's gradient (a gather) into e''s
+            # (a max aggregation has no epilogue inside the MFMA kernels: the edge launch stores e' and K18 reduces it)
             if (FUSED_AGG and self.node_model is not None
-                    and isinstance(self.edge_model, EdgeProcessor) and isinstance(self.node_model, NodeProcessor)):
+                    and isinstance(self.edge_model, EdgeProcessor) and isinstance(self.node_model, NodeProcessor)
+                    and self.node_model.aggregation != "max"):
                 edge_attr, agg = self.edge_model.forward_sorted(x, topo, edge_attr, aggregate=True, need_edges=need_edges)
             else:
                 edge_attr = self.edge_model.forward_sorted(x, topo, edge_attr)
@@ -193,13 +255,14 @@ class MetaLayer(nn.Module):
 
 def build_GN_block(in_dim_node: int, in_dim_edge: int, hidden_dim_node: int = 128, hidden_dim_edge: int = 128,
                    hidden_layers_node: int = 2, hidden_layers_edge: int = 2, activation: str = "ReLU",
-                   initializer: None | str = None, norm_type: None | str = "LayerNorm"):
-    """models/GNN.py:110-165."""
+                   initializer: None | str = None, norm_type: None | str = "LayerNorm", aggregation: str = "sum"):
+    """models/GNN.py:110-165; ``aggregation`` goes to the block's ``NodeProcessor``."""
+    _check_aggregation(aggregation, "build_GN_block")
     return MetaLayer(
         edge_model=EdgeProcessor(in_dim_node, in_dim_edge, hidden_dim_edge, hidden_layers_edge, activation,
                                  initializer, norm_type),
         node_model=NodeProcessor(in_dim_node, in_dim_edge, hidden_dim_node, hidden_layers_node, activation,
-                                 initializer, norm_type),
+                                 initializer, norm_type, aggregation=aggregation),
     )
 
 
@@ -207,14 +270,15 @@ def build_GN_block(in_dim_node: int, in_dim_edge: int, hidden_dim_node: int = 12
 class GraphProcessor(nn.Module):
     def __init__(self, n_iterations: int, in_dim_node: int, in_dim_edge: int, hidden_dim_node: int = 128,
                  hidden_dim_edge: int = 128, hidden_layers_node: int = 2, hidden_layers_edge: int = 2,
-                 activation: str = "ReLU", initializer: None | str = None, norm_type="LayerNorm"):
-        """n_iterations GN blocks with unshared weights (models/GNN.py:168-211)."""
+                 activation: str = "ReLU", initializer: None | str = None, norm_type="LayerNorm", aggregation: str = "sum"):
+        """n_iterations GN blocks with unshared weights (models/GNN.py:168-211); ``aggregation`` is every block's."""
         super().__init__()
+        self.aggregation = _check_aggregation(aggregation, "GraphProcessor")
         self.blocks = nn.ModuleList()
         for _ in range(n_iterations):
             self.blocks.append(build_GN_block(in_dim_node, in_dim_edge, hidden_dim_node, hidden_dim_edge,
                                               hidden_layers_node, hidden_layers_edge, activation, initializer,
-                                              norm_type))
+                                              norm_type, aggregation=aggregation))
 
     def forward(self, x, edge_index, edge_attr):
         """models/GNN.py:213-216; ``edge_attr`` in and out in the caller's edge order."""
@@ -267,10 +331,13 @@ class GraphNet(nn.Module):
         norm_type = kwargs.get("norm_type", "LayerNorm")
         activation = kwargs.get("activation", "ReLU")
         initializer = kwargs.get("initializer", None)
+        # "sum" (the reference's code), "mean" (its write-up) or "max"; any other value is an error, never a silent sum
+        aggregation = _check_aggregation(kwargs.get("aggregation", "sum"), "GraphNet")
 
         self.name = "GraphNet"
         self.out_dim = out_dim
         self.space_dim = space_dim
+        self.aggregation = aggregation
 
         self.node_encoder = MLP(in_dim_node, out_dim_node, hidden_dim_node, hidden_layers_node, activation=activation,
                                 initializer=initializer, norm_type=norm_type)
@@ -279,7 +346,7 @@ class GraphNet(nn.Module):
         self.graph_processor = GraphProcessor(n_blocks, out_dim_node, out_dim_edge, hidden_dim_processor_node,
                                               hidden_dim_processor_edge, hidden_layers_processor_node,
                                               hidden_layers_processor_edge, activation=activation,
-                                              initializer=initializer, norm_type=norm_type)
+                                              initializer=initializer, norm_type=norm_type, aggregation=aggregation)
         self.node_decoder = MLP(out_dim_node, out_dim, hidden_dim_decoder, hidden_layers_decoder, norm_type=None)
 
     def forward_device(self, x: Tensor, pos: Tensor, topo: GraphTopology) -> Tensor:

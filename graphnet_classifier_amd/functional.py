@@ -54,6 +54,83 @@ def scatter_sum_csr(src: torch.Tensor, rowptr: torch.Tensor, perm, dst_of_row: t
     return _ScatterSumCSR.apply(src, rowptr, perm, dst_of_row, num_nodes)
 
 
+class _SegmentMeanCSR(torch.autograd.Function):
+    """K18 mean (csrc/segment_reduce.hip): keeps nothing but the topology."""
+
+    @staticmethod
+    def forward(ctx, src, rowptr, perm, dst_of_row, num_nodes):
+        ctx.save_for_backward(dst_of_row, rowptr)
+        return native.segment_reduce_csr(src, rowptr, perm, num_nodes, native.SEGMENT_MEAN)[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dst_of_row, rowptr = ctx.saved_tensors  # d out[dst(e)] / d src[e] = I / deg(dst(e))
+        return native.segment_reduce_backward(grad_out, dst_of_row, rowptr, None, native.SEGMENT_MEAN), None, None, None, None
+
+
+class _SegmentMaxCSR(torch.autograd.Function):
+    """K18 max: the winners' rows are stored only when a gradient will need them or the caller asks for them."""
+
+    @staticmethod
+    def forward(ctx, src, rowptr, perm, dst_of_row, num_nodes, want_argmax):
+        need = ctx.needs_input_grad[0]
+        out, argmax = native.segment_reduce_csr(src, rowptr, perm, num_nodes, native.SEGMENT_MAX, with_argmax=need or want_argmax)
+        if need:
+            ctx.save_for_backward(dst_of_row, rowptr, argmax)
+        if argmax is None:
+            return out, None
+        ctx.mark_non_differentiable(argmax)
+        return out, argmax
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_argmax=None):
+        dst_of_row, rowptr, argmax = ctx.saved_tensors  # the gradient of a column goes to the row that won it, and only there
+        return native.segment_reduce_backward(grad_out, dst_of_row, rowptr, argmax, native.SEGMENT_MAX), None, None, None, None, None
+
+
+def segment_mean_csr(src: torch.Tensor, rowptr: torch.Tensor, perm, dst_of_row: torch.Tensor, num_nodes: int):
+    """out[v] = mean of the src rows whose destination is v (+0.0 for none): the ascending sum of ``scatter_sum_csr`` divided by
+    ``float(deg)``.  Arguments as ``scatter_sum_csr``; ``dst_of_row`` may be None when no gradient is wanted."""
+    if dst_of_row is None and src.requires_grad and torch.is_grad_enabled():
+        raise ValueError("segment_mean_csr: dst_of_row is needed for the backward")
+    return _SegmentMeanCSR.apply(src, rowptr, perm, dst_of_row, num_nodes)
+
+
+def segment_max_csr(src: torch.Tensor, rowptr: torch.Tensor, perm, dst_of_row: torch.Tensor, num_nodes: int,
+                    return_argmax: bool = False):
+    """out[v] = column-wise maximum of the src rows whose destination is v (+0.0 for none; a NaN wins; a tie goes to the lowest
+    sorted position).  ``return_argmax``: ``(out, argmax)`` with ``argmax`` int32 [num_nodes, D], the winning row of ``src``, -1
+    for a destination without rows.  Without it, and without autograd, the launch stores no winners."""
+    if dst_of_row is None and src.requires_grad and torch.is_grad_enabled():
+        raise ValueError("segment_max_csr: dst_of_row is needed for the backward")
+    out, argmax = _SegmentMaxCSR.apply(src, rowptr, perm, dst_of_row, num_nodes, bool(return_argmax))
+    return (out, argmax) if return_argmax else out
+
+
+class _DivByDegree(torch.autograd.Function):
+    """Rows of an [N, D] aggregate divided by the in-degree (gnc_rows_div_degree_f32); linear, so the same launch on the gradient."""
+
+    @staticmethod
+    def forward(ctx, agg, rowptr, inplace):
+        ctx.save_for_backward(rowptr)
+        if inplace:
+            ctx.mark_dirty(agg)
+            return native.rows_div_degree_(agg, rowptr)
+        return native.rows_div_degree_(agg.clone(memory_format=torch.contiguous_format), rowptr)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (rowptr,) = ctx.saved_tensors
+        return native.rows_div_degree_(grad_out.clone(memory_format=torch.contiguous_format), rowptr), None, None
+
+
+def div_by_degree(agg: torch.Tensor, rowptr: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """``agg[v] / float(deg(v))`` for the per-destination sums ``agg`` [N, D] of a CSR (rows of degree 0 unchanged): with
+    ``scatter_sum_csr`` - or the edge launch's aggregation epilogue - in front of it, the bits of ``segment_mean_csr``.
+    ``inplace=True`` overwrites ``agg`` (the caller owns it and nothing else reads the sums)."""
+    return _DivByDegree.apply(agg, rowptr, bool(inplace))
+
+
 class _PermuteRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table, perm, inv_perm):

@@ -142,6 +142,11 @@ _SIGNATURES = {
                                              c_int64, c_void_p, c_int64, c_void_p]),
     "gnc_graph_pool_backward_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                               c_void_p]),
+    "gnc_segment_reduce_csr_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64,
+                                             c_void_p, c_void_p]),
+    "gnc_segment_reduce_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                                  c_void_p, c_int64, c_void_p]),
+    "gnc_rows_div_degree_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     "gnc_adam_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p]),
 }
@@ -455,6 +460,96 @@ def gather_rows_add(table: torch.Tensor, index: torch.Tensor, addend: torch.Tens
         _check(lib.gnc_gather_rows_add_f32(table.data_ptr(), _ld(table), index.data_ptr(), addend.data_ptr(), _ld(addend), n, d,
                                            out.data_ptr(), _ld(out), _stream(table)), "gnc_gather_rows_add_f32")
     return out
+
+
+
+# --------------------------------------------------------------------------- K18: mean / max aggregation
+SEGMENT_MEAN, SEGMENT_MAX = 1, 2  # GNC_SEGMENT_* of include/gnc_hip.h
+SEGMENT_MODES = {"mean": SEGMENT_MEAN, "max": SEGMENT_MAX}
+
+
+def _segment_mode(mode) -> int:
+    mode = SEGMENT_MODES.get(mode, mode)
+    if mode not in (SEGMENT_MEAN, SEGMENT_MAX):
+        raise ValueError(f"segment_reduce: mode {mode!r} is not one of {sorted(SEGMENT_MODES)}")
+    return mode
+
+
+def segment_reduce_csr(src: torch.Tensor, rowptr: torch.Tensor, perm: torch.Tensor | None, num_nodes: int, mode,
+                       with_argmax: bool = False):
+    """K1 with another reducer (csrc/segment_reduce.hip): ``(out [num_nodes, D], argmax)``.  ``mode``: ``"mean"`` / ``"max"``;
+    ``argmax`` int32 [num_nodes, D] - the row of ``src`` that won each column, -1 for a destination without rows - comes only
+    with ``with_argmax`` (max), else None and the launch stores nothing for it."""
+    lib = load_library()
+    _require_cuda(src, rowptr, perm)
+    mode = _segment_mode(mode)
+    if with_argmax and mode != SEGMENT_MAX:
+        raise ValueError("segment_reduce_csr: argmax comes with mode 'max' only")
+    if rowptr.dtype != torch.int32 or (perm is not None and perm.dtype != torch.int32):
+        raise TypeError("segment_reduce_csr expects int32 rowptr / perm")
+    if rowptr.numel() != num_nodes + 1:
+        raise ValueError(f"segment_reduce_csr: rowptr has {rowptr.numel()} entries for {num_nodes} nodes")
+    src = _rowmajor(src)
+    e, d = src.shape
+    out = torch.empty(num_nodes, d, dtype=torch.float32, device=src.device)
+    argmax = torch.empty(num_nodes, d, dtype=torch.int32, device=src.device) if with_argmax else None
+    # algorithmic bytes (DESIGN.md, K18): K1's, plus one int32 per output element when the winners are stored
+    work = (4.0 * d * e + 4.0 * d * num_nodes + 4.0 * (num_nodes + 1) + (4.0 * e if perm is not None else 0.0)
+            + (4.0 * d * num_nodes if with_argmax else 0.0))
+    name = "segment_" + ("mean" if mode == SEGMENT_MEAN else "max_argmax" if with_argmax else "max") + "_csr"
+    with torch.cuda.device(src.device):
+        _check(_launch(name, src,
+                       lambda: lib.gnc_segment_reduce_csr_f32(src.data_ptr(), _ld(src), rowptr.data_ptr(),
+                                                              perm.data_ptr() if perm is not None else None, num_nodes, e, d, mode,
+                                                              out.data_ptr(), _ld(out),
+                                                              argmax.data_ptr() if argmax is not None else None, _stream(src)), work),
+               "gnc_segment_reduce_csr_f32")
+    return out, argmax
+
+
+def segment_reduce_backward(grad_out: torch.Tensor, dst_of_row: torch.Tensor, rowptr: torch.Tensor, argmax: torch.Tensor | None,
+                            mode) -> torch.Tensor:
+    """``grad_src`` [E, D] of ``segment_reduce_csr`` in one pass over its rows: ``dst_of_row`` int32 [E] is the destination of
+    each row of the forward's ``src``; mean needs ``rowptr``, max the forward's ``argmax``."""
+    lib = load_library()
+    _require_cuda(grad_out, dst_of_row, rowptr, argmax)
+    mode = _segment_mode(mode)
+    grad_out = _rowmajor(grad_out)
+    n, d = grad_out.shape
+    if dst_of_row.dtype != torch.int32 or rowptr.dtype != torch.int32:
+        raise TypeError("segment_reduce_backward expects int32 dst_of_row / rowptr")
+    if rowptr.numel() != n + 1:
+        raise ValueError(f"segment_reduce_backward: rowptr has {rowptr.numel()} entries for {n} rows of grad_out")
+    if mode == SEGMENT_MAX and (argmax is None or argmax.dtype != torch.int32 or tuple(argmax.shape) != (n, d)
+                                or not argmax.is_contiguous()):
+        raise ValueError("segment_reduce_backward: max needs the forward's contiguous int32 argmax [N, D]")
+    e = dst_of_row.numel()
+    grad_src = torch.empty(e, d, dtype=torch.float32, device=grad_out.device)
+    with torch.cuda.device(grad_out.device):
+        _check(_launch("segment_" + ("mean" if mode == SEGMENT_MEAN else "max") + "_backward", grad_out,
+                       lambda: lib.gnc_segment_reduce_backward_f32(grad_out.data_ptr(), _ld(grad_out), dst_of_row.data_ptr(),
+                                                                   rowptr.data_ptr(),
+                                                                   argmax.data_ptr() if mode == SEGMENT_MAX else None, n, e, d, mode,
+                                                                   grad_src.data_ptr(), _ld(grad_src), _stream(grad_out)),
+                       4.0 * d * e + 4.0 * e + (8.0 if mode == SEGMENT_MAX else 4.0) * d * n),
+               "gnc_segment_reduce_backward_f32")
+    return grad_src
+
+
+def rows_div_degree_(table: torch.Tensor, rowptr: torch.Tensor) -> torch.Tensor:
+    """In place: row v of ``table`` [N, D] divided by ``float(rowptr[v + 1] - rowptr[v])``, rows of degree 0 left alone."""
+    lib = load_library()
+    _require_cuda(table, rowptr)
+    if table.dtype != torch.float32 or table.dim() != 2 or (table.size(1) > 0 and table.stride(1) != 1):
+        raise ValueError("rows_div_degree_: a 2-D float32 table with unit column stride expected")
+    if rowptr.dtype != torch.int32 or rowptr.numel() != table.size(0) + 1:
+        raise ValueError(f"rows_div_degree_: int32 rowptr with {table.size(0) + 1} entries expected")
+    n, d = table.shape
+    with torch.cuda.device(table.device):
+        _check(_launch("rows_div_degree", table,
+                       lambda: lib.gnc_rows_div_degree_f32(table.data_ptr(), _ld(table), rowptr.data_ptr(), n, d, _stream(table)),
+                       8.0 * d * n + 4.0 * (n + 1)), "gnc_rows_div_degree_f32")
+    return table
 
 
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:

@@ -627,6 +627,35 @@ int gnc_graph_pool_forward_f32(const float* y, int64_t rows, int64_t C, const in
 int gnc_graph_pool_backward_f32(const float* dsum, const float* dmean, const float* dmax, int64_t ld_grad, const int32_t* argmax,
                                 const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, int64_t C, float* dy, void* stream);
 
+/* ---- K18: mean / max neighbourhood aggregation (csrc/segment_reduce.hip) --------------
+ * The node model's aggregation with another reducer than K1's sum, over the same destination-sorted CSR and with K1's argument
+ * conventions: out[v, :] reduces src[row(k), :] over the sorted positions k in [rowptr[v], rowptr[v+1]), row(k) = perm[k] or k
+ * itself when `perm` is NULL.  No atomics; rows are folded in ascending k (the sort is stable: original edge order); every out
+ * row is written exactly once; two runs, and a graph alone or inside a block-diagonal batch, give the same bits.
+ *   GNC_SEGMENT_MEAN: the running sum exactly as gnc_scatter_sum_csr_f32 forms it (from +0.0, ascending k), then sum / (float)deg,
+ *                     a true fp32 division.  A destination without rows gives +0.0.  `argmax` must be NULL.
+ *   GNC_SEGMENT_MAX:  the fold rule of K17: the larger value wins, a NaN beats everything (argmax at the first NaN), a tie goes to
+ *                     the lowest sorted position, -0.0 == +0.0.  A destination without rows gives +0.0 and argmax -1.
+ *                     `argmax`: NULL (inference: no extra store) or int32 [num_nodes, feat_dim] contiguous, the row of `src`
+ *                     that won each column.
+ * Backward, one pass over the num_rows rows of grad_src [num_rows, ld_src] (row r of grad_src belongs to row r of the forward's
+ * src; dst_of_row[r] is its destination): MEAN writes grad_out[dst, :] / (float)deg(dst) (needs rowptr), MAX writes
+ * grad_out[dst, c] where argmax[dst, c] == r and exact +0.0 elsewhere (needs argmax).  No [E, D] intermediate.
+ * gnc_rows_div_degree_f32: in place, table[v, :] /= (float)deg(v) with the MEAN kernel's division; rows of degree 0 are left
+ * alone.  Applied to a table of K1 sums (or of the fused aggregation epilogue) it gives the MEAN kernel's bits; it is linear, so
+ * applied to the gradient it is its own backward.
+ * All three: int status, no allocation, no synchronisation, kernel nodes under stream capture.  Added without an ABI bump: a
+ * library without these symbols fails the symbol lookup of the binding. */
+#define GNC_SEGMENT_MEAN 1
+#define GNC_SEGMENT_MAX 2
+int gnc_segment_reduce_csr_f32(const float* src, int64_t ld_src, const int32_t* rowptr, const int32_t* perm, int64_t num_nodes,
+                               int64_t num_edges, int32_t feat_dim, int32_t mode, float* out, int64_t ld_out, int32_t* argmax,
+                               void* stream);
+int gnc_segment_reduce_backward_f32(const float* grad_out, int64_t ld_grad, const int32_t* dst_of_row, const int32_t* rowptr,
+                                    const int32_t* argmax, int64_t num_nodes, int64_t num_rows, int32_t feat_dim, int32_t mode,
+                                    float* grad_src, int64_t ld_src, void* stream);
+int gnc_rows_div_degree_f32(float* table, int64_t ld, const int32_t* rowptr, int64_t num_nodes, int32_t feat_dim, void* stream);
+
 /* ---- graph construction on the device ---------------------------
  * Inputs: an already resized uint8 RGB image [H, W, C] in HBM.  Outputs: the tensors
  * utils/dataloader.py:49-51 builds (x, pos float32; edge_index int64 [2, E] row-major), in the
