@@ -675,17 +675,28 @@ class LinearClassifier(nn.Module):
 
 
 class CombinedModel(nn.Module):
-    READOUTS = ("flatten", "mean", "max", "sum", "hybrid")
+    READOUTS = ("flatten", "mean", "max", "sum", "hybrid", "attention")
 
-    def __init__(self, graph_net: GraphNet | None = None, num_nodes: int = 128 * 128, classes: int = 2, *, readout: str = "flatten"):
+    def __init__(self, graph_net: GraphNet | None = None, num_nodes: int = 128 * 128, classes: int = 2, *, readout: str = "flatten",
+                 gate_hidden: int | None = None):
         """models/GNN.py:327-332.  ``readout="flatten"`` is the reference's model: ``fc1`` over the ``num_nodes * out_dim`` flattened
         node outputs.  ``"mean"`` / ``"max"`` / ``"sum"`` / ``"hybrid"``: a global pooling read-out (the one the reference's write-up
         describes; K17) hands ONE vector per graph - ``out_dim`` wide, ``3 * out_dim`` for ``hybrid`` = [mean | max | sum] - to the
         same three-layer classifier.  It is permutation invariant and defined for every node count; ``num_nodes`` is kept but
-        sizes nothing.  Same ``state_dict`` keys either way; ``readout`` is not stored in it."""
+        sizes nothing.  Same ``state_dict`` keys either way; ``readout`` is not stored in it.
+
+        ``"attention"`` (K19): the write-up's attention read-out.  A gate ``score(v) = W2 relu(W1 h_v + b1) + b2`` - ``self.gate``,
+        an ``MLP(out_dim, 1, hidden_dim=gate_hidden)`` with one hidden layer of ``gate_hidden`` (32 by default) units and no norm
+        - scores every node, and the graph's vector is the sum of its node outputs weighted by the softmax of the scores over the
+        graph: ``out_dim`` wide, permutation invariant, defined for every node count.  The gate is built AFTER the classifier, so
+        under one seed every other parameter equals the ``"mean"`` model's; its keys ``gate.model.0.*`` / ``gate.model.2.*`` exist for
+        this read-out alone, and ``gate_hidden`` with another read-out is a ValueError.  A checkpoint of another pooled read-out
+        loads with ``load_state_dict(..., strict=False)``: the gate then stays at its initialisation."""
         super().__init__()
         if readout not in self.READOUTS:
             raise ValueError(f"CombinedModel: readout {readout!r} is not one of {self.READOUTS}")
+        if gate_hidden is not None and readout != "attention":
+            raise ValueError(f"CombinedModel: gate_hidden belongs to readout='attention', not to {readout!r}")
         self.graph_net = graph_net if graph_net is not None else GraphNet()
         self.num_nodes = num_nodes
         self.readout = readout
@@ -694,6 +705,9 @@ class CombinedModel(nn.Module):
         else:
             in_features = (3 if readout == "hybrid" else 1) * self.graph_net.out_dim
         self.classifier = LinearClassifier(in_features=in_features, classes=classes)
+        if readout == "attention":  # after the classifier: the other parameters draw the random numbers they draw without it
+            self.gate = MLP(self.graph_net.out_dim, 1, hidden_dim=32 if gate_hidden is None else int(gate_hidden), hidden_layers=1,
+                            activation="ReLU", norm_type=None)
         # True: ``forward`` accepts a graph of any node count N.  On the flatten model (off by default; a plain attribute, not a
         # constructor argument and not in the state_dict) it feeds fc1 rows [0, min(N, num_nodes)) of the GraphNet output, the rest
         # of the vector zero (forward_batched(graph_ptr=...)'s rule; the reference's read-out is only defined for
@@ -716,7 +730,10 @@ class CombinedModel(nn.Module):
         if gp is not None:
             num_graphs = gp.numel() - 1
         if self.pooled:
-            feats = Fn.graph_pool(y, gp, self.readout)  # [G, F]
+            if self.readout == "attention":  # the gate scores ALL rows; rows of no graph get zero score gradient from K19
+                feats = Fn.graph_attention_pool(y, self.gate.forward_segments([(y, None)]).view(-1), gp)  # [G, out_dim]
+            else:
+                feats = Fn.graph_pool(y, gp, self.readout)  # [G, F]
             if num_graphs == 1:
                 return self.classifier(feats[0]).unsqueeze(0)  # the single-graph launch (csrc/readout.hip)
             if READOUT_HIP and native.readout_batched_supported(num_graphs, feats.size(1), fc1.out_features, fc2.out_features,
@@ -740,6 +757,23 @@ class CombinedModel(nn.Module):
             rows = (start[:, None] + k[None, :]).clamp_(max=max(y.size(0) - 1, 0))
             feats = (y[rows] * valid[..., None]).reshape(gp.numel() - 1, self.num_nodes * od)
         return self.classifier(feats)
+
+    def attention_weights(self, x, pos=None, edge_index=None) -> Tensor:
+        """The attention read-out's node weights [N] of ONE graph (``readout="attention"`` only; same arguments as ``forward``,
+        the tuple form included): the softmax of the gate's scores over the graph's nodes, on the device of ``x``.  No gradient."""
+        if self.readout != "attention":
+            raise ValueError(f"CombinedModel.attention_weights: readout is {self.readout!r}, not 'attention'")
+        if pos is None and edge_index is None and isinstance(x, tuple):
+            x, pos, edge_index = x
+        dev = require_gpu_param(self.classifier.fc1.weight, "CombinedModel")
+        back = x.device
+        with torch.no_grad():
+            x = x.to(device=dev, dtype=torch.float32)
+            pos = pos.to(device=dev, dtype=torch.float32)
+            y = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev))
+            whole = torch.arange(2, dtype=torch.int64, device=dev) * y.size(0)  # [0, N], built on the device
+            _, alpha = Fn.graph_attention_pool(y, self.gate.forward_segments([(y, None)]).view(-1), whole, return_weights=True)
+        return alpha if back == dev else alpha.to(back)
 
     def forward(self, x, pos=None, edge_index=None):
         """models/GNN.py:334-341; accepts the (x, pos, edge_index) tuple; logits are 1-D [classes]."""

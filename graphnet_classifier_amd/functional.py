@@ -760,6 +760,37 @@ def graph_pool(y: torch.Tensor, graph_ptr: torch.Tensor, mode: str) -> torch.Ten
     return _GraphPool.apply(y, graph_ptr, native.POOL_MODES[mode])
 
 
+class _GraphAttentionPool(torch.autograd.Function):
+    """Attention read-out over the graphs of a block-diagonal batch (csrc/attention_pool.hip, K19): one launch (three for a few
+    large graphs) forward, one streaming launch backward that recomputes the weights from the per-graph (max, sum) it kept."""
+
+    @staticmethod
+    def forward(ctx, y, scores, graph_ptr):
+        out, saved = native.graph_attention_pool_forward(y, scores, graph_ptr)
+        ctx.save_for_backward(y, scores, graph_ptr, out, saved)
+        ctx.mark_non_differentiable(saved)
+        return out, saved
+
+    @staticmethod
+    def backward(ctx, grad, _grad_saved):
+        y, scores, graph_ptr, out, saved = ctx.saved_tensors
+        need_dy, need_ds = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dy, ds = native.graph_attention_pool_backward(grad, y, scores, out, saved, graph_ptr, need_dy, need_ds)
+        return dy, ds, None
+
+
+def graph_attention_pool(y: torch.Tensor, scores: torch.Tensor, graph_ptr: torch.Tensor, return_weights: bool = False):
+    """Attention read-out: ``out[g] = sum_v alpha_v y[v]`` over the rows of graph g with ``alpha = softmax(scores[rows of g])``;
+    ``y`` [rows, C] and ``scores`` [rows] float32 on the GPU, ``graph_ptr`` int64 [G + 1] on the same device (as ``graph_pool``'s:
+    rows outside the graphs are ignored and receive zero gradient, an empty graph pools to zeros).  Differentiable in ``y`` and
+    ``scores``.  ``return_weights=True``: ``(out, alpha)`` with ``alpha`` [rows] float32, zero outside the graphs, not
+    differentiable."""
+    out, saved = _GraphAttentionPool.apply(y, scores, graph_ptr)
+    if not return_weights:
+        return out
+    return out, native.graph_attention_weights(scores.detach(), saved, graph_ptr)
+
+
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """[pos[dst]-pos[src], L1 norm] per edge (models/GNN.py:299-302).  ``pos`` is input data
     (utils/dataloader.py:50); gradients with respect to it are not provided."""

@@ -142,6 +142,12 @@ _SIGNATURES = {
                                              c_int64, c_void_p, c_int64, c_void_p]),
     "gnc_graph_pool_backward_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                               c_void_p]),
+    "gnc_graph_attention_pool_workspace_floats": (c_int64, [c_int64, c_int64, c_int64]),
+    "gnc_graph_attention_pool_forward_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                                       c_void_p, c_int64, c_void_p]),
+    "gnc_graph_attention_pool_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                                        c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gnc_graph_attention_weights_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "gnc_segment_reduce_csr_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64,
                                              c_void_p, c_void_p]),
     "gnc_segment_reduce_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
@@ -1022,6 +1028,94 @@ def graph_pool_backward(grad: torch.Tensor, modes: int, argmax: torch.Tensor | N
                                                                int(rows), C, dy.data_ptr(), _stream(grad)),
                        float(rows * C)), "gnc_graph_pool_backward_f32")
     return dy
+
+
+# --------------------------------------------------------------------------- K19: attention read-out
+def _attention_scores(scores: torch.Tensor, y: torch.Tensor, who: str) -> torch.Tensor:
+    if scores.dtype != torch.float32 or scores.dim() != 1 or scores.size(0) != y.size(0) or scores.device != y.device:
+        raise ValueError(f"{who}: scores must be float32 [rows] = [{y.size(0)}] on the device of y, got {scores.dtype} "
+                         f"{tuple(scores.shape)} on {scores.device}")
+    return scores.contiguous()
+
+
+def graph_attention_pool_forward(y: torch.Tensor, scores: torch.Tensor, graph_ptr: torch.Tensor):
+    """Softmax-weighted pooling (K19): for each graph ``graph_ptr`` (DEVICE int64 [G + 1], never read on the host) names, the
+    softmax of its rows' ``scores`` [rows] and the column sums of ``y`` [rows, C] (float32) weighted by it.  Returns ``(out, saved)``:
+    ``out`` [G, C]; ``saved`` [G, 2] = (max score, sum of exponentials) per graph, which is all the backward and
+    ``graph_attention_weights`` need.  An empty graph pools to +0.0; rows outside the graphs are ignored."""
+    lib = load_library()
+    _require_cuda(y, graph_ptr)  # (scores on another device: the ValueError below)
+    y = _rowmajor(y).contiguous()
+    dev, rows, C = y.device, y.size(0), y.size(1)
+    scores = _attention_scores(scores, y, "graph_attention_pool_forward")
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    floats = lib.gnc_graph_attention_pool_workspace_floats(rows, C, G)
+    if floats < 0:
+        raise RuntimeError(f"graph_attention_pool_forward: rows {rows} / width {C} / graphs {G} outside the kernel's set")
+    out = torch.empty(G, C, dtype=torch.float32, device=dev)
+    saved = torch.empty(G, 2, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(floats, 1), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("graph_attention_pool_forward", y,
+                       lambda: lib.gnc_graph_attention_pool_forward_f32(y.data_ptr(), scores.data_ptr(), rows, C, gp.data_ptr(), G,
+                                                                        out.data_ptr(), C, saved.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                                        _stream(y)),
+                       float(rows * (C + 1))), "gnc_graph_attention_pool_forward_f32")
+    return out, saved
+
+
+def graph_attention_pool_backward(grad: torch.Tensor, y: torch.Tensor, scores: torch.Tensor, out: torch.Tensor, saved: torch.Tensor,
+                                  graph_ptr: torch.Tensor, need_dy: bool = True, need_ds: bool = True):
+    """``(dy [rows, C], ds [rows])`` of ``graph_attention_pool_forward`` from ``grad`` [G, C] and the forward's ``out`` / ``saved``;
+    an unwanted one is None and costs nothing.  Every row is written; rows of no graph get exact zeros."""
+    lib = load_library()
+    _require_cuda(grad, y, out, saved, graph_ptr)
+    grad, y = _rowmajor(grad), _rowmajor(y).contiguous()
+    dev, rows, C = y.device, y.size(0), y.size(1)
+    scores = _attention_scores(scores, y, "graph_attention_pool_backward")
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    out = _rowmajor(out)
+    if grad.shape != (G, C) or out.shape != (G, C) or saved.shape != (G, 2) or saved.dtype != torch.float32 or not saved.is_contiguous():
+        raise ValueError(f"graph_attention_pool_backward: grad {tuple(grad.shape)} / out {tuple(out.shape)} / saved {tuple(saved.shape)} "
+                         f"are not the forward's [{G}, {C}] / [{G}, {C}] / [{G}, 2]")
+    if lib.gnc_graph_attention_pool_workspace_floats(rows, C, G) < 0:
+        raise RuntimeError(f"graph_attention_pool_backward: rows {rows} / width {C} / graphs {G} outside the kernel's set")
+    if not (need_dy or need_ds):
+        return None, None
+    dy = torch.empty(rows, C, dtype=torch.float32, device=dev) if need_dy else None
+    ds = torch.empty(rows, dtype=torch.float32, device=dev) if need_ds else None
+    with torch.cuda.device(dev):
+        _check(_launch("graph_attention_pool_backward", grad,
+                       lambda: lib.gnc_graph_attention_pool_backward_f32(grad.data_ptr(), _ld(grad), y.data_ptr(), scores.data_ptr(),
+                                                                         out.data_ptr(), _ld(out), saved.data_ptr(), gp.data_ptr(), G,
+                                                                         rows, C, dy.data_ptr() if need_dy else None,
+                                                                         ds.data_ptr() if need_ds else None, _stream(grad)),
+                       float(rows * (C + 1))), "gnc_graph_attention_pool_backward_f32")
+    return dy, ds
+
+
+def graph_attention_weights(scores: torch.Tensor, saved: torch.Tensor, graph_ptr: torch.Tensor) -> torch.Tensor:
+    """The softmax weights ``alpha`` [rows] behind ``graph_attention_pool_forward`` (one small launch from its ``saved``): they sum
+    to one over each non-empty graph; rows of no graph get +0.0."""
+    lib = load_library()
+    _require_cuda(scores, saved, graph_ptr)
+    if scores.dtype != torch.float32 or scores.dim() != 1:
+        raise ValueError(f"graph_attention_weights: scores must be float32 [rows], got {scores.dtype} {tuple(scores.shape)}")
+    scores = scores.contiguous()
+    dev, rows = scores.device, scores.size(0)
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    if saved.shape != (G, 2) or saved.dtype != torch.float32 or saved.device != dev or not saved.is_contiguous():
+        raise ValueError(f"graph_attention_weights: saved must be the forward's float32 [{G}, 2]")
+    alpha = torch.empty(rows, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("graph_attention_weights", scores,
+                       lambda: lib.gnc_graph_attention_weights_f32(scores.data_ptr(), saved.data_ptr(), gp.data_ptr(), G, rows,
+                                                                   alpha.data_ptr(), _stream(scores)),
+                       float(rows)), "gnc_graph_attention_weights_f32")
+    return alpha
 
 
 # --------------------------------------------------------------------------- K16: split-K first Linear of a wide-input MLP

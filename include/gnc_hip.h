@@ -627,6 +627,39 @@ int gnc_graph_pool_forward_f32(const float* y, int64_t rows, int64_t C, const in
 int gnc_graph_pool_backward_f32(const float* dsum, const float* dmean, const float* dmax, int64_t ld_grad, const int32_t* argmax,
                                 const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, int64_t C, float* dy, void* stream);
 
+/* ---- K19: attention read-out (csrc/attention_pool.hip) ---------------------------------
+ * Softmax-weighted global pooling with K17's conventions for `y` [rows, C], `graph_ptr` (DEVICE int64 [num_graphs + 1], never read
+ * on the host, clamped into [0, rows]) and the rows of no graph, plus one score per row, `scores` [rows] float32.  For graph g with
+ * rows [a, b):  m = max_v s_v,  e_v = expf(s_v - m) (the accurate expf),  Z = sum_v e_v,  out[g, c] = (sum_v e_v y[v, c]) / Z (an
+ * IEEE division); `out` [G, C] with row pitch ld_out >= C.  An empty graph gives +0.0 and nothing is divided; rows of no graph are
+ * never read.  `saved` [G, 2] floats receives (m, Z) per graph ((0, 0) for an empty one): the backward recomputes
+ * alpha_v = expf(s_v - m) / Z from it, no [rows] array is kept.  Non-finite scores are outside the contract but stay inside their
+ * graph: a NaN score makes every column of its own graph NaN, a NaN in y[v, c] column c of its graph, nothing else.
+ *
+ * Summation order: K17's, for Z and for the weighted column sums (chunks of `chunk_rows` rows from the graph's first row, the
+ * fixed tree inside a chunk, ascending chunk order; e_v y[v, c] enters by one fmaf) - a graph pooled alone and inside any batch
+ * gives the same bits, as do two runs.  The regime is gnc_graph_pool_plan's (rows, C, num_graphs alone; same bits either way):
+ * split == 0, one launch of one workgroup per (graph, column tile); split == 1, three launches (the maxima, one workgroup per
+ * (chunk, column tile) writing partials to `workspace`, the merge).  gnc_graph_attention_pool_workspace_floats: the floats the
+ * call needs (0 outside the split regime: slots * (C + 1) in it; -1: sizes outside the served set, which is K17's - rows < 2^31,
+ * 1 <= C <= 2^20, num_graphs >= 1; the launches then return GNC_ERR_UNSUPPORTED).  No atomics, no counters, no memset.
+ *
+ * Backward, ONE streaming launch over the rows: dy[v, :] = alpha_v dout[g, :] and ds[v] = alpha_v sum_c dout[g, c] (y[v, c] -
+ * out[g, c]) (the softmax Jacobian with sum_u alpha_u (dout_g . y_u) = dout_g . out_g folded in; the dot over C in a fixed lane
+ * order), exact +0.0 for rows of no graph.  `dout` [G, C] with row pitch ld_dout, `out` the forward's with pitch ld_out; dy
+ * [rows, C] contiguous, ds [rows]; either may be NULL and is then skipped (y and out are only read for ds).
+ * gnc_graph_attention_weights_f32 writes alpha [rows] (+0.0 for rows of no graph) from `scores` and `saved`.  Added without an ABI
+ * bump: a library without these symbols fails the symbol lookup of the binding. */
+int64_t gnc_graph_attention_pool_workspace_floats(int64_t rows, int64_t C, int64_t num_graphs);
+int gnc_graph_attention_pool_forward_f32(const float* y, const float* scores, int64_t rows, int64_t C, const int64_t* graph_ptr,
+                                         int64_t num_graphs, float* out, int64_t ld_out, float* saved, float* workspace,
+                                         int64_t workspace_floats, void* stream);
+int gnc_graph_attention_pool_backward_f32(const float* dout, int64_t ld_dout, const float* y, const float* scores, const float* out,
+                                          int64_t ld_out, const float* saved, const int64_t* graph_ptr, int64_t num_graphs,
+                                          int64_t rows, int64_t C, float* dy, float* ds, void* stream);
+int gnc_graph_attention_weights_f32(const float* scores, const float* saved, const int64_t* graph_ptr, int64_t num_graphs,
+                                    int64_t rows, float* alpha, void* stream);
+
 /* ---- K18: mean / max neighbourhood aggregation (csrc/segment_reduce.hip) --------------
  * The node model's aggregation with another reducer than K1's sum, over the same destination-sorted CSR and with K1's argument
  * conventions: out[v, :] reduces src[row(k), :] over the sorted positions k in [rowptr[v], rowptr[v+1]), row(k) = perm[k] or k
