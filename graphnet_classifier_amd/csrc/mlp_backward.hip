@@ -1178,129 +1178,159 @@ int launch_bwd_stream(const gnc_mlp_desc_t& d, const BwdArgs& b, const BwdPlan& 
   return gnc::check_launch("mlp_backward_stream_kernel");
 }
 
-// waves per workgroup of the 32-row streaming kernel for T 32-column tiles (the dispatch below and the partial-row query)
-int bwd_stream_waves(int T, int64_t rows) {
-  if (T < 4) return 4;
-  if (rows <= (int64_t)2 * RPW * gnc::num_cu()) return 2;  // small batch: see mlp_stream.hip
-  return 8;
-}
-
 int bwd_grid(int64_t rows) {
   int64_t grid = gnc::ceil_div(gnc::ceil_div(rows, RPW), BWAVES);
   return (int)(grid > gnc::num_cu() ? gnc::num_cu() : grid);
 }
 
-}  // namespace
+enum class BwdKernel { none, fused, col16, col16_persist, resident, stream32, stream16 };
 
-namespace {
-// widths 129..256: the 16-row kernel of mlp_backward16.hip (GNC_NO_BACKWARD16=1 switches it off for A/B runs)
-bool use_stream16(const gnc_mlp_desc_t& d, bool want_dx) {
-  static const bool off = getenv("GNC_NO_BACKWARD16") != nullptr;
-  return !off && bwd_stream16_supported(d, want_dx);
-}
-}  // namespace
+// The routing decision of one K8 launch: the kernel family, the numbers its launcher needs, and the facts the shape
+// queries report about it.  gnc_mlp_backward_f32 and every gnc_mlp_backward_* query read this struct; none of them
+// looks at a family's precondition on its own.
+struct BwdRoute {
+  BwdKernel kernel = BwdKernel::none;
+  int T = 0, nmm = 0, nadd = 0;  // resident: tiles, MATMUL / ADD segments (bwd_shape); stream32: tiles
+  int fused_nadd = 0;            // fused: ADD segments, 0 / 2 (fused_shape)
+  int waves = 0;                 // stream32: waves per workgroup
+  BwdPlan plan = {};             // stream32: the chunk plan (without the forward chunks when act_given)
+  bool saved = false;            // act_given: the launch takes the forward's post-activations as inputs
+  bool folds_dx_add = false;     // dx_add_grad_out is honoured
+  bool reads_saved_act = false;  // act_given is honoured (shape only: saved_act_ok adds the pointer tests)
+  bool gathers_grad = false;     // grad_gather is gathered inside the launch (shape only: grad_gather_ok)
+  int ln_partial_rows = 0;       // rows of ln_partial the launch fills; 0: no LayerNorm, or the kernel writes yhat
+  int fused_rows = 0;            // fused: rows of dw_partial[] (and of ln_partial)
+};
 
-extern "C" size_t gnc_sizeof_mlp_bwd_desc(void) { return sizeof(gnc_mlp_bwd_desc_t); }
-
-extern "C" int gnc_mlp_backward_supported(const gnc_mlp_desc_t* fwd) {
-  int rc = validate_desc(fwd, false);
-  if (rc) return rc;
-  int nmm, nadd, T;
-  BwdPlan pl;
-  if (!(fwd->save_act[0] && fwd->num_linear >= 2 && bwd_col16_supported(*fwd)) && !bwd_shape(*fwd, &nmm, &nadd, &T) &&
-      !bwd_stream_plan(*fwd, true, &pl, &T) && !use_stream16(*fwd, true)) {
-    gnc::set_error("gnc_mlp_backward: shape outside the HIP backward kernels (needs ReLU, widths <= 256, aligned tables)");
-    return GNC_ERR_UNSUPPORTED;
+// The cascade, in the launcher's order: fused (only when asked for: dw_partial given) -> col16 -> col16-persist (both only
+// with act_given) -> resident -> stream32 -> stream16.  `want_dx` changes the chunk plans of the two streaming kernels.
+// Pointer fields of `d` are looked at for alignment only.  The A/B switches of the backward are all read here, once per
+// process; none of them moves a launch to another family except GNC_NO_BACKWARD16 (widths 129..256 have no kernel then).
+BwdRoute bwd_route(const gnc_mlp_desc_t& d, bool want_dx, bool fused_asked, bool act_given) {
+  static const bool no_stream16 = getenv("GNC_NO_BACKWARD16") != nullptr;
+  static const bool no_dx_fold = getenv("GNC_NO_STREAM_DX_FOLD") != nullptr;    // the streaming kernels leave the add to the caller
+  static const bool no_saved = getenv("GNC_NO_SAVED_ACT") != nullptr;           // the backward recomputes the forward of every tile
+  static const bool no_gather = getenv("GNC_NO_GRAD_GATHER_FOLD") != nullptr;   // the caller gathers the rows itself
+  static const bool no_fused = getenv("GNC_NO_FUSED_BACKWARD") != nullptr;      // gnc_mlp_backward_fused_rows says 0
+  static const bool no_ln_sums = getenv("GNC_NO_STREAM_LN_SUMS") != nullptr;    // the streaming kernels write y_hat again
+  BwdRoute r;
+  r.saved = act_given;
+  // one line per family below: (family, folds dx_add, has a form that reads saved activations, gathers, ln_partial rows)
+  auto take = [&](BwdKernel k, bool folds, bool saved_form, bool gathers, int ln_rows) {
+    r.kernel = k;
+    r.folds_dx_add = folds;
+    r.reads_saved_act = act_given && !no_saved && saved_form;
+    r.gathers_grad = !no_gather && gathers;
+    r.ln_partial_rows = d.ln_gamma ? ln_rows : 0;
+    return r;
+  };
+  if (fused_asked) {  // fused data + weight-gradient kernel (three Linear layers, widths <= 64), saved or recomputing; or nothing
+    static_assert(kFusedSmem <= 160 * 1024, "fused backward kernel: LDS budget");
+    r.fused_nadd = fused_shape(d);
+    if (r.fused_nadd < 0) return r;
+    r.fused_rows = no_fused ? 0 : fused_grid(d.rows) * FWAVES;
+    return take(BwdKernel::fused, true, true, r.fused_nadd == 2, r.fused_rows);
   }
-  return GNC_OK;
+  // saved activations: small batches on the column-split data kernel, large ones at exactly 128 features on its persistent form
+  if (act_given && bwd_col16_supported(d)) return take(BwdKernel::col16, true, true, true, bwd_col16_ln_partial_rows(d.rows));
+  if (act_given && bwd_col16_persist_supported(d))
+    return take(BwdKernel::col16_persist, true, true, d.in_dim[0] <= 128, bwd_col16_persist_ln_partial_rows(d.rows));
+  // weights-resident data kernel (widths <= 64): a SAVED instance exists for the node processors' shape only (widths 33..64,
+  // two MATMUL segments), the others recompute
+  if (bwd_shape(d, &r.nmm, &r.nadd, &r.T))
+    return take(BwdKernel::resident, true, r.T == 2 && r.nmm == 2 && r.nadd == 0, false, bwd_grid(d.rows) * BWAVES);
+  // 32-row streaming kernel (widths <= 128): SAVED instances for the 65..128 class; one ln_partial row per wave of its grid
+  if (bwd_stream_plan(d, want_dx, &r.plan, &r.T, act_given)) {
+    r.waves = r.T < 4 ? 4 : d.rows <= (int64_t)2 * RPW * gnc::num_cu() ? 2 : 8;  // 65..128: 2 for a small batch (see mlp_stream.hip)
+    const int64_t tiles = gnc::ceil_div(d.rows, (int64_t)r.waves * RPW);
+    const int ln_rows = (int)(tiles < gnc::num_cu() ? tiles : gnc::num_cu()) * r.waves;
+    return take(BwdKernel::stream32, !no_dx_fold, r.T == 4, false, no_ln_sums ? 0 : ln_rows);
+  }
+  // 16-row streaming kernel (widths 129..256)
+  if (!no_stream16 && bwd_stream16_supported(d, want_dx))
+    return take(BwdKernel::stream16, !no_dx_fold, true, false, no_ln_sums ? 0 : bwd_stream16_ln_partial_rows(d.rows));
+  return r;
 }
 
-// 1 if the small-batch data kernel (mlp_bwd_col16.hip) serves this backward exactly as the operands lie: it reads neither the
-// segment tables nor (without dx) the first Linear's weight, so the caller need not make 16-B-row copies of [N, 3] inputs or
-// nn.Linear(3, H) weights.  fwd.save_act must carry the saved post-activations (see gnc_mlp_bwd_desc_t).
-extern "C" int gnc_mlp_backward_small_batch_supported(const gnc_mlp_desc_t* fwd) {
-  if (!fwd || validate_desc(fwd, false) != GNC_OK || fwd->num_linear < 2 || !fwd->save_act[0]) return 0;
-  return bwd_col16_supported(*fwd) ? 1 : 0;
+// the route of a query that sees the forward description only: saved post-activations are announced in fwd.save_act (the
+// same pointers as act[]), and the input gradient counts as wanted
+BwdRoute bwd_route_of_fwd(const gnc_mlp_desc_t& fwd) { return bwd_route(fwd, true, false, fwd.save_act[0] != nullptr); }
+
+// act_given is honoured: the routed kernel reads the rows, and they are contiguous [rows, out_dim[l]] rows of 16-B pieces
+bool saved_act_ok(const gnc_mlp_bwd_desc_t& bd, const BwdRoute& r) {
+  for (int l = 0; l < bd.fwd.num_linear - 1; ++l)
+    if (!bd.act[l] || !al16(bd.act[l]) || bd.fwd.out_dim[l] % 4 != 0) return false;
+  return r.reads_saved_act;
 }
 
-extern "C" int gnc_mlp_backward_dx_add_honoured(const gnc_mlp_desc_t* fwd) {
-  int nmm, nadd, T;
-  BwdPlan pl;
-  static const bool off = getenv("GNC_NO_STREAM_DX_FOLD") != nullptr;  // A/B switch: the streaming kernels leave the add to the caller
-  if (!fwd || validate_desc(fwd, false) != GNC_OK) return 0;
-  if (fwd->save_act[0] && fwd->num_linear >= 2 && (bwd_col16_supported(*fwd) || bwd_col16_persist_supported(*fwd))) return 1;
-  if (bwd_shape(*fwd, &nmm, &nadd, &T)) return 1;
-  return (!off && (bwd_stream_plan(*fwd, true, &pl, &T) || use_stream16(*fwd, true))) ? 1 : 0;
+// grad_gather is honoured: the routed kernel gathers in the launch, and the table is one it can address
+bool grad_gather_ok(const gnc_mlp_bwd_desc_t& bd, const BwdRoute& r) {
+  const gnc_mlp_desc_t& d = bd.fwd;
+  if (!bd.grad_gather || !bd.grad_gather_index || !r.gathers_grad) return false;
+  if (bd.ld_grad_gather % 4 != 0 || !al16(bd.grad_gather) || bd.ld_grad_gather < d.out_dim[d.num_linear - 1]) return false;
+  if (r.kernel != BwdKernel::fused) return true;
+  // the fused kernel gathers with the ids of its second ADD segment (in the edge processor both are the destination)
+  if (bd.grad_gather_index != d.seg[2].index || bd.grad_gather_rows != d.seg[2].table_rows) return false;
+  // ids one row past either table (rows beyond the end of the batch) must still be addressable in 32 bits
+  const int64_t bytes = bd.grad_gather_rows * (int64_t)bd.ld_grad_gather * 4;
+  return bytes + 256 <= 0xffffffffll && d.seg[2].table_rows * (int64_t)d.seg[2].ld * 4 + 256 <= 0xffffffffll;
 }
 
-
-extern "C" int gnc_mlp_backward_f32(const gnc_mlp_bwd_desc_t* bd, void* stream_) {
-  if (!bd) { gnc::set_error("gnc_mlp_backward_f32: null descriptor"); return GNC_ERR_INVALID_ARGUMENT; }
+// the fused data + weight-gradient kernel (r.kernel == fused)
+int launch_fused_route(const gnc_mlp_bwd_desc_t* bd, const BwdRoute& r, hipStream_t stream) {
   const gnc_mlp_desc_t& d = bd->fwd;
-  int rc = validate_desc(&d, false);
-  if (rc) return rc;
-  if (d.ef_pos) {  // the backward reads the segment's rows (dW_0): a training forward materialises them (gnc_edge_features_f32)
-    gnc::set_error("gnc_mlp_backward_f32: fwd.ef_pos (computed edge features) is an inference-only form");
-    return GNC_ERR_UNSUPPORTED;
+  GNC_REQUIRE(bd->dw_partial[1] && bd->dw_partial[2], "gnc_mlp_backward_f32: dw_partial[0..2] must all be given");
+  GNC_REQUIRE(!d.ln_gamma || bd->ln_partial, "gnc_mlp_backward_f32: the fused kernel needs ln_partial with LayerNorm");
+  GNC_REQUIRE(!bd->grad_gather || grad_gather_ok(*bd, r),
+              "gnc_mlp_backward_f32: grad_gather is not honoured for this description (gnc_mlp_backward_grad_gather_honoured)");
+  GNC_REQUIRE(bd->grad_out || bd->grad_gather, "gnc_mlp_backward_f32: grad_out is null");
+  GNC_REQUIRE(!bd->grad_out || (bd->ld_grad_out % 4 == 0 && al16(bd->grad_out) && bd->ld_grad_out >= d.out_dim[2]),
+              "gnc_mlp_backward_f32: grad_out must be 16-B aligned with ld %% 4 == 0");
+  GNC_REQUIRE(!bd->dx || bd->ld_dx >= d.in_dim[0], "gnc_mlp_backward_f32: ld_dx < in_dim[0]");
+  BwdArgs fb = {};
+  fb.gg = bd->grad_gather;
+  fb.gg_index = bd->grad_gather_index;
+  fb.ld_gg = bd->ld_grad_gather;
+  fb.gg_rows = bd->grad_gather_rows;
+  fb.g_sum = bd->grad_sum;
+  fb.ld_g_sum = bd->ld_grad_sum;
+  GNC_REQUIRE(!(bd->grad_gather && bd->grad_out && bd->dx && bd->dx_add_grad_out) ||
+                  (bd->grad_sum && al16(bd->grad_sum) && bd->ld_grad_sum % 4 == 0 && bd->ld_grad_sum >= d.out_dim[2]),
+              "gnc_mlp_backward_f32: grad_out + grad_gather with dx_add_grad_out needs the grad_sum scratch tensor");
+  fb.grad_out = bd->grad_out;
+  fb.ld_grad_out = bd->ld_grad_out;
+  fb.dz[0] = bd->dz[0];
+  fb.dx = bd->dx;
+  fb.ld_dx = bd->ld_dx;
+  fb.dx_add_grad_out = bd->dx_add_grad_out ? 1 : 0;
+  fb.ln_partial = d.ln_gamma ? bd->ln_partial : nullptr;
+  FusedOut fo = {};
+  for (int l = 0; l < 3; ++l) {
+    fo.dw[l] = bd->dw_partial[l];
+    fo.M[l] = d.out_dim[l];
+    fo.K[l] = l == 0 ? d.seg[0].width : d.in_dim[l];
   }
-  int nmm = 0, nadd = 0, T = 0;
-  BwdPlan pl;
-  if (bd->dw_partial[0]) {  // fused data + weight-gradient kernel
-    const int fn = fused_shape(d);
-    if (fn < 0) { gnc::set_error("gnc_mlp_backward_f32: dw_partial given but the shape is outside the fused kernel"); return GNC_ERR_UNSUPPORTED; }
-    GNC_REQUIRE(bd->dw_partial[1] && bd->dw_partial[2], "gnc_mlp_backward_f32: dw_partial[0..2] must all be given");
-    GNC_REQUIRE(!d.ln_gamma || bd->ln_partial, "gnc_mlp_backward_f32: the fused kernel needs ln_partial with LayerNorm");
-    GNC_REQUIRE(!bd->grad_gather || gnc_mlp_backward_grad_gather_honoured(bd) == 1,
-                "gnc_mlp_backward_f32: grad_gather is not honoured for this description (gnc_mlp_backward_grad_gather_honoured)");
-    GNC_REQUIRE(bd->grad_out || bd->grad_gather, "gnc_mlp_backward_f32: grad_out is null");
-    GNC_REQUIRE(!bd->grad_out || (bd->ld_grad_out % 4 == 0 && al16(bd->grad_out) && bd->ld_grad_out >= d.out_dim[2]),
-                "gnc_mlp_backward_f32: grad_out must be 16-B aligned with ld %% 4 == 0");
-    GNC_REQUIRE(!bd->dx || bd->ld_dx >= d.in_dim[0], "gnc_mlp_backward_f32: ld_dx < in_dim[0]");
-    BwdArgs fb = {};
-    fb.gg = bd->grad_gather;
-    fb.gg_index = bd->grad_gather_index;
-    fb.ld_gg = bd->ld_grad_gather;
-    fb.gg_rows = bd->grad_gather_rows;
-    fb.g_sum = bd->grad_sum;
-    fb.ld_g_sum = bd->ld_grad_sum;
-    GNC_REQUIRE(!(bd->grad_gather && bd->grad_out && bd->dx && bd->dx_add_grad_out) ||
-                    (bd->grad_sum && al16(bd->grad_sum) && bd->ld_grad_sum % 4 == 0 && bd->ld_grad_sum >= d.out_dim[2]),
-                "gnc_mlp_backward_f32: grad_out + grad_gather with dx_add_grad_out needs the grad_sum scratch tensor");
-    fb.grad_out = bd->grad_out;
-    fb.ld_grad_out = bd->ld_grad_out;
-    fb.dz[0] = bd->dz[0];
-    fb.dx = bd->dx;
-    fb.ld_dx = bd->ld_dx;
-    fb.dx_add_grad_out = bd->dx_add_grad_out ? 1 : 0;
-    fb.ln_partial = d.ln_gamma ? bd->ln_partial : nullptr;
-    FusedOut fo = {};
-    for (int l = 0; l < 3; ++l) {
-      fo.dw[l] = bd->dw_partial[l];
-      fo.M[l] = d.out_dim[l];
-      fo.K[l] = l == 0 ? d.seg[0].width : d.in_dim[l];
-    }
-    if (bd->act_given) {
-      GNC_REQUIRE(gnc_mlp_backward_saved_act_honoured(bd) == 1,
-                  "gnc_mlp_backward_f32: act_given is not honoured for this description (gnc_mlp_backward_saved_act_honoured)");
-      fb.act[0] = bd->act[0];
-      fb.act[1] = bd->act[1];
-      return launch_fused_saved(d, fb, fo, fn, (hipStream_t)stream_);
-    }
-    return launch_fused_recompute(d, fb, fo, fn, (hipStream_t)stream_);
+  if (r.saved) {
+    GNC_REQUIRE(saved_act_ok(*bd, r),
+                "gnc_mlp_backward_f32: act_given is not honoured for this description (gnc_mlp_backward_saved_act_honoured)");
+    fb.act[0] = bd->act[0];
+    fb.act[1] = bd->act[1];
+    return launch_fused_saved(d, fb, fo, r.fused_nadd, stream);
   }
-  if (bd->act_given && bwd_col16_supported(d)) return launch_bwd_col16(*bd, (hipStream_t)stream_);  // small batches, saved activations
-  if (bd->act_given && bwd_col16_persist_supported(d)) return launch_bwd_col16_persist(*bd, (hipStream_t)stream_);  // large batches at 128 features
+  return launch_fused_recompute(d, fb, fo, r.fused_nadd, stream);
+}
+
+// the data kernels of the split path (resident, stream32, stream16); with no kernel, the error
+int launch_data_route(const gnc_mlp_bwd_desc_t* bd, const BwdRoute& r, hipStream_t stream) {
+  const gnc_mlp_desc_t& d = bd->fwd;
   GNC_REQUIRE(!bd->grad_gather, "gnc_mlp_backward_f32: grad_gather is only honoured by the fused data + weight-gradient kernel");
-  const bool resident = bwd_shape(d, &nmm, &nadd, &T);
-  const bool saved = bd->act_given != 0;
-  GNC_REQUIRE(!saved || gnc_mlp_backward_saved_act_honoured(bd) == 1,
+  GNC_REQUIRE(!r.saved || saved_act_ok(*bd, r),
               "gnc_mlp_backward_f32: act_given is not honoured for this description (gnc_mlp_backward_saved_act_honoured)");
-  const bool stream32 = !resident && bwd_stream_plan(d, bd->dx != nullptr, &pl, &T, saved);
-  const bool stream16 = !resident && !stream32 && use_stream16(d, bd->dx != nullptr);
-  if (!resident && !stream32 && !stream16) {
+  if (r.kernel == BwdKernel::none) {
     gnc::set_error("gnc_mlp_backward_f32: shape outside the HIP backward kernels");
     return GNC_ERR_UNSUPPORTED;
   }
+  const bool resident = r.kernel == BwdKernel::resident;
   const int L = d.num_linear;
   GNC_REQUIRE(bd->grad_out && bd->ld_grad_out % 4 == 0 && al16(bd->grad_out) && bd->ld_grad_out >= d.out_dim[L - 1],
               "gnc_mlp_backward_f32: grad_out must be 16-B aligned with ld %% 4 == 0");
@@ -1328,26 +1358,26 @@ extern "C" int gnc_mlp_backward_f32(const gnc_mlp_bwd_desc_t* bd, void* stream_)
               "gnc_mlp_backward_f32: dx_add_grad_out needs a row-ordered last MATMUL segment as wide as the output");
   b.ln_partial = d.ln_gamma ? bd->ln_partial : nullptr;
 
-  if (stream16) return launch_bwd_stream16(d, b, (hipStream_t)stream_, saved);
-  if (!resident) {
-    hipStream_t st = (hipStream_t)stream_;
-    switch (T) {
-      case 1: return launch_bwd_stream<1, 4>(d, b, pl, st);
-      case 2: return launch_bwd_stream<2, 4>(d, b, pl, st);
+  if (r.kernel == BwdKernel::stream16) return launch_bwd_stream16(d, b, stream, r.saved);
+  if (r.kernel == BwdKernel::stream32) {
+    const BwdPlan& pl = r.plan;
+    switch (r.T) {
+      case 1: return launch_bwd_stream<1, 4>(d, b, pl, stream);
+      case 2: return launch_bwd_stream<2, 4>(d, b, pl, stream);
       default: {
-        const bool small = bwd_stream_waves(T, d.rows) == 2;
-        if (pl.saved) return small ? launch_bwd_stream<4, 2, true>(d, b, pl, st) : launch_bwd_stream<4, 8, true>(d, b, pl, st);
-        return small ? launch_bwd_stream<4, 2>(d, b, pl, st) : launch_bwd_stream<4, 8>(d, b, pl, st);
+        const bool small = r.waves == 2;
+        if (pl.saved) return small ? launch_bwd_stream<4, 2, true>(d, b, pl, stream) : launch_bwd_stream<4, 8, true>(d, b, pl, stream);
+        return small ? launch_bwd_stream<4, 2>(d, b, pl, stream) : launch_bwd_stream<4, 8>(d, b, pl, stream);
       }
     }
   }
+  const int T = r.T, nmm = r.nmm, nadd = r.nadd;
   const int total_chunks = nmm + (L - 1);
   const size_t smem =
       ((size_t)total_chunks * T * 32 * LDSW + (size_t)(L + 2) * T * 32 + (size_t)BWAVES * RPW * LDSW) * sizeof(float);
   if (smem > 160 * 1024) { gnc::set_error("gnc_mlp_backward_f32: weights do not fit in LDS"); return GNC_ERR_UNSUPPORTED; }
-  hipStream_t stream = (hipStream_t)stream_;
 #define GNC_BWD(HT_, NMM_, NADD_) return launch_bwd<HT_, NMM_, NADD_>(d, b, total_chunks, smem, grid, stream)
-  if (saved) return launch_bwd<2, 2, 0, true>(d, b, total_chunks, smem, grid, stream);  // (the support query admits only this shape)
+  if (r.saved) return launch_bwd<2, 2, 0, true>(d, b, total_chunks, smem, grid, stream);  // (the route admits only this shape)
   if (T == 2) {
     if (nadd == 2) GNC_BWD(2, 1, 2);
     if (nmm == 1) GNC_BWD(2, 1, 0);
@@ -1361,75 +1391,78 @@ extern "C" int gnc_mlp_backward_f32(const gnc_mlp_bwd_desc_t* bd, void* stream_)
 #undef GNC_BWD
 }
 
-extern "C" int gnc_mlp_backward_saved_act_honoured(const gnc_mlp_bwd_desc_t* bd) {
-  static const bool off = getenv("GNC_NO_SAVED_ACT") != nullptr;  // A/B switch: the backward recomputes the forward of every tile
-  if (off || !bd) return 0;
+}  // namespace
+
+extern "C" int gnc_mlp_backward_f32(const gnc_mlp_bwd_desc_t* bd, void* stream_) {
+  if (!bd) { gnc::set_error("gnc_mlp_backward_f32: null descriptor"); return GNC_ERR_INVALID_ARGUMENT; }
   const gnc_mlp_desc_t& d = bd->fwd;
-  if (validate_desc(&d, false) != GNC_OK) return 0;
-  for (int l = 0; l < d.num_linear - 1; ++l)  // contiguous [rows, out_dim[l]] rows read as 16-B pieces
-    if (!bd->act[l] || !al16(bd->act[l]) || d.out_dim[l] % 4 != 0) return 0;
-  if (bd->dw_partial[0]) return fused_shape(d) >= 0 ? 1 : 0;  // fused data + weight-gradient kernel (widths <= 64)
-  if (d.num_linear >= 2 && bwd_col16_supported(d)) return 1;     // small batches: the column-split data kernel
-  if (bwd_col16_persist_supported(d)) return 1;
-  // split path: the streaming kernels read them (and gnc_xty_f32 after them); the weights-resident data kernel recomputes
-  int nmm, nadd, T;
-  BwdPlan pl;
-  if (d.num_linear < 2) return 0;
-  // weights-resident data kernel: a SAVED instance exists for the node processors' shape (widths 33..64, two MATMUL segments)
-  if (bwd_shape(d, &nmm, &nadd, &T)) return (T == 2 && nmm == 2 && nadd == 0) ? 1 : 0;
-  // SAVED instances exist for the 65..128 class of the 32-row kernel and for the 16-row kernel (129..256)
-  if (bwd_stream_plan(d, bd->dx != nullptr, &pl, &T, true)) return T == 4 ? 1 : 0;
-  return use_stream16(d, bd->dx != nullptr) ? 1 : 0;
+  int rc = validate_desc(&d, false);
+  if (rc) return rc;
+  if (d.ef_pos) {  // the backward reads the segment's rows (dW_0): a training forward materialises them (gnc_edge_features_f32)
+    gnc::set_error("gnc_mlp_backward_f32: fwd.ef_pos (computed edge features) is an inference-only form");
+    return GNC_ERR_UNSUPPORTED;
+  }
+  const bool fused_asked = bd->dw_partial[0] != nullptr;
+  const BwdRoute r = bwd_route(d, bd->dx != nullptr, fused_asked, bd->act_given != 0);
+  hipStream_t stream = (hipStream_t)stream_;
+  switch (r.kernel) {
+    case BwdKernel::fused: return launch_fused_route(bd, r, stream);
+    case BwdKernel::col16: return launch_bwd_col16(*bd, stream);                  // small batches, saved activations
+    case BwdKernel::col16_persist: return launch_bwd_col16_persist(*bd, stream);  // large batches at 128 features
+    case BwdKernel::resident: case BwdKernel::stream32: case BwdKernel::stream16: break;
+    case BwdKernel::none:
+      if (fused_asked) { gnc::set_error("gnc_mlp_backward_f32: dw_partial given but the shape is outside the fused kernel"); return GNC_ERR_UNSUPPORTED; }
+  }
+  return launch_data_route(bd, r, stream);
+}
+
+extern "C" size_t gnc_sizeof_mlp_bwd_desc(void) { return sizeof(gnc_mlp_bwd_desc_t); }
+
+extern "C" int gnc_mlp_backward_supported(const gnc_mlp_desc_t* fwd) {
+  int rc = validate_desc(fwd, false);
+  if (rc) return rc;
+  BwdRoute r = bwd_route_of_fwd(*fwd);
+  // this query has never counted the col16-persist kernel: a description that only it serves (its own test does not ask
+  // for ReLU or for 16-B rows of the tables and the first two matrices) is answered as without saved activations
+  if (r.kernel == BwdKernel::col16_persist) r = bwd_route(*fwd, true, false, false);
+  if (r.kernel == BwdKernel::none) {
+    gnc::set_error("gnc_mlp_backward: shape outside the HIP backward kernels (needs ReLU, widths <= 256, aligned tables)");
+    return GNC_ERR_UNSUPPORTED;
+  }
+  return GNC_OK;
+}
+
+extern "C" int gnc_mlp_backward_small_batch_supported(const gnc_mlp_desc_t* fwd) {
+  if (!fwd || validate_desc(fwd, false) != GNC_OK) return 0;
+  return bwd_route_of_fwd(*fwd).kernel == BwdKernel::col16 ? 1 : 0;
+}
+
+extern "C" int gnc_mlp_backward_dx_add_honoured(const gnc_mlp_desc_t* fwd) {
+  if (!fwd || validate_desc(fwd, false) != GNC_OK) return 0;
+  return bwd_route_of_fwd(*fwd).folds_dx_add ? 1 : 0;
+}
+
+extern "C" int gnc_mlp_backward_saved_act_honoured(const gnc_mlp_bwd_desc_t* bd) {
+  if (!bd || validate_desc(&bd->fwd, false) != GNC_OK) return 0;
+  // asked before act_given is set: the route is the one the launch takes once it is
+  return saved_act_ok(*bd, bwd_route(bd->fwd, bd->dx != nullptr, bd->dw_partial[0] != nullptr, true)) ? 1 : 0;
 }
 
 extern "C" int gnc_mlp_backward_grad_gather_honoured(const gnc_mlp_bwd_desc_t* bd) {
-  static const bool off = getenv("GNC_NO_GRAD_GATHER_FOLD") != nullptr;  // A/B switch: the caller gathers the rows itself
-  if (off || !bd || !bd->grad_gather || !bd->grad_gather_index) return 0;
-  if (!bd->dw_partial[0]) {  // split path: only the small-batch data kernel (saved activations) gathers in the launch
-    return (bd->act_given && gnc_mlp::validate_desc(&bd->fwd, false) == GNC_OK && (bwd_col16_supported(bd->fwd) || (bwd_col16_persist_supported(bd->fwd) && bd->fwd.in_dim[0] <= 128)) &&
-            bd->ld_grad_gather % 4 == 0 && al16(bd->grad_gather) && bd->ld_grad_gather >= bd->fwd.out_dim[bd->fwd.num_linear - 1])
-               ? 1 : 0;
-  }
-  const gnc_mlp_desc_t& d = bd->fwd;
-  if (validate_desc(&d, false) != GNC_OK || fused_shape(d) != 2) return 0;
-  // the fused kernel gathers with the ids of its second ADD segment (in the edge processor both are the destination)
-  if (bd->grad_gather_index != d.seg[2].index || bd->grad_gather_rows != d.seg[2].table_rows) return 0;
-  const int64_t bytes = bd->grad_gather_rows * (int64_t)bd->ld_grad_gather * 4;
-  if (bd->ld_grad_gather % 4 != 0 || !al16(bd->grad_gather) || bd->ld_grad_gather < d.out_dim[2]) return 0;
-  // ids one row past either table (rows beyond the end of the batch) must still be addressable in 32 bits
-  if (bytes + 256 > 0xffffffffll || d.seg[2].table_rows * (int64_t)d.seg[2].ld * 4 + 256 > 0xffffffffll) return 0;
-  return 1;
+  if (!bd || validate_desc(&bd->fwd, false) != GNC_OK) return 0;
+  return grad_gather_ok(*bd, bwd_route(bd->fwd, bd->dx != nullptr, bd->dw_partial[0] != nullptr, bd->act_given != 0)) ? 1 : 0;
 }
 
 extern "C" int gnc_mlp_backward_fused_rows(const gnc_mlp_desc_t* fwd) {
-  static const bool off = getenv("GNC_NO_FUSED_BACKWARD") != nullptr;  // A/B switch
-  if (off || !fwd || gnc_mlp::validate_desc(fwd, false) != GNC_OK || fused_shape(*fwd) < 0) return 0;
-  static_assert(kFusedSmem <= 160 * 1024, "fused backward kernel: LDS budget");
-  return fused_grid(fwd->rows) * FWAVES;
+  if (!fwd || validate_desc(fwd, false) != GNC_OK) return 0;
+  return bwd_route(*fwd, true, true, false).fused_rows;
 }
 
 extern "C" int gnc_mlp_backward_ln_partial_rows(const gnc_mlp_desc_t* fwd) {
-  if (!fwd || gnc_mlp::validate_desc(fwd, false) != GNC_OK || !fwd->ln_gamma) return 0;
-  static const bool off = getenv("GNC_NO_STREAM_LN_SUMS") != nullptr;  // A/B switch: the streaming kernels write y_hat again
-  // backward descriptions carry the forward's saved post-activations in fwd.save_act too (same pointers as act[]): with
-  // them a small batch runs the column-split data kernel, one partial row per 16-row tile
-  if (fwd->save_act[0] && fwd->num_linear >= 2 && bwd_col16_supported(*fwd)) return bwd_col16_ln_partial_rows(fwd->rows);
-  if (fwd->save_act[0] && bwd_col16_persist_supported(*fwd)) return bwd_col16_persist_ln_partial_rows(fwd->rows);
-  int nmm = 0, nadd = 0, T = 0;
-  if (bwd_shape(*fwd, &nmm, &nadd, &T)) return bwd_grid(fwd->rows) * BWAVES;
-  if (off) return 0;
-  // the streaming kernels: the answer must not depend on whether the caller will ask for dx (the chunk plans do)
-  BwdPlan pl;
-  int T0 = 0;
-  const bool s32 = bwd_stream_plan(*fwd, true, &pl, &T), s32_nodx = bwd_stream_plan(*fwd, false, &pl, &T0);
-  if (s32 != s32_nodx || (s32 && T != T0)) return 0;
-  if (s32) {  // the 32-row kernel: one row per wave of its grid
-    const int wv = bwd_stream_waves(T, fwd->rows);
-    const int64_t tiles = gnc::ceil_div(fwd->rows, (int64_t)wv * RPW);
-    return (int)(tiles < gnc::num_cu() ? tiles : gnc::num_cu()) * wv;
-  }
-  if (use_stream16(*fwd, true) && use_stream16(*fwd, false)) return bwd_stream16_ln_partial_rows(fwd->rows);
-  return 0;
+  if (!fwd || validate_desc(fwd, false) != GNC_OK) return 0;
+  // the answer must not depend on whether the caller will ask for dx (the chunk plans of the streaming kernels do)
+  const BwdRoute r = bwd_route_of_fwd(*fwd), nodx = bwd_route(*fwd, false, false, fwd->save_act[0] != nullptr);
+  return (r.kernel == nodx.kernel && r.T == nodx.T) ? r.ln_partial_rows : 0;
 }
 
 extern "C" int gnc_xty_partials(int64_t rows) {

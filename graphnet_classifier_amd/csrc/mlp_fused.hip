@@ -253,23 +253,97 @@ extern "C" size_t gnc_sizeof_mlp_desc(void) { return sizeof(gnc_mlp_desc_t); }
 
 extern "C" int gnc_mlp_supported(const gnc_mlp_desc_t* desc) { return validate_desc(desc, false); }
 
+namespace {
+
+// accumulator tiles (32 features each) of the hidden width; an output wider than 32 features that needs more raises it
+struct TileClass { int T; bool narrow_out; };
+TileClass tile_class(const gnc_mlp_desc_t& d) {
+  int T = tiles_for(d.out_dim[0]);
+  const int od = d.out_dim[d.num_linear - 1];
+  const bool narrow_out = od <= 32;
+  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
+  return {T, narrow_out};
+}
+
+// copy of a description with the aggregation epilogue asked for, for the shape queries: missing pointers are filled
+// (they are tested against null only, never dereferenced)
+gnc_mlp_desc_t agg_probe(const gnc_mlp_desc_t& d) {
+  static int32_t dummy_i;
+  static float dummy_f;
+  gnc_mlp_desc_t probe = d;
+  const int od = d.out_dim[d.num_linear - 1];
+  if (!probe.agg_out) probe.agg_out = &dummy_f;
+  if (!probe.agg_index) probe.agg_index = &dummy_i;
+  if (!probe.agg_fix) probe.agg_fix = &dummy_i;
+  if (probe.ld_agg < od) probe.ld_agg = od;
+  return probe;
+}
+
+enum class FwdKernel { none, col16, resident, stream16, stream, generic };
+
+// The one walk through the forward families, in order: col16 (small batches) -> resident (weights fit in LDS) ->
+// stream16 (129..256 features; at 65..128 for small batches, or with GNC_STREAM16_D128) -> stream (65..128) -> generic.
+// Every family decides for itself whether it takes the description (launch_*); this function only orders them and knows
+// which of them carry the aggregation epilogue at which tile class.  *which names the family that took it.
+// probe_only: nothing is launched, and finding no kernel is an answer (*which == none), not an error.
+int forward_chain(const gnc_mlp_desc_t& d, hipStream_t stream, bool probe_only, FwdKernel* which) {
+  static const bool s16_128 = getenv("GNC_STREAM16_D128") != nullptr;  // A/B: 16-row kernel also for 65..128 features
+  static const bool no_small16 = getenv("GNC_NO_SMALL16") != nullptr;  // A/B: small batches at 65..128 stay on 32-row tiles
+  const TileClass tc = tile_class(d);
+  const int T = tc.T;
+  const bool agg = d.agg_out != nullptr;
+  // Small batches at 65..128 features (one ~1000-node graph per call, main.py:60): a 32-row wave tile is 768 dependent
+  // v_mfma_f32_32x32x2 steps (49 k cycles, 20 us) whatever the batch; 16-row tiles on v_mfma_f32_16x16x4 in 2-wave
+  // workgroups halve that chain and spread the rows over twice as many SIMDs.
+  const bool small16 = !no_small16 && T == 4 && d.rows <= (int64_t)2 * 16 * gnc::num_cu();
+  *which = FwdKernel::none;
+  bool ok = false;
+  int rc = launch_col16(d, stream, &ok, probe_only);
+  if (rc || ok) { if (ok) *which = FwdKernel::col16; return rc; }
+  rc = launch_resident(d, T, tc.narrow_out, stream, &ok, probe_only);
+  if (rc || ok) { if (ok) *which = FwdKernel::resident; return rc; }
+  // the streaming kernels carry the epilogue at their own widths only: stream16 at T == 8 (and for small16), stream at T == 4
+  if (T == 8 || (T == 4 && s16_128 && !agg) || small16) {
+    rc = launch_stream16(d, stream, &ok, probe_only);
+    if (rc || ok) { if (ok) *which = FwdKernel::stream16; return rc; }
+  }
+  if (!agg || T == 4) {
+    rc = launch_stream(d, T, tc.narrow_out, stream, &ok, probe_only);  // wide layers: double-buffered weight stream
+    if (rc || ok) { if (ok) *which = FwdKernel::stream; return rc; }
+  }
+  if (agg || d.save_act[0]) {  // the generic kernel has neither
+    if (probe_only) return GNC_OK;
+    if (agg)
+      gnc::set_error("gnc_mlp_forward_f32: the fused aggregation epilogue is not available for this description "
+                     "(gnc_mlp_agg_supported)");
+    else
+      gnc::set_error("gnc_mlp_forward_f32: save_act is not available for this description (gnc_mlp_save_act_supported)");
+    return GNC_ERR_UNSUPPORTED;
+  }
+  *which = FwdKernel::generic;
+  if (probe_only) return GNC_OK;
+  switch (T * 2 + (tc.narrow_out ? 1 : 0)) {
+    case 1 * 2 + 0: case 1 * 2 + 1: return launch<1, 1>(d, stream);
+    case 2 * 2 + 0: return launch<2, 2>(d, stream);
+    case 2 * 2 + 1: return launch<2, 1>(d, stream);
+    case 4 * 2 + 0: return launch<4, 4>(d, stream);
+    case 4 * 2 + 1: return launch<4, 1>(d, stream);
+    case 8 * 2 + 0: return launch<8, 8>(d, stream);
+    case 8 * 2 + 1: return launch<8, 1>(d, stream);
+  }
+  gnc::set_error("gnc_mlp_forward_f32: no kernel for hidden width %d / out width %d", d.out_dim[0], d.out_dim[d.num_linear - 1]);
+  return GNC_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+
 // shape-only answer for the fused aggregation epilogue: would the weights-resident kernel take this description
 // with agg_out set?  (pointer fields are used for alignment / aliasing tests only, never dereferenced)
 extern "C" int gnc_mlp_agg_supported(const gnc_mlp_desc_t* desc) {
   int rc = validate_desc(desc, false);
   if (rc) return rc;
-  const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
-  gnc_mlp_desc_t probe = *desc;
-  int32_t dummy_i = 0;
-  float dummy_f = 0.f;
-  if (!probe.agg_out) probe.agg_out = &dummy_f;
-  if (!probe.agg_index) probe.agg_index = &dummy_i;
-  if (!probe.agg_fix) probe.agg_fix = &dummy_i;
-  if (probe.ld_agg < od) probe.ld_agg = od;
+  const auto [T, narrow_out] = tile_class(*desc);
+  const gnc_mlp_desc_t probe = agg_probe(*desc);
   bool ok = false;
   {  // small batches: the column-split kernel serves the launch WITHOUT the epilogue, and K1 on its rows afterwards
      // (scatter_sum_csr_small) is cheaper than the epilogue's fix-up + zero-fill launches
@@ -306,18 +380,8 @@ extern "C" int gnc_mlp_agg_supported(const gnc_mlp_desc_t* desc) {
 extern "C" int gnc_mlp_agg_only_supported(const gnc_mlp_desc_t* desc) {
   int rc = gnc_mlp_agg_supported(desc);
   if (rc) return rc;
-  const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
-  gnc_mlp_desc_t probe = *desc;
-  int32_t dummy_i = 0;
-  float dummy_f = 0.f;
-  if (!probe.agg_out) probe.agg_out = &dummy_f;
-  if (!probe.agg_index) probe.agg_index = &dummy_i;
-  if (!probe.agg_fix) probe.agg_fix = &dummy_i;
-  if (probe.ld_agg < od) probe.ld_agg = od;
+  const auto [T, narrow_out] = tile_class(*desc);
+  const gnc_mlp_desc_t probe = agg_probe(*desc);
   bool ok = false;
   rc = launch_resident(probe, T, narrow_out, nullptr, &ok, true, true);
   if (rc) return rc;
@@ -339,11 +403,7 @@ extern "C" int gnc_mlp_forward_agg_only_f32(const gnc_mlp_desc_t* desc, void* st
   rc = gnc_mlp_agg_only_supported(desc);
   if (rc) return rc;
   if (desc->rows == 0) return GNC_OK;
-  const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
+  const auto [T, narrow_out] = tile_class(*desc);
   bool launched = false;
   rc = launch_resident(*desc, T, narrow_out, (hipStream_t)stream, &launched, false, true);
   if (!rc && !launched) {
@@ -353,46 +413,21 @@ extern "C" int gnc_mlp_forward_agg_only_f32(const gnc_mlp_desc_t* desc, void* st
   return rc;
 }
 
-// shape-only answer for the training forward's saved post-activations: the weights-resident kernel writes them
-namespace {
-// Small batches at 65..128 features (one ~1000-node graph per call, main.py:60): a 32-row wave tile is 768 dependent
-// v_mfma_f32_32x32x2 steps (49 k cycles, 20 us) whatever the batch; 16-row tiles on v_mfma_f32_16x16x4 in 2-wave
-// workgroups halve that chain and spread the rows over twice as many SIMDs.  GNC_NO_SMALL16=1 switches back for A/B runs.
-bool small16(const gnc_mlp_desc_t& d, int T) {
-  static const bool off = getenv("GNC_NO_SMALL16") != nullptr;
-  return !off && T == 4 && d.rows <= (int64_t)2 * 16 * gnc::num_cu();
-}
-}  // namespace
-
+// shape-only answer for the training forward's saved post-activations: every kernel of the chain but the generic one writes them
 extern "C" int gnc_mlp_save_act_supported(const gnc_mlp_desc_t* desc) {
   int rc = validate_desc(desc, false);
   if (rc) return rc;
   const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
   gnc_mlp_desc_t probe = *desc;
   alignas(16) static float dummy_f[4];
   for (int l = 0; l < L - 1; ++l)
     if (!probe.save_act[l]) probe.save_act[l] = dummy_f;
-  bool ok = false;
-  if (L >= 2) {  // the dispatch chain of gnc_mlp_forward_f32: column split, resident, 16-row streaming (129..256), 32-row streaming
-    rc = launch_col16(probe, nullptr, &ok, true);
+  FwdKernel k = FwdKernel::none;
+  if (L >= 2) {
+    rc = forward_chain(probe, nullptr, true, &k);
     if (rc) return rc;
-    if (!ok) rc = launch_resident(probe, T, narrow_out, nullptr, &ok, true);
-    if (rc) return rc;
-    static const bool s16_128 = getenv("GNC_STREAM16_D128") != nullptr;
-    if (!ok && (T == 8 || (T == 4 && s16_128 && !probe.agg_out) || small16(probe, T))) {
-      rc = launch_stream16(probe, nullptr, &ok, true);
-      if (rc) return rc;
-    }
-    if (!ok) {
-      rc = launch_stream(probe, T, narrow_out, nullptr, &ok, true);
-      if (rc) return rc;
-    }
   }
-  if (!ok) {
+  if (k == FwdKernel::none) {
     gnc::set_error("gnc_mlp_save_act_supported: needs >= 2 Linear layers with ReLU, hidden widths that are multiples of 4 "
                    "(at most 256) and aligned tables (the generic kernel does not write them)");
     return GNC_ERR_UNSUPPORTED;
@@ -408,19 +443,12 @@ extern "C" int gnc_mlp_save_act_supported(const gnc_mlp_desc_t* desc) {
 extern "C" int gnc_mlp_operands_in_place_supported(const gnc_mlp_desc_t* desc) {
   int rc = validate_desc(desc, false);
   if (rc) return rc;
-  const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
-  bool ok = false;
+  FwdKernel k = FwdKernel::none;
   if (desc->rows > 0) {
-    rc = launch_col16(*desc, nullptr, &ok, true);
-    if (rc) return rc;
-    if (!ok) rc = launch_resident(*desc, T, narrow_out, nullptr, &ok, true);
+    rc = forward_chain(*desc, nullptr, true, &k);
     if (rc) return rc;
   }
-  if (!ok) {
+  if (k != FwdKernel::col16 && k != FwdKernel::resident) {
     gnc::set_error("gnc_mlp_operands_in_place_supported: this description runs on a kernel that reads rows of 16-B pieces");
     return GNC_ERR_UNSUPPORTED;
   }
@@ -432,11 +460,7 @@ extern "C" int gnc_mlp_operands_in_place_supported(const gnc_mlp_desc_t* desc) {
 extern "C" int gnc_mlp_edge_features_supported(const gnc_mlp_desc_t* desc) {
   int rc = validate_desc(desc, false);
   if (rc) return rc;
-  const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
+  const auto [T, narrow_out] = tile_class(*desc);
   gnc_mlp_desc_t probe = *desc;
   alignas(16) static float dummy_f[4];
   static int32_t dummy_i[1];
@@ -470,12 +494,12 @@ extern "C" int gnc_mlp_edge_features_supported(const gnc_mlp_desc_t* desc) {
 extern "C" int gnc_mlp_small_batch_supported(const gnc_mlp_desc_t* desc) {
   int rc = validate_desc(desc, false);
   if (rc) return rc;
-  bool ok = false;
+  FwdKernel k = FwdKernel::none;
   if (desc->rows > 0) {
-    rc = launch_col16(*desc, nullptr, &ok, true);
+    rc = forward_chain(*desc, nullptr, true, &k);
     if (rc) return rc;
   }
-  if (!ok) {
+  if (k != FwdKernel::col16) {
     gnc::set_error("gnc_mlp_small_batch_supported: not a small-batch description (rows, widths <= 128, ReLU)");
     return GNC_ERR_UNSUPPORTED;
   }
@@ -487,16 +511,11 @@ extern "C" int gnc_mlp_forward_f32(const gnc_mlp_desc_t* desc, void* stream_) {
   if (rc) return rc;
   if (desc->rows == 0) return GNC_OK;
   hipStream_t stream = (hipStream_t)stream_;
-  const int L = desc->num_linear;
-  int T = tiles_for(desc->out_dim[0]);
-  const int od = desc->out_dim[L - 1];
-  const bool narrow_out = od <= 32;
-  if (!narrow_out && tiles_for(od) > T) T = tiles_for(od);
-
-  bool launched = false;
   if (desc->ef_pos) {  // K6 prologue (ABI 19): the weights-resident kernel only, and only where the query says so
     rc = gnc_mlp_edge_features_supported(desc);
     if (rc) return rc;
+    const auto [T, narrow_out] = tile_class(*desc);
+    bool launched = false;
     rc = launch_resident(*desc, T, narrow_out, stream, &launched);
     if (!rc && !launched) {
       gnc::set_error("gnc_mlp_forward_f32: ef_pos given but the weights-resident kernel did not take the launch");
@@ -504,47 +523,6 @@ extern "C" int gnc_mlp_forward_f32(const gnc_mlp_desc_t* desc, void* stream_) {
     }
     return rc;
   }
-  rc = launch_col16(*desc, stream, &launched);  // small batches at 65..128 features: column-split workgroups
-  if (rc || launched) return rc;
-  rc = launch_resident(*desc, T, narrow_out, stream, &launched);  // weights-resident variant (decides by LDS fit)
-  if (rc || launched) return rc;
-  if (desc->agg_out && T != 4 && T != 8) {
-    gnc::set_error("gnc_mlp_forward_f32: the fused aggregation epilogue is not available for this description "
-                   "(gnc_mlp_agg_supported)");
-    return GNC_ERR_UNSUPPORTED;
-  }
-  static const bool s16_128 = getenv("GNC_STREAM16_D128") != nullptr;  // A/B: 16-row kernel also for 65..128 features
-  // 129..256 features: 16-row tiles on the 16x16x4 MFMA; 65..128 features: its 2-wave instances for small batches (small16)
-  if (T == 8 || (T == 4 && s16_128 && !desc->agg_out) || small16(*desc, T)) {
-    rc = launch_stream16(*desc, stream, &launched);
-    if (rc || launched) return rc;
-    if (desc->agg_out && T == 8) {
-      gnc::set_error("gnc_mlp_forward_f32: the fused aggregation epilogue is not available for this description "
-                     "(gnc_mlp_agg_supported)");
-      return GNC_ERR_UNSUPPORTED;
-    }
-  }
-  rc = launch_stream(*desc, T, narrow_out, stream, &launched);  // wide layers: double-buffered weight stream
-  if (rc || launched) return rc;
-  if (desc->agg_out) {
-    gnc::set_error("gnc_mlp_forward_f32: the fused aggregation epilogue is not available for this description "
-                   "(gnc_mlp_agg_supported)");
-    return GNC_ERR_UNSUPPORTED;
-  }
-  if (desc->save_act[0]) {
-    gnc::set_error("gnc_mlp_forward_f32: save_act is not available for this description (gnc_mlp_save_act_supported)");
-    return GNC_ERR_UNSUPPORTED;
-  }
-
-  switch (T * 2 + (narrow_out ? 1 : 0)) {
-    case 1 * 2 + 0: case 1 * 2 + 1: return launch<1, 1>(*desc, stream);
-    case 2 * 2 + 0: return launch<2, 2>(*desc, stream);
-    case 2 * 2 + 1: return launch<2, 1>(*desc, stream);
-    case 4 * 2 + 0: return launch<4, 4>(*desc, stream);
-    case 4 * 2 + 1: return launch<4, 1>(*desc, stream);
-    case 8 * 2 + 0: return launch<8, 8>(*desc, stream);
-    case 8 * 2 + 1: return launch<8, 1>(*desc, stream);
-  }
-  gnc::set_error("gnc_mlp_forward_f32: no kernel for hidden width %d / out width %d", desc->out_dim[0], od);
-  return GNC_ERR_UNSUPPORTED;
+  FwdKernel k;
+  return forward_chain(*desc, stream, false, &k);
 }

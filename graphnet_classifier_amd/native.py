@@ -692,20 +692,25 @@ def _prepare_mlp(segments, weights, biases, residual, rows, modes, vector_rows: 
 SAVE_ACT = os.environ.get("GNC_NO_SAVED_ACT") is None  # A/B switch: training forwards keep nothing, backwards recompute
 
 
+def _saved_act_honoured(lib, desc, act_ptrs, need_dx: bool, fused: bool) -> bool:
+    """gnc_mlp_backward_saved_act_honoured for the forward description ``desc`` with post-activations at ``act_ptrs``:
+    ``need_dx`` - the backward will be asked for the input gradient, ``fused`` - and for weight-gradient partials (the
+    kernel choice, and with it the answer, depends on both).  The query looks at the addresses' alignment only."""
+    bd = MlpBwdDesc()
+    ctypes.memmove(ctypes.byref(bd.fwd), ctypes.byref(desc), ctypes.sizeof(MlpDesc))
+    for l, ptr in enumerate(act_ptrs):
+        bd.act[l] = ptr
+    bd.act_given, bd.dx = 1, (act_ptrs[0] if need_dx else None)
+    bd.dw_partial[0] = act_ptrs[0] if fused else None
+    return lib.gnc_mlp_backward_saved_act_honoured(ctypes.byref(bd)) == 1
+
+
 def _backward_reads_saved_act(lib, desc, any_tensor, need_dx: bool = True) -> bool:
     """Would gnc_mlp_backward_f32 read saved post-activations for this description?  (Shape question only: the K8 kernel
     of some shapes - the weights-resident data kernel of the node processors - recomputes regardless, and a forward that
-    saved for it would write tensors nobody reads.)  ``need_dx``: whether that backward will be asked for the input
-    gradient (the kernel choice, and with it the answer, depends on it)."""
-    bd = MlpBwdDesc()
-    ctypes.memmove(ctypes.byref(bd.fwd), ctypes.byref(desc), ctypes.sizeof(MlpDesc))
-    ptr = any_tensor.data_ptr()  # any 16-B aligned device address: the query looks at alignment only
-    for l in range(desc.num_linear - 1):
-        bd.act[l] = ptr
-    bd.act_given, bd.dx = 1, (ptr if need_dx else None)
-    if lib.gnc_mlp_backward_fused_rows(ctypes.byref(bd.fwd)) > 0:
-        bd.dw_partial[0] = ptr
-    return lib.gnc_mlp_backward_saved_act_honoured(ctypes.byref(bd)) == 1
+    saved for it would write tensors nobody reads.)  ``any_tensor``: any 16-B aligned device tensor."""
+    fused = lib.gnc_mlp_backward_fused_rows(ctypes.byref(desc)) > 0
+    return _saved_act_honoured(lib, desc, [any_tensor.data_ptr()] * (desc.num_linear - 1), need_dx, fused)
 
 
 def mlp_forward(segments, weights, biases, ln=None, activation: str = "ReLU", act_param: float = 0.0,
@@ -1347,24 +1352,44 @@ def small_batch_kernel_serves(segments, weights, biases, ln=None, activation: st
 
 
 # --------------------------------------------------------------------------- K8 backward
+def _backward_desc(lib, segments, weights, biases, ln, activation, residual, rows, modes, saved_act):
+    """The forward description of a K8 launch or query: ``(desc, segs, w, b, residual, rows, unpadded)``.  A small batch
+    with saved activations is described as its operands lie first (``unpadded``, with them in ``desc.save_act``): its data
+    kernel reads them in place, no padded copies of the reference's 3-column inputs / first-layer weights (two pad launches
+    each); every other kernel gets rows of 16-B pieces."""
+    def describe(vector_rows):
+        segs, w, b, res, rows_, _ = _prepare_mlp(segments, weights, biases, residual, rows, modes, vector_rows=vector_rows)
+        dummy = torch.empty(1, w[-1].size(0), device=segs[0][0].device)
+        # (no residual: the backward never reads it)
+        return make_mlp_desc(segs, w, b, ln, activation, 0.0, None, dummy, rows_), segs, w, b, res, rows_
+
+    if saved_act and activation == "ReLU" and len(saved_act) == len(weights) - 1 and _rows_of(segments, rows) <= _small_batch_rows(lib):
+        unpadded = describe(False)
+        for l, a in enumerate(saved_act):
+            unpadded[0].save_act[l] = a.data_ptr()
+        if lib.gnc_mlp_backward_small_batch_supported(ctypes.byref(unpadded[0])) == 1:
+            return (*unpadded, True)
+    return (*describe(True), False)
+
+
+def _residual_is_last_matmul(segs, residual, out_width: int) -> bool:
+    """The residual is the last MATMUL segment handed to the kernel, row-ordered and as wide as the output: a kernel can
+    fold its gradient (grad_out) into the dx of that segment."""
+    if residual is None:
+        return False
+    table, index, width = [sg for sg in segs if sg[3] == SEG_MATMUL][-1][:3]
+    return index is None and table.data_ptr() == residual.data_ptr() and width == out_width
+
+
+# --------------------------------------------------------------------------- K8 backward
 def mlp_backward_supported(segments, weights, biases, ln, activation, residual, rows, modes=None, saved_act=None) -> bool:
     """Shape query of the HIP backward kernel (ReLU, widths <= 64, 2..7 Linear layers ...).  With ``saved_act`` a small batch
     is asked about as its operands lie (its data kernel needs no padded copies, so the query makes none either)."""
     lib = load_library()
     if activation not in ACTIVATIONS or not (1 <= len(weights) <= GNC_MAX_LINEAR) or len(segments) > GNC_MAX_SEGMENTS:
         return False
-    if saved_act and activation == "ReLU" and len(saved_act) == len(weights) - 1 and _rows_of(segments, rows) <= _small_batch_rows(lib):
-        segs, w, b, res, rows_, _ = _prepare_mlp(segments, weights, biases, residual, rows, modes, vector_rows=False)
-        dummy = torch.empty(1, w[-1].size(0), device=segs[0][0].device)
-        desc = make_mlp_desc(segs, w, b, ln, activation, 0.0, res, dummy, rows_)
-        for l, a in enumerate(saved_act):
-            desc.save_act[l] = a.data_ptr()
-        if lib.gnc_mlp_backward_small_batch_supported(ctypes.byref(desc)) == 1:
-            return True
-    segs, w, b, res, rows, _ = _prepare_mlp(segments, weights, biases, residual, rows, modes)
-    dummy = torch.empty(1, w[-1].size(0), device=segs[0][0].device)
-    desc = make_mlp_desc(segs, w, b, ln, activation, 0.0, res, dummy, rows)
-    return lib.gnc_mlp_backward_supported(ctypes.byref(desc)) == 0
+    desc, *_, unpadded = _backward_desc(lib, segments, weights, biases, ln, activation, residual, rows, modes, saved_act)
+    return unpadded or lib.gnc_mlp_backward_supported(ctypes.byref(desc)) == 0
 
 
 def mlp_backward(segments, weights, biases, ln, grad_out: torch.Tensor | None, rows: int | None = None, modes=None,
@@ -1388,52 +1413,31 @@ def mlp_backward(segments, weights, biases, ln, grad_out: torch.Tensor | None, r
     ``saved_act``: the list ``mlp_forward(save_act=...)`` filled for the same call; kernels that honour it
     (gnc_mlp_backward_saved_act_honoured) read the post-activations instead of recomputing them."""
     lib = load_library()
-    given = (segments, weights, biases, residual, rows, modes)
     bd = MlpBwdDesc()
-    unpadded = False
-    if saved_act and len(saved_act) == len(weights) - 1 and _rows_of(segments, rows) <= _small_batch_rows(lib):
-        # a small batch with saved activations: its data kernel reads the operands where they lie (no padded copies of the
-        # reference's 3-column inputs / first-layer weights: two pad launches each)
-        segs, w, b, residual, rows, _ = _prepare_mlp(*given, vector_rows=False)
-        dummy = torch.empty(1, w[-1].size(0), device=segs[0][0].device)
-        bd.fwd = make_mlp_desc(segs, w, b, ln, "ReLU", 0.0, None, dummy, rows)
-        for l, a in enumerate(saved_act):
-            bd.fwd.save_act[l] = a.data_ptr()
-        unpadded = lib.gnc_mlp_backward_small_batch_supported(ctypes.byref(bd.fwd)) == 1
-    if not unpadded:
-        segs, w, b, residual, rows, _ = _prepare_mlp(*given)
-        dummy = torch.empty(1, w[-1].size(0), device=segs[0][0].device)
-        bd.fwd = make_mlp_desc(segs, w, b, ln, "ReLU", 0.0, None, dummy, rows)
+    bd.fwd, segs, w, b, residual, rows, unpadded = _backward_desc(lib, segments, weights, biases, ln, "ReLU", residual, rows,
+                                                                   modes, saved_act)
     dev = segs[0][0].device
-    # residual given: ask the kernel to fold its gradient (grad_out) into the dx of the segment it came from
-    mm = [sg for sg in segs if sg[3] == SEG_MATMUL]
-    fold = (residual is not None and need_dx and mm[-1][1] is None and mm[-1][0].data_ptr() == residual.data_ptr()
-            and mm[-1][2] == w[-1].size(0) and lib.gnc_mlp_backward_dx_add_honoured(ctypes.byref(bd.fwd)) == 1)
-    bd.dx_add_grad_out = 1 if fold else 0
-    n_lin = len(w)
+    n_lin, out_w = len(w), w[-1].size(0)
+
+    def empty(n, width):
+        return torch.empty(n, width, dtype=torch.float32, device=dev)
+
+    # which kernel: the fused data + weight-gradient one (per-wave partials of dW_l / db_l and of the LayerNorm sums instead of
+    # the a_l / dz_l / y_hat tensors), or the split path (a data kernel that emits a_l and dz_l for gnc_xty_f32)
     frows = lib.gnc_mlp_backward_fused_rows(ctypes.byref(bd.fwd)) if fused else 0
-    parts = None
-    if frows > 0:
-        mk = [(w[l].size(0), w[l].size(1)) for l in range(n_lin)]
-        parts = [torch.empty(frows, m * k + m, dtype=torch.float32, device=dev) for m, k in mk]
-        for l in range(n_lin):
-            bd.dw_partial[l] = parts[l].data_ptr()
-    if saved_act:
+    fused = frows > 0
+    parts = [empty(frows, x.size(0) * x.size(1) + x.size(0)) for x in w] if fused else []
+    for l, part in enumerate(parts):
+        bd.dw_partial[l] = part.data_ptr()
+    # ... reading the forward's saved post-activations, where that kernel has them as inputs
+    if saved_act and len(saved_act) == n_lin - 1 and _saved_act_honoured(lib, bd.fwd, [a.data_ptr() for a in saved_act], need_dx, fused):
+        bd.act_given = 1
         for l, a in enumerate(saved_act):
             bd.act[l] = a.data_ptr()
-        bd.act_given = 1
-        bd.dx = 1 if need_dx else None  # (the query looks at whether dx is wanted; the real pointer follows below)
-        if len(saved_act) != n_lin - 1 or lib.gnc_mlp_backward_saved_act_honoured(ctypes.byref(bd)) != 1:
-            for l in range(len(saved_act)):
-                bd.act[l] = None
-            bd.act_given = 0
-        bd.dx = None
-        if bd.act_given:  # the shape queries that only see the forward description learn about the saved rows this way
-            for l, a in enumerate(saved_act):
-                bd.fwd.save_act[l] = a.data_ptr()
-            fold = (residual is not None and need_dx and mm[-1][1] is None and mm[-1][0].data_ptr() == residual.data_ptr()
-                    and mm[-1][2] == w[-1].size(0) and lib.gnc_mlp_backward_dx_add_honoured(ctypes.byref(bd.fwd)) == 1)
-            bd.dx_add_grad_out = 1 if fold else 0
+            bd.fwd.save_act[l] = a.data_ptr()  # the shape queries that only see the forward description learn of them this way
+    # residual given: ask the kernel to fold its gradient (grad_out) into the dx of the segment it came from
+    res_fold = _residual_is_last_matmul(segs, residual, out_w)
+    bd.dx_add_grad_out = int(need_dx and res_fold and (fused or lib.gnc_mlp_backward_dx_add_honoured(ctypes.byref(bd.fwd)) == 1))
     gt = gi = None
     if grad_gather is not None:
         gt, gi = _vector_rows(_rowmajor(grad_gather[0])), grad_gather[1]
@@ -1441,8 +1445,6 @@ def mlp_backward(segments, weights, biases, ln, grad_out: torch.Tensor | None, r
         bd.grad_gather_index, bd.grad_gather_rows = gi.data_ptr(), gt.size(0)
         # the residual's gradient is the EFFECTIVE output gradient: when the kernel cannot fold it into dx itself (the
         # residual went through a padded copy: width % 4 != 0), the caller adds it and needs the rows as a tensor
-        res_fold = (mm[-1][1] is None and residual is not None and mm[-1][0].data_ptr() == residual.data_ptr()
-                    and mm[-1][2] == w[-1].size(0))
         caller_adds_residual = residual is not None and need_dx and not res_fold
         if caller_adds_residual or lib.gnc_mlp_backward_grad_gather_honoured(ctypes.byref(bd)) != 1:  # gather in front of the launch (K2)
             grad_out = gather_rows(gt, gi) if grad_out is None else gather_rows_add(gt, gi, _rowmajor(grad_out))
@@ -1453,73 +1455,50 @@ def mlp_backward(segments, weights, biases, ln, grad_out: torch.Tensor | None, r
     g = (_rowmajor(grad_out) if unpadded else _vector_rows(_rowmajor(grad_out))) if grad_out is not None else None
     if g is not None:
         bd.grad_out, bd.ld_grad_out = g.data_ptr(), _ld(g)
-    g_sum = None
     g_eff = g if gt is None else None   # the effective output gradient as a tensor (None: part of it is gathered in the kernel)
     launch_ref = g if g is not None else gt
-    if frows > 0:
-        # fused data + weight-gradient kernel: per-wave partials of dW_l / db_l (and of the LayerNorm sums) instead of
-        # the a_l / dz_l / y_hat tensors; only dz_0 (gradient of gathered ADD segments) and dx are written
-        bd.dx_add_grad_out = 1 if (residual is not None and need_dx and mm[-1][1] is None
-                                   and mm[-1][0].data_ptr() == residual.data_ptr() and mm[-1][2] == w[-1].size(0)) else 0
+    g_sum = None
+    if fused:
         if gt is not None and g is not None and bd.dx_add_grad_out:  # scratch for the summed rows (see gnc_hip.h, grad_sum)
-            g_sum = torch.empty(rows, w[-1].size(0), dtype=torch.float32, device=dev)
+            g_sum = empty(rows, out_w)
             bd.grad_sum, bd.ld_grad_sum = g_sum.data_ptr(), _ld(g_sum)
-        dz0 = torch.empty(rows, w[0].size(0), dtype=torch.float32, device=dev) if len(segs) > 1 else None
-        if dz0 is not None:
-            bd.dz[0] = dz0.data_ptr()
-        dx = torch.empty(rows, w[0].size(1), dtype=torch.float32, device=dev) if need_dx else None
-        if dx is not None:
-            bd.dx, bd.ld_dx = dx.data_ptr(), _ld(dx)
-        ln_part = None
-        if ln is not None:
-            ln_part = torch.empty(frows, 2 * w[-1].size(0), dtype=torch.float32, device=dev)
-            bd.ln_partial = ln_part.data_ptr()
-        flops = 2.0 * rows * (3 * sum(x.size(0) * x.size(1) for x in w))
-        with torch.cuda.device(dev):
-            _check(_launch(f"mlp_backward_fused_in{w[0].size(1)}_h{w[0].size(0)}_out{w[-1].size(0)}_L{n_lin}", launch_ref,
-                           lambda: lib.gnc_mlp_backward_f32(ctypes.byref(bd), _stream(launch_ref)), flops), "gnc_mlp_backward_f32")
-        dws, dbs = [], []
-        for (m, k), part in zip(mk, parts):
-            tot = part.sum(dim=0)  # fixed order: reproducible
-            dws.append(tot[:m * k].view(m, k))
-            dbs.append(tot[m * k:])
-        ln_sums = None
-        if ln_part is not None:
-            tot = ln_part.sum(dim=0)
-            ln_sums = (tot[:w[-1].size(0)], tot[w[-1].size(0):])
-        return {"act": None, "dz": [dz0] + [None] * (n_lin - 1), "dx": dx, "yhat": None, "ln_sums": ln_sums, "dw": dws, "db": dbs,
-                "residual_folded": bool(bd.dx_add_grad_out), "grad_out": g_eff, "saved_act_used": bool(bd.act_given),
-                "_keep": (segs, w, b, g, gt, gi, g_sum, saved_act)}
-    # split path: the data kernel emits a_l (unless the forward saved them: act_given) and dz_l for gnc_xty_f32
-    act = list(saved_act) if bd.act_given else [torch.empty(rows, w[l].size(0), dtype=torch.float32, device=dev) for l in range(n_lin - 1)]
-    dz = [torch.empty(rows, w[l].size(0), dtype=torch.float32, device=dev) for l in range(n_lin)]
-    for l in range(n_lin):
-        bd.dz[l] = dz[l].data_ptr()
-        if l < n_lin - 1:
+        act = None  # only dz_0 (gradient of gathered ADD segments) and dx are written
+        dz = [empty(rows, w[0].size(0)) if len(segs) > 1 else None] + [None] * (n_lin - 1)
+    else:
+        act = list(saved_act) if bd.act_given else [empty(rows, w[l].size(0)) for l in range(n_lin - 1)]
+        dz = [empty(rows, w[l].size(0)) for l in range(n_lin)]
+        for l in range(n_lin - 1):
             bd.act[l] = act[l].data_ptr()
-    dx = torch.empty(rows, w[0].size(1), dtype=torch.float32, device=dev) if need_dx else None
+    for l in range(n_lin):
+        bd.dz[l] = dz[l].data_ptr() if dz[l] is not None else None
+    dx = empty(rows, w[0].size(1)) if need_dx else None
     if dx is not None:
         bd.dx, bd.ld_dx = dx.data_ptr(), _ld(dx)
     yhat = ln_part = None
     if ln is not None:
-        prow = lib.gnc_mlp_backward_ln_partial_rows(ctypes.byref(bd.fwd))
+        prow = frows if fused else lib.gnc_mlp_backward_ln_partial_rows(ctypes.byref(bd.fwd))
         if prow > 0:  # d gamma / d beta sums formed inside the data kernel: no y_hat tensor, no colsum pass
-            ln_part = torch.empty(prow, 2 * w[-1].size(0), dtype=torch.float32, device=dev)
+            ln_part = empty(prow, 2 * out_w)
             bd.ln_partial = ln_part.data_ptr()
         else:
-            yhat = torch.empty(rows, w[-1].size(0), dtype=torch.float32, device=dev)
+            yhat = empty(rows, out_w)
             bd.yhat = yhat.data_ptr()
-    flops = 2.0 * rows * (2 * sum(x.size(0) * x.size(1) for x in w))
+    flops = 2.0 * rows * ((3 if fused else 2) * sum(x.size(0) * x.size(1) for x in w))
     with torch.cuda.device(dev):
-        _check(_launch(f"mlp_backward_in{w[0].size(1)}_h{w[0].size(0)}_out{w[-1].size(0)}_L{n_lin}", launch_ref,
+        _check(_launch(f"mlp_backward{'_fused' if fused else ''}_in{w[0].size(1)}_h{w[0].size(0)}_out{out_w}_L{n_lin}", launch_ref,
                        lambda: lib.gnc_mlp_backward_f32(ctypes.byref(bd), _stream(launch_ref)), flops), "gnc_mlp_backward_f32")
-    ln_sums = None
-    if ln_part is not None and not defer_ln_sums:
+    r = {"act": act, "dz": dz, "dx": dx, "yhat": yhat, "ln_sums": None, "residual_folded": bool(bd.dx_add_grad_out),
+         "grad_out": g_eff, "saved_act_used": bool(bd.act_given), "_keep": (segs, w, b, g, gt, gi, g_sum, saved_act)}
+    if fused:
+        tots = [part.sum(dim=0) for part in parts]  # fixed order: reproducible
+        r["dw"] = [tot[:x.numel()].view(x.size(0), x.size(1)) for tot, x in zip(tots, w)]
+        r["db"] = [tot[x.numel():] for tot, x in zip(tots, w)]
+    else:
+        r["ln_part"] = ln_part if defer_ln_sums else None
+    if ln_part is not None and (fused or not defer_ln_sums):
         tot = ln_part.sum(dim=0)  # fixed order: reproducible
-        ln_sums = (tot[:w[-1].size(0)], tot[w[-1].size(0):])  # (d beta, d gamma)
-    return {"act": act, "dz": dz, "dx": dx, "yhat": yhat, "ln_sums": ln_sums, "ln_part": ln_part if defer_ln_sums else None,
-            "residual_folded": bool(bd.dx_add_grad_out), "grad_out": g_eff,
-            "saved_act_used": bool(bd.act_given), "_keep": (segs, w, b, g, gt, gi, saved_act)}
+        r["ln_sums"] = (tot[:out_w], tot[out_w:])  # (d beta, d gamma)
+    return r
 
 
 def _xty_spans(n: int, step: int):

@@ -249,6 +249,8 @@ typedef struct gnc_mlp_desc {
 /* sizeof(gnc_mlp_desc_t) as compiled into the library, for binding cross-checks. */
 size_t gnc_sizeof_mlp_desc(void);
 int gnc_mlp_supported(const gnc_mlp_desc_t* desc /* host */);
+/* The kernel family is chosen by one walk (forward_chain in mlp_fused.hip; the table in DESIGN.md, K4); the save_act,
+ * operands_in_place and small_batch queries below answer as routed by it. */
 int gnc_mlp_forward_f32(const gnc_mlp_desc_t* desc /* host */, void* stream);
 /* fused aggregation epilogue: 0 if this description can run with agg_out set (shape fields only) */
 int gnc_mlp_agg_supported(const gnc_mlp_desc_t* desc /* host */);
@@ -377,21 +379,23 @@ typedef struct gnc_mlp_bwd_desc {
 } gnc_mlp_bwd_desc_t;
 
 size_t gnc_sizeof_mlp_bwd_desc(void);
-int gnc_mlp_backward_supported(const gnc_mlp_desc_t* fwd /* host */);
-int gnc_mlp_backward_dx_add_honoured(const gnc_mlp_desc_t* fwd /* host */); /* 1 / 0 */
-/* ABI 18: 1 if the small-batch data kernel serves this backward with the operands exactly as they lie (fwd.save_act = the saved
- * post-activations): no 16-B-row copies of [N, 3] inputs / nn.Linear(3, H) weights are needed in front of it */
+/* The seven queries below all read the one routing decision gnc_mlp_backward_f32 itself launches by (bwd_route in
+ * mlp_backward.hip; the table in DESIGN.md, K8).  Those that take only `fwd` answer as routed by it for a launch that
+ * wants dx, with act_given where fwd.save_act[0] is set, on the split path (no dw_partial). */
+int gnc_mlp_backward_supported(const gnc_mlp_desc_t* fwd /* host */);       /* 0: some data kernel is routed */
+int gnc_mlp_backward_dx_add_honoured(const gnc_mlp_desc_t* fwd /* host */); /* 1: the routed kernel folds dx_add_grad_out */
+/* ABI 18: 1 if the routed kernel is the small-batch data kernel, which reads the operands exactly as they lie: no 16-B-row
+ * copies of [N, 3] inputs / nn.Linear(3, H) weights are needed in front of it */
 int gnc_mlp_backward_small_batch_supported(const gnc_mlp_desc_t* fwd /* host */);
-/* 1 if gnc_mlp_backward_f32 accepts desc->grad_gather for this description (grad_gather* and dw_partial filled in as
- * for the call), else 0: the caller then gathers the rows itself (gnc_gather_rows_f32 / gnc_gather_rows_add_f32) */
+/* 1 if the kernel routed for desc (grad_gather*, dw_partial, dx and act_given filled in as for the call) gathers
+ * desc->grad_gather in the launch, else 0: the caller gathers the rows itself (gnc_gather_rows_f32 / gnc_gather_rows_add_f32) */
 int gnc_mlp_backward_grad_gather_honoured(const gnc_mlp_bwd_desc_t* desc /* host */);
-/* 1 if gnc_mlp_backward_f32 accepts desc->act_given for this description (act[] and dw_partial filled in as for the call) */
+/* 1 if the kernel routed for desc with act_given (act[], dw_partial and dx filled in as for the call) reads act[] */
 int gnc_mlp_backward_saved_act_honoured(const gnc_mlp_bwd_desc_t* desc /* host */);
-/* rows of `ln_partial` this description needs, 0 if its backward kernel cannot form the LayerNorm sums in flight */
+/* rows of `ln_partial` the routed kernel fills, 0 if it cannot form the LayerNorm sums in flight (it writes yhat) */
 int gnc_mlp_backward_ln_partial_rows(const gnc_mlp_desc_t* fwd /* host */);
-/* rows of `dw_partial[l]` (and then also of `ln_partial`) if this description can run the fused data + weight-
- * gradient kernel (three Linear layers, widths <= 64, one row-ordered MATMUL segment and 0 or 2 gathered ADD
- * segments with stated tables), else 0 */
+/* rows of `dw_partial[l]` (and then also of `ln_partial`) if a launch with dw_partial is routed to the fused data +
+ * weight-gradient kernel, else 0 */
 int gnc_mlp_backward_fused_rows(const gnc_mlp_desc_t* fwd /* host */);
 int gnc_mlp_backward_f32(const gnc_mlp_bwd_desc_t* desc /* host */, void* stream);
 int gnc_xty_partials(int64_t rows);
