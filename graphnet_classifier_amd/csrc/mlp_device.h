@@ -405,11 +405,39 @@ __device__ __forceinline__ f32x8 lds_group(const float* abuf, int kg, int i, int
 // pipelined mma_chunk_from_lds_split for a compile-time count of K-groups.  The fp32 row group travels two K-groups ahead of
 // its MFMAs (its LDS round trip must be over before its split can start), the split and the weight fragments one.
 // `with_group(kg)` is called behind the MFMAs of K-group kg: instructions of the caller that are to ride along with them (the
-// W-split edge processor's gather requests); they share the K-group's scheduling region, and the last one is fenced too.
+// W-split edge processor's gather requests, its residual read-back and the staging of the gathered sums); they share the
+// K-group's scheduling region, and the last one is fenced too.
 struct no_group_work {
   __device__ __forceinline__ void operator()(int) const {}
 };
-template <int T, int NKG, class WithGroup = no_group_work>
+// RB / ST: work of `with_group` that is pinned into MFMA slots as well - RB 16-B LDS reads behind the first MFMAs of the
+// second-last K-group (two per slot), ST staged pieces (up to four vector instructions and one LDS write each) behind the
+// last ST MFMAs of the last K-group, whose slots carry no split of a next group.
+template <int NM, int NDS, int RB>
+__device__ __forceinline__ void pin_group_slots_reads() {
+#pragma unroll
+  for (int m = 0; m < NM; ++m) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    if (2 * m + 1 < RB) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    else if (2 * m < RB) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    if (m >= NM - NDS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int NM, int ST>
+__device__ __forceinline__ void pin_group_slots_staged() {
+#pragma unroll
+  for (int m = 0; m < NM; ++m) {
+    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+    if (m >= NM - ST) {
+      __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int T, int NKG, class WithGroup = no_group_work, int RB = 0, int ST = 0>
 __device__ __forceinline__ void mma_chunk_from_lds_split_pipe(f32x16 (&acc)[T], const float* abuf, const __bf16* wsp, int i, int h,
                                                               WithGroup with_group = WithGroup()) {
   static_assert(NKG >= 1 && NKG <= 4, "K-groups of one staged 64-column tile");
@@ -429,7 +457,10 @@ __device__ __forceinline__ void mma_chunk_from_lds_split_pipe(f32x16 (&acc)[T], 
     mma_group_frags<T>(acc, x, w);
     with_group(kg);
     if (kg + 2 < NKG) pin_group_slots<6 * T, (3 * T + 2 < 6 * T ? 3 * T + 2 : 6 * T)>();
-    else if (kg + 1 < NKG) pin_group_slots<6 * T, 3 * T>();
+    else if (kg + 1 < NKG) {
+      if constexpr (RB > 0) pin_group_slots_reads<6 * T, 3 * T, RB>();
+      else pin_group_slots<6 * T, 3 * T>();
+    } else if constexpr (ST > 0) pin_group_slots_staged<6 * T, ST>();
     else if constexpr (!__is_same(WithGroup, no_group_work)) __builtin_amdgcn_sched_barrier(0);
     x = xn;
     w = wn;

@@ -14,7 +14,8 @@
 //                         issued from INSIDE the last MATMUL step's MFMA loop, one 4-row piece per
 //                         k-group (a wave's LDS / VMEM / scalar instructions ride in the shadow of its
 //                         own MFMAs; in front of the loop they would crawl whenever the SIMD mate is
-//                         in an MFMA phase);
+//                         in an MFMA phase); the pipelined fixed-width edge instances request all of them behind
+//                         the first two k-groups and stage the sums behind the last one (FRONT, below);
 //   the first step's rows of the NEXT tile are requested right after that and have the
 //   remaining Linear layers, LayerNorm and epilogue (>= 8k cycles) to land.  Gather ids are
 //   fetched one tile earlier still, with one coalesced load per segment and tile.
@@ -140,6 +141,15 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
   // their launches measured no faster with it.  A first Linear with Linears behind it is pipelined
   // when its staged segment is 64 wide (tested per launch).
   constexpr bool PIPE = SPLIT != 0 && SPK && !DUAL && (FULL || (SPLIT == 2 && NMM == 1) || (SPLIT == 1 && NADD == 0));
+  // FRONT (the pipelined FULL edge instances, storing and aggregate-only): the request schedule of the gathered ADD rows.
+  // GPK = 4-row pieces of each table requested behind one K-group of the interleaved first Linear.  The even share (two per
+  // K-group) issues the last four of the sixteen loads behind the last MFMAs of the phase, a few instructions before the ADD
+  // step adds them.  FRONT requests four pieces of each table behind K-group 0 and four behind K-group 1, reads the residual
+  // back from the staged tile behind K-group 2 (the tile is read for the last time two K-groups ahead) and stages the sums
+  // of the gathered pieces behind the MFMAs of K-group 3, whose slots carry no split of a next group.  Same loads, adds and
+  // LDS accesses on the same operands, placed elsewhere ("request schedule"; §4 `r08`).
+  constexpr bool FRONT = GADD && SPLIT == 1 && PIPE;
+  constexpr int GPK = FRONT ? 4 : 2;
   __bf16* const wsp = reinterpret_cast<__bf16*>(lds + nf32 * CH);
   auto wsplit = [&](int chunk) -> const __bf16* { return wsp + (chunk - nf32) * 3 * SPLANE; };
   constexpr int PSTRIDE = WT * 32;
@@ -399,12 +409,13 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
             const uint32_t cola = (uint32_t)(c4 * 4 < sa.ld ? c4 * 16 : 0), colb = (uint32_t)(c4 * 4 < sb.ld ? c4 * 16 : 0);
             const int rba = (int)(offs[NMM] * (uint32_t)(sa.ld * 4)), rbb = (int)(offs[NMM + 1] * (uint32_t)(sb.ld * 4));
             int na = __shfl(rba, rs, 64), nb = __shfl(rbb, rs, 64);
-            if constexpr (SPLIT == 1) {  // two pieces of each table per 16-k group
+            if constexpr (SPLIT == 1) {  // GPK pieces of each table per 16-k group
               const __bf16* wch = wsplit(s);
-              // one K-group's gather requests: two pieces of each table
+              // one K-group's gather requests: GPK pieces of each table behind K-groups 0 .. 8 / GPK - 1, none behind the
+              // rest (GPK = 2: one even share per group)
               auto request = [&](int kg) {
 #pragma unroll
-                for (int g = 2 * kg; g < 2 * kg + 2; ++g) {
+                for (int g = GPK * kg; g < GPK * kg + GPK && g < 8; ++g) {
                   const uint32_t oa = (uint32_t)na + cola, ob = (uint32_t)nb + colb;
                   if (g + 1 < 8) {
                     na = __shfl(rba, (g + 1) * 4 + rs, 64);
@@ -414,7 +425,29 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
                   addB[g] = window_load(wb, ob);
                 }
               };
-              if constexpr (PIPE) {  // the staged segment is 64 wide here: four K-groups, kg's requests riding along with its MFMAs
+              if constexpr (FRONT) {
+                // The tile's rows are read for the last time two K-groups ahead, so the residual's read-back rides with
+                // K-group 2 and the sums of the gathered pieces are staged behind the MFMAs of K-group 3.
+                auto request_stage = [&](int kg) {
+                  request(kg);
+                  if (kg == 2) {
+#pragma unroll
+                    for (int t = 0; t < HT; ++t)
+#pragma unroll
+                      for (int q = 0; q < 4; ++q) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(abuf + i * LDSW + 32 * t + 8 * q + 4 * h);
+                        res[t][4 * q + 0] = v.x; res[t][4 * q + 1] = v.y; res[t][4 * q + 2] = v.z; res[t][4 * q + 3] = v.w;
+                      }
+                  }
+                  if (kg == 3) {
+                    compiler_lds_barrier();
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) *reinterpret_cast<f32x4*>(abuf + (p * 4 + rs) * LDSW + c4 * 4) = addA[p] + addB[p];
+                    compiler_lds_barrier();
+                  }
+                };
+                mma_chunk_from_lds_split_pipe<HT, 4, decltype(request_stage), 4 * HT, NP>(hid, abuf, wch, i, h, request_stage);
+              } else if constexpr (PIPE) {  // the staged segment is 64 wide here: four K-groups, kg's requests riding along with its MFMAs
                 mma_chunk_from_lds_split_pipe<HT, 4>(hid, abuf, wch, i, h, request);
               } else {
 #pragma unroll
@@ -475,7 +508,7 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
         }
         else mma_chunk_from_lds<HT>(hid, abuf, wres + s * CH, (sv[s].width + 7) >> 3, i, h);
       }
-      if constexpr (RESREG) if (s == NMM - 1) {
+      if constexpr (RESREG && !FRONT) if (s == NMM - 1) {
 #pragma unroll
         for (int t = 0; t < HT; ++t)
 #pragma unroll
@@ -487,10 +520,12 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       PROBE(1);  // load issue + first-Linear MFMAs
     }
     if constexpr (NADD > 0) {
-      f32x4 sum[NP];
+      if constexpr (!FRONT) {
+        f32x4 sum[NP];
 #pragma unroll
-      for (int p = 0; p < NP; ++p) sum[p] = addA[p] + addB[p];
-      stage(sum, sv[NMM].width);
+        for (int p = 0; p < NP; ++p) sum[p] = addA[p] + addB[p];
+        stage(sum, sv[NMM].width);
+      }
       load_rows(cur, sv[0], nwt, off0);  // next tile's first step: the rest of this tile to land
       off0 = row_offset(nwt + stride, sv[0]);
       add_tile_from_lds<HT>(hid, abuf, i, h);
