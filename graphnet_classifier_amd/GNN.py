@@ -284,6 +284,9 @@ class GraphProcessor(nn.Module):
         """models/GNN.py:213-216; ``edge_attr`` in and out in the caller's edge order."""
         if len(self.blocks) == 0:
             return x, edge_attr
+        if getattr(self, "pools", None):
+            raise ValueError("GraphProcessor.forward: top-K pooling (pool_ratio) changes the node and edge sets; call "
+                             "GraphNet.forward / forward_device")
         dev = require_gpu_param(next(self.parameters()), "GraphProcessor")
         back = x.device
         x = x.to(device=dev, dtype=torch.float32)
@@ -296,12 +299,60 @@ class GraphProcessor(nn.Module):
             x, edge_attr = x.to(back), edge_attr.to(back)
         return x, edge_attr
 
-    def forward_sorted(self, x, topo: GraphTopology, edge_attr, need_edges: bool = True):
-        """``need_edges=False``: the caller drops the edge output; the last block may then return None for it."""
+    def forward_sorted(self, x, topo: GraphTopology, edge_attr, need_edges: bool = True, graph_ptr: Tensor | None = None,
+                       return_pooling: bool = False):
+        """``need_edges=False``: the caller drops the edge output; the last block may then return None for it.
+
+        With pooling layers (``self.pools``, attached by ``GraphNet(pool_ratio=...)``): behind block k its ``TopKPool`` erases
+        nodes, and the blocks after it run on the pooled rows and the pooled topology.  ``graph_ptr``: DEVICE int64 [G + 1]
+        (None = all rows are one graph).  ``return_pooling=True``: ``(x, edge_attr, graph_ptr', kept)`` with the offsets of the
+        pooled graphs and ``kept`` int32 [N'], the survivors' ORIGINAL rows (composed over the layers; None without pooling)."""
+        pools = getattr(self, "pools", None)
         last = len(self.blocks) - 1
+        kept = None
         for k, block in enumerate(self.blocks):
             x, edge_attr = block.forward_sorted(x, topo, edge_attr, need_edges=need_edges or k < last)
+            if pools and str(k) in pools:
+                if graph_ptr is None:
+                    graph_ptr = torch.arange(2, dtype=torch.int64, device=x.device) * x.size(0)  # [0, N], built on the device
+                # behind the last block nothing reads the pooled edges: nodes only
+                x, edge_attr, pooled_topo, graph_ptr, here = pools[str(k)].forward_sorted(x, topo, edge_attr, graph_ptr,
+                                                                                          need_edges=need_edges or k < last)
+                topo = pooled_topo if pooled_topo is not None else topo
+                if return_pooling:
+                    kept = here if kept is None else kept[here.long()]
+        if return_pooling:
+            return x, edge_attr, graph_ptr, kept
         return x, edge_attr
+
+
+# --------------------------------------------------------------------------- K20 top-K node pooling
+class TopKPool(nn.Module):
+    """The pooling layer of the write-up's GN block (K20): ``score(v) = W2 relu(W1 h_v + b1) + b2`` from ``self.gate`` - an
+    ``MLP(in_dim, 1, hidden_dim=hidden)`` with one hidden layer and no norm, on the fused-MLP kernels over all rows - then, per
+    graph, the ``k = min(n, max(1, ceil(ratio n)))`` best nodes are kept in their old order and gated, ``h'_v = h_v tanh(score(v))``
+    (``functional.topk_pool``).  One host read-back of the pooled sizes per call."""
+
+    def __init__(self, in_dim: int, ratio: float, hidden: int = 32):
+        super().__init__()
+        self.ratio = native._check_ratio(ratio, "TopKPool")
+        self.gate = MLP(in_dim, 1, hidden_dim=int(hidden), hidden_layers=1, activation="ReLU", norm_type=None)
+
+    def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor | None, graph_ptr: Tensor, need_edges: bool = True):
+        """``(x', edge_attr', topo', graph_ptr', kept)`` on a prepared topology; ``edge_attr`` in its sorted edge order."""
+        scores = self.gate.forward_segments([(x, None)]).view(-1)
+        return Fn.topk_pool(x, scores, topo, graph_ptr, self.ratio, edge_attr if need_edges else None, need_edges=need_edges)
+
+
+def uses_node_pooling(model: nn.Module) -> bool:
+    """True when ``model`` holds a ``TopKPool``: its forward reads sizes back from the device, so it cannot be captured."""
+    return any(isinstance(m, TopKPool) for m in model.modules())
+
+
+def _no_capture_with_pooling(model: nn.Module, who: str) -> None:
+    if uses_node_pooling(model):
+        raise ValueError(f"{who}: top-K node pooling (GraphNet(pool_ratio=...)) reads the pooled node and edge counts back from the "
+                         f"device in every pooling layer, which a hipGraph capture cannot record; run this model eagerly")
 
 
 # --------------------------------------------------------------------------- a7 GraphNet
@@ -333,6 +384,21 @@ class GraphNet(nn.Module):
         initializer = kwargs.get("initializer", None)
         # "sum" (the reference's code), "mean" (its write-up) or "max"; any other value is an error, never a silent sum
         aggregation = _check_aggregation(kwargs.get("aggregation", "sum"), "GraphNet")
+        # K20: top-K node pooling behind the GN blocks (the write-up's "Pooling(h(k))").  None: no pooling, no module, no keys.
+        pool_ratio, pool_after, pool_hidden = kwargs.get("pool_ratio"), kwargs.get("pool_after"), kwargs.get("pool_hidden")
+        if pool_ratio is None:
+            if pool_after is not None or pool_hidden is not None:
+                raise ValueError("GraphNet: pool_after / pool_hidden belong to pool_ratio, which is None")
+        else:
+            pool_ratio = native._check_ratio(pool_ratio, "GraphNet(pool_ratio=...)")
+            pool_after = list(range(n_blocks)) if pool_after is None else list(pool_after)
+            if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < n_blocks for i in pool_after) \
+                    or len(set(pool_after)) != len(pool_after):
+                raise ValueError(f"GraphNet: pool_after {pool_after!r} must hold distinct block indices in [0, {n_blocks})")
+            pool_after = sorted(pool_after)
+            pool_hidden = 32 if pool_hidden is None else int(pool_hidden)
+            if pool_hidden < 1:
+                raise ValueError(f"GraphNet: pool_hidden {pool_hidden} must be positive")
 
         self.name = "GraphNet"
         self.out_dim = out_dim
@@ -348,18 +414,46 @@ class GraphNet(nn.Module):
                                               hidden_layers_processor_edge, activation=activation,
                                               initializer=initializer, norm_type=norm_type, aggregation=aggregation)
         self.node_decoder = MLP(out_dim_node, out_dim, hidden_dim_decoder, hidden_layers_decoder, norm_type=None)
+        # the pools LAST: every other parameter draws the random numbers it draws without them (graph_processor.pools.<i>.gate.*)
+        self.pool_ratio, self.pool_after = pool_ratio, tuple(pool_after) if pool_ratio is not None else ()
+        if pool_ratio is not None and self.pool_after:
+            self.graph_processor.pools = nn.ModuleDict({str(i): TopKPool(out_dim_node, pool_ratio, pool_hidden) for i in self.pool_after})
 
-    def forward_device(self, x: Tensor, pos: Tensor, topo: GraphTopology) -> Tensor:
-        """GraphNet.forward on device tensors with a prepared topology (models/GNN.py:297-309)."""
+    @property
+    def pooling(self) -> bool:
+        """True when top-K pooling layers sit between the GN blocks: the output then has fewer rows than the input."""
+        return bool(self.pool_after)
+
+    def pooled_nodes(self, n: int) -> int:
+        """Rows the output holds for ONE graph of ``n`` nodes: ``k = min(n, max(1, ceil(ratio n)))`` applied once per pooling layer."""
+        n = int(n)
+        for _ in self.pool_after:
+            n = native.topk_keep_count(self.pool_ratio, n)
+        return n
+
+    def forward_device(self, x: Tensor, pos: Tensor, topo: GraphTopology, graph_ptr: Tensor | None = None,
+                       return_pooling: bool = False):
+        """GraphNet.forward on device tensors with a prepared topology (models/GNN.py:297-309).  ``graph_ptr``: DEVICE int64
+        [G + 1] offsets of the graphs, read by the pooling layers alone (None = one graph; rows of no graph are erased by the first
+        pooling layer).  ``return_pooling=True``: ``(out, graph_ptr', kept)`` - the offsets of the rows of ``out`` (``graph_ptr``
+        itself without pooling) and the ORIGINAL rows of the survivors, int32 ascending (None without pooling).  With pooling every
+        pooling layer reads two sizes back from the device (one host synchronisation each)."""
         out = self.node_encoder.forward_segments([(x.view(x.size(0), -1), None)])         # :305
         # :299-302 + :306: K6 as the prologue of the edge encoder's launch where a kernel offers it (inference, large batches)
         edge_attr = self.edge_encoder.forward_edge_features(pos, topo.src_sorted, topo.dst_sorted)
         if edge_attr is None:
             edge_attr = Fn.edge_features(pos, topo.src_sorted, topo.dst_sorted)           # :299-302 (K6)
             edge_attr = self.edge_encoder.forward_segments([(edge_attr, None)])           # :306
-        out, _ = self.graph_processor.forward_sorted(out, topo, edge_attr, need_edges=not DROP_DEAD_EDGE_STORE)  # :307
+        kept = None
+        if self.pooling:
+            out, _, graph_ptr, kept = self.graph_processor.forward_sorted(out, topo, edge_attr, need_edges=not DROP_DEAD_EDGE_STORE,
+                                                                          graph_ptr=graph_ptr, return_pooling=True)
+        else:
+            out, _ = self.graph_processor.forward_sorted(out, topo, edge_attr, need_edges=not DROP_DEAD_EDGE_STORE)  # :307
         out = self.node_decoder.forward_segments([(out, None)])                           # :308
-        return _poison_if_deferred(topo, out)  # validation not read back yet: a bad edge_index must not yield a plausible result
+        # validation not read back yet: a bad edge_index must not yield a plausible result (the ORIGINAL topology's flags)
+        out = _poison_if_deferred(topo, out)
+        return (out, graph_ptr, kept) if return_pooling else out
 
     def forward(self, x, pos, edge_index):
         dev = require_gpu_param(self.node_encoder.model[0].weight, "GraphNet")
@@ -400,6 +494,7 @@ class CapturedForward:
     def __init__(self, model: nn.Module, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int | None = None,
                  node_capacity: int | None = None):
         gnet = model.graph_net if isinstance(model, CombinedModel) else model
+        _no_capture_with_pooling(model, "CapturedForward")
         dev = require_gpu_param(next(model.parameters()), "CapturedForward")
         self.model, self.device = model, dev
         self.edge_capacity, self.num_nodes = edge_capacity, int(x.size(0))
@@ -608,6 +703,7 @@ class CapturedRaggedBatchForward(CapturedForward):
     def __init__(self, model: nn.Module, batch, edge_capacity: int, node_capacity: int):
         if not isinstance(model, CombinedModel):
             raise TypeError("CapturedRaggedBatchForward: a CombinedModel expected")
+        _no_capture_with_pooling(model, "CapturedRaggedBatchForward")
         dev = require_gpu_param(next(model.parameters()), "CapturedRaggedBatchForward")
         if model.training and _has_batchnorm(model):
             # batch statistics span ALL rows: the dummy rows would enter them (eval mode normalises row by row)
@@ -770,10 +866,27 @@ class CombinedModel(nn.Module):
         with torch.no_grad():
             x = x.to(device=dev, dtype=torch.float32)
             pos = pos.to(device=dev, dtype=torch.float32)
-            y = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev))
+            y = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev))  # (pooled GraphNet: the survivors)
             whole = torch.arange(2, dtype=torch.int64, device=dev) * y.size(0)  # [0, N], built on the device
             _, alpha = Fn.graph_attention_pool(y, self.gate.forward_segments([(y, None)]).view(-1), whole, return_weights=True)
         return alpha if back == dev else alpha.to(back)
+
+    def kept_nodes(self, x, pos=None, edge_index=None) -> Tensor:
+        """The nodes of ONE graph that survive the GraphNet's top-K pooling layers (``GraphNet(pool_ratio=...)`` only; same
+        arguments as ``forward``, the tuple form included): int64 [N'] ORIGINAL node ids, ascending, on the device of ``x`` - on a
+        superpixel graph, the map of the regions the read-out sees.  No gradient."""
+        if not self.graph_net.pooling:
+            raise ValueError("CombinedModel.kept_nodes: the GraphNet has no pooling layers (pool_ratio is None)")
+        if pos is None and edge_index is None and isinstance(x, tuple):
+            x, pos, edge_index = x
+        dev = require_gpu_param(self.classifier.fc1.weight, "CombinedModel")
+        back = x.device
+        with torch.no_grad():
+            x = x.to(device=dev, dtype=torch.float32)
+            pos = pos.to(device=dev, dtype=torch.float32)
+            _, _, kept = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev), return_pooling=True)
+        kept = kept.long()
+        return kept if back == dev else kept.to(back)
 
     def forward(self, x, pos=None, edge_index=None):
         """models/GNN.py:334-341; accepts the (x, pos, edge_index) tuple; logits are 1-D [classes]."""
@@ -784,7 +897,7 @@ class CombinedModel(nn.Module):
         x = x.to(device=dev, dtype=torch.float32)
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
-        y = self.graph_net.forward_device(x, pos, topo)
+        y = self.graph_net.forward_device(x, pos, topo)  # (a pooled GraphNet: the survivors' rows, one graph)
         if self.pooled:
             logits = self.readout_logits(y, torch.arange(2, dtype=torch.int64, device=dev) * y.size(0))[0]  # [0, N], built on the device
             return logits if back == dev else logits.to(back)
@@ -810,6 +923,9 @@ class CombinedModel(nn.Module):
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
         if graph_ptr is None:
+            if self.graph_net.pooling and not self.pooled:
+                raise ValueError("forward_batched(num_graphs=...): behind top-K pooling (pool_ratio) the flatten read-out needs the "
+                                 "graphs' offsets; pass graph_ptr")
             if num_graphs is None or x.size(0) != num_graphs * self.num_nodes:
                 raise ValueError(f"expected num_graphs x {self.num_nodes} node rows (got {x.size(0)}); pass graph_ptr "
                                  f"for graphs of other sizes")
@@ -823,7 +939,12 @@ class CombinedModel(nn.Module):
         either ``num_graphs`` (graph g owns rows ``[g * num_nodes, (g + 1) * num_nodes)``) or a DEVICE int64 ``graph_ptr``
         [G + 1].  ``x`` may hold more rows than the graphs own (the padded buffers of a captured ragged-batch step: slack and
         dummy rows behind ``graph_ptr[-1]``): the read-out takes rows through ``graph_ptr`` only.  No host synchronisation."""
-        y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
         if self.pooled and graph_ptr is None:  # the num_graphs form: graph g owns rows [g * num_nodes, (g + 1) * num_nodes)
             graph_ptr = torch.arange(num_graphs + 1, dtype=torch.int64, device=x.device) * self.num_nodes
+        if self.graph_net.pooling:  # K20: the read-out takes the POOLED graphs' offsets
+            if graph_ptr is None:
+                raise ValueError("forward_batched_device: behind top-K pooling (pool_ratio) the flatten read-out needs graph_ptr")
+            y, graph_ptr, _ = self.graph_net.forward_device(x, pos, topo, graph_ptr=graph_ptr, return_pooling=True)
+            return self.readout_logits(y, graph_ptr)
+        y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
         return self.readout_logits(y, graph_ptr, num_graphs)

@@ -1060,7 +1060,7 @@ int bwd_shape(const gnc_mlp_desc_t& d, int* nmm_out, int* nadd_out, int* T_out) 
   if (H > KC || od > KC) return 0;
   for (int l = 1; l < L; ++l)
     if (d.in_dim[l] > KC || d.out_dim[l] > KC) return 0;
-  int nmm = 0, nadd = 0;
+  int nmm = 0, nadd = 0, wide = H > od ? H : od;
   for (int s = 0; s < d.num_segments; ++s) {
     const gnc_mlp_segment_t& g = d.seg[s];
     if (g.width > KC || g.ld % 4 != 0 || !al16(g.ptr)) return 0;
@@ -1069,10 +1069,13 @@ int bwd_shape(const gnc_mlp_desc_t& d, int* nmm_out, int* nadd_out, int* T_out) 
     } else {
       if (nadd) return 0;
       ++nmm;
+      // the kernel forms a segment's dx in HT tiles of 32 columns: a MATMUL segment wider than the hidden and output widths
+      // (a 64-wide input under a 32-unit hidden layer, K20's scorer) needs the tile count of ITS width
+      if (g.width > wide) wide = g.width;
     }
   }
   if (nmm < 1 || nmm > 3 || (nadd != 0 && !(nadd == 2 && nmm == 1))) return 0;
-  const int T = tiles_for(H > od ? H : od);
+  const int T = tiles_for(wide);
   if (T > 2) return 0;
   *nmm_out = nmm;
   *nadd_out = nadd;

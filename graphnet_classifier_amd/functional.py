@@ -791,6 +791,68 @@ def graph_attention_pool(y: torch.Tensor, scores: torch.Tensor, graph_ptr: torch
     return out, native.graph_attention_weights(scores.detach(), saved, graph_ptr)
 
 
+class _TopKNodeRows(torch.autograd.Function):
+    """Gated compaction of the node rows (csrc/topk_pool.hip, K20): ``x'[v'] = x[v] tanh(s_v)`` for the kept rows; one streaming
+    launch each way, the backward writes every row of ``dx`` / ``ds`` once (exact +0.0 for a dropped row)."""
+
+    @staticmethod
+    def forward(ctx, x, scores, kept, new_id):
+        out = native.topk_pool_rows_forward(x, kept, scores)
+        ctx.save_for_backward(x, scores, new_id)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, scores, new_id = ctx.saved_tensors
+        dx, ds = native.topk_pool_rows_backward(grad, new_id, x, scores, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return dx, ds, None, None
+
+
+class _TopKEdgeRows(torch.autograd.Function):
+    """Compaction of the edge rows without a gate (K20): ``e'[j'] = e[j]`` for the kept edges, ``de[j] = de'[j']`` or +0.0."""
+
+    @staticmethod
+    def forward(ctx, e, kept_edges, edge_new_id):
+        ctx.save_for_backward(edge_new_id)
+        return native.topk_pool_rows_forward(e, kept_edges)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (edge_new_id,) = ctx.saved_tensors
+        return native.topk_pool_rows_backward(grad, edge_new_id)[0], None, None
+
+
+def topk_pool(x: torch.Tensor, scores: torch.Tensor, topo, graph_ptr: torch.Tensor, ratio: float, edge_attr: torch.Tensor | None = None,
+              need_edges: bool = True):
+    """Top-K node pooling (K20): per graph of ``graph_ptr`` (device int64 [G + 1]) keep the ``k = min(n, max(1, ceil(ratio n)))``
+    rows with the best ``scores`` [rows] - larger first, ``-0.0 == +0.0``, NaN last, ties by lower row - IN THEIR OLD ORDER, gate
+    them (``x' = x tanh(s)``, so the scorer receives a gradient), and keep the edges of ``topo`` between two kept nodes, renumbered
+    (still destination-sorted: no sort, no topology build).  ``edge_attr`` [E, De], in ``topo``'s sorted order, is compacted
+    without a gate.  Returns ``(x', edge_attr' | None, topo', graph_ptr', kept)``; ``kept`` int32 [N'] are the survivors' old rows,
+    ascending.  Differentiable in ``x``, ``scores`` and ``edge_attr``.
+
+    ONE host synchronisation per call: the sizes N' and E' are read back from the device (a single read of both) to size the
+    outputs, so this cannot run inside a hipGraph capture.  ``need_edges=False`` (nothing reads the pooled edges, e.g. behind the
+    last GN block): nodes only, ``topo'`` is None and the read-back is of N' alone - still one."""
+    from .topology import GraphTopology
+    scores = scores.reshape(-1)
+    new_id, kept, gp_out, counts = native.topk_pool_select(scores.detach(), graph_ptr, ratio)
+    if need_edges:
+        src, dst, kept_edges, edge_new_id, rowptr = native.topk_pool_filter_edges(topo.src_sorted, topo.dst_sorted, topo.rowptr, new_id, kept,
+                                                                                 counts)
+        n_out, e_out = counts.tolist()  # the one read-back of this pooling layer
+    else:
+        n_out, e_out = int(counts[0].item()), 0
+    kept = kept[:n_out]
+    x_out = _TopKNodeRows.apply(x, scores, kept, new_id)
+    if not need_edges:
+        return x_out, None, None, gp_out, kept
+    kept_edges = kept_edges[:e_out]
+    topo_out = GraphTopology.from_sorted(rowptr[:n_out + 1], src[:e_out], dst[:e_out], n_out, topo.status, topo.deferred)
+    e_rows = _TopKEdgeRows.apply(edge_attr, kept_edges, edge_new_id) if edge_attr is not None else None
+    return x_out, e_rows, topo_out, gp_out, kept
+
+
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """[pos[dst]-pos[src], L1 norm] per edge (models/GNN.py:299-302).  ``pos`` is input data
     (utils/dataloader.py:50); gradients with respect to it are not provided."""

@@ -8,6 +8,7 @@ is raised -- the product path never silently routes around the HIP kernels.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_void_p
 
@@ -148,6 +149,13 @@ _SIGNATURES = {
     "gnc_graph_attention_pool_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                                         c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "gnc_graph_attention_weights_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "gnc_topk_pool_select_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gnc_topk_pool_edge_workspace_ints": (c_int64, [c_int64]),
+    "gnc_topk_pool_filter_edges": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnc_topk_pool_rows_forward_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnc_topk_pool_rows_backward_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                                  c_int64, c_void_p, c_void_p]),
     "gnc_segment_reduce_csr_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64,
                                              c_void_p, c_void_p]),
     "gnc_segment_reduce_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
@@ -1121,6 +1129,157 @@ def graph_attention_weights(scores: torch.Tensor, saved: torch.Tensor, graph_ptr
                                                                    alpha.data_ptr(), _stream(scores)),
                        float(rows)), "gnc_graph_attention_weights_f32")
     return alpha
+
+
+# --------------------------------------------------------------------------- K20: top-K node pooling
+def topk_keep_count(ratio: float, n: int) -> int:
+    """Rows a graph of ``n`` rows keeps: ``min(n, max(1, math.ceil(ratio * n)))``, 0 for an empty graph (the kernel's rule)."""
+    return min(int(n), max(1, math.ceil(float(ratio) * int(n)))) if n > 0 else 0
+
+
+def _check_ratio(ratio, who: str) -> float:
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) <= 1.0:
+        raise ValueError(f"{who}: ratio must be a number in (0, 1], got {ratio!r}")
+    return float(ratio)
+
+
+def topk_pool_select(scores: torch.Tensor, graph_ptr: torch.Tensor, ratio: float):
+    """Per graph of ``graph_ptr`` (DEVICE int64 [G + 1], never read on the host), the ``k = min(n, max(1, ceil(ratio n)))`` rows
+    with the best ``scores`` [rows] (float32): larger first, ``-0.0 == +0.0``, NaN below ``-inf``, ties by lower row.  Returns
+    ``(new_id, kept, graph_ptr_out, counts)``, all on the device and allocated at their upper bounds: ``new_id`` int32 [rows] (-1 =
+    dropped), ``kept`` int32 [rows] of which the first N' hold the survivors' old ids in ascending order, ``graph_ptr_out`` int64
+    [G + 1], ``counts`` int64 [2] whose first entry is N' (the second is ``topk_pool_filter_edges``'s E').  No host
+    synchronisation here: the caller reads ``counts`` back ONCE per pooling layer and narrows with views."""
+    lib = load_library()
+    ratio = _check_ratio(ratio, "topk_pool_select")
+    _require_cuda(scores, graph_ptr)
+    if scores.dtype != torch.float32 or scores.dim() != 1:
+        raise ValueError(f"topk_pool_select: scores must be float32 [rows], got {scores.dtype} {tuple(scores.shape)}")
+    scores = scores.contiguous()
+    dev, rows = scores.device, scores.size(0)
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    new_id = torch.empty(rows, dtype=torch.int32, device=dev)
+    kept = torch.empty(rows, dtype=torch.int32, device=dev)
+    gp_out = torch.empty(G + 1, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("topk_pool_select", scores,
+                       lambda: lib.gnc_topk_pool_select_f32(scores.data_ptr(), gp.data_ptr(), G, rows, ratio, new_id.data_ptr(),
+                                                            kept.data_ptr(), gp_out.data_ptr(), counts.data_ptr(), _stream(scores)),
+                       float(rows)), "gnc_topk_pool_select_f32")
+    return new_id, kept, gp_out, counts
+
+
+def topk_pool_filter_edges(src_sorted: torch.Tensor, dst_sorted: torch.Tensor, rowptr: torch.Tensor, new_id: torch.Tensor,
+                           kept: torch.Tensor, counts: torch.Tensor):
+    """Stream compaction of a destination-sorted edge list (int32 [E] each, ``rowptr`` int32 [rows + 1]) to the edges whose two
+    endpoints ``topk_pool_select`` kept, renumbered; the order is kept, so the result is still destination-sorted.  Returns
+    ``(src, dst, kept_edges, edge_new_id, rowptr_out)`` at their upper bounds (E, E, E, E, rows + 1): the first E' entries of the
+    first three and the first N' + 1 of ``rowptr_out`` are written, ``edge_new_id`` [E] holds -1 for a dropped edge; ``counts[1]``
+    receives E'.  No host synchronisation here (see ``topk_pool_select``)."""
+    lib = load_library()
+    _require_cuda(src_sorted, dst_sorted, rowptr, new_id, kept, counts)
+    rows, E = new_id.numel(), src_sorted.numel()
+    for name, t, n in (("src_sorted", src_sorted, E), ("dst_sorted", dst_sorted, E), ("rowptr", rowptr, rows + 1), ("new_id", new_id, rows),
+                       ("kept", kept, rows)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"topk_pool_filter_edges: {name} must be contiguous int32 [{n}], got {t.dtype} {tuple(t.shape)}")
+    if counts.dtype != torch.int64 or counts.numel() != 2 or not counts.is_contiguous():
+        raise ValueError("topk_pool_filter_edges: counts must be the select's int64 [2]")
+    dev = new_id.device
+    src, dst, kept_edges, edge_new_id = (torch.empty(E, dtype=torch.int32, device=dev) for _ in range(4))
+    rowptr_out = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    need = lib.gnc_topk_pool_edge_workspace_ints(E)
+    if need < 0:
+        raise RuntimeError(f"topk_pool_filter_edges: {E} edges outside the kernel's set")
+    ws = torch.empty(max(need, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("topk_pool_filter_edges", new_id,
+                       lambda: lib.gnc_topk_pool_filter_edges(src_sorted.data_ptr(), dst_sorted.data_ptr(), rowptr.data_ptr(), E, rows,
+                                                              new_id.data_ptr(), kept.data_ptr(), counts.data_ptr(), src.data_ptr(),
+                                                              dst.data_ptr(), kept_edges.data_ptr(), edge_new_id.data_ptr(),
+                                                              rowptr_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(new_id)),
+                       float(E)), "gnc_topk_pool_filter_edges")
+    return src, dst, kept_edges, edge_new_id, rowptr_out
+
+
+def topk_pool_rows_forward(x: torch.Tensor, kept: torch.Tensor, scores: torch.Tensor | None = None,
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+    """``out[i] = x[kept[i]] * tanh(scores[kept[i]])`` (``scores`` None: no gate, the bits of ``x``): ``x`` [rows, C] float32 with
+    unit column stride (a row stride above C is taken as it is), ``kept`` int32 [n_out] - a HOST-known length, i.e. the narrowed
+    view of ``topk_pool_select``'s - and ``scores`` float32 [rows]."""
+    lib = load_library()
+    _require_cuda(x, kept, scores, out)
+    x = _rowmajor(x)
+    rows, C, n_out = x.size(0), x.size(1), kept.numel()
+    if kept.dtype != torch.int32 or kept.dim() != 1 or not kept.is_contiguous() or n_out > rows:
+        raise ValueError(f"topk_pool_rows_forward: kept must be contiguous int32 [<= {rows}], got {kept.dtype} {tuple(kept.shape)}")
+    if scores is not None:
+        scores = _attention_scores(scores, x, "topk_pool_rows_forward")
+    if out is None:
+        out = torch.empty(n_out, C, dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or tuple(out.shape) != (n_out, C) or (C and out.stride(1) != 1):
+        raise ValueError(f"topk_pool_rows_forward: out must be float32 [{n_out}, {C}] with unit column stride")
+    if C == 0 or n_out == 0:
+        return out
+    with torch.cuda.device(x.device):
+        _check(_launch("topk_pool_rows_forward", x,
+                       lambda: lib.gnc_topk_pool_rows_forward_f32(x.data_ptr(), _ld(x), rows, C, kept.data_ptr(), n_out,
+                                                                  scores.data_ptr() if scores is not None else None, out.data_ptr(),
+                                                                  _ld(out), _stream(x)),
+                       float(n_out * C)), "gnc_topk_pool_rows_forward_f32")
+    return out
+
+
+def topk_pool_rows_backward(grad: torch.Tensor, new_id: torch.Tensor, x: torch.Tensor | None = None, scores: torch.Tensor | None = None,
+                            need_dx: bool = True, need_ds: bool = True, dx: torch.Tensor | None = None, ds: torch.Tensor | None = None):
+    """``(dx [rows, C], ds [rows])`` of ``topk_pool_rows_forward`` from ``grad`` [n_out, C] and ``new_id`` int32 [rows]: with
+    ``j = new_id[r]``, ``dx[r] = tanh(s_r) grad[j]`` and ``ds[r] = (1 - tanh(s_r)^2) sum_c grad[j, c] x[r, c]``; a dropped row gets
+    exact +0.0.  Every row is written exactly once (no memset, no atomics).  Without ``scores``: the ungated form, ``dx`` alone.
+    An unwanted gradient is None and costs nothing."""
+    lib = load_library()
+    _require_cuda(grad, new_id, x, scores, dx, ds)
+    grad = _rowmajor(grad)
+    n_out, C, rows = grad.size(0), grad.size(1), new_id.numel()
+    if new_id.dtype != torch.int32 or new_id.dim() != 1 or not new_id.is_contiguous():
+        raise ValueError(f"topk_pool_rows_backward: new_id must be contiguous int32 [rows], got {new_id.dtype} {tuple(new_id.shape)}")
+    need_ds = need_ds and scores is not None
+    if not (need_dx or need_ds):
+        return None, None
+    if need_ds:
+        x = _rowmajor(x)
+        if tuple(x.shape) != (rows, C):
+            raise ValueError(f"topk_pool_rows_backward: x {tuple(x.shape)} is not the forward's [{rows}, {C}]")
+    if scores is not None:
+        if scores.dtype != torch.float32 or scores.dim() != 1 or scores.numel() != rows:
+            raise ValueError(f"topk_pool_rows_backward: scores must be float32 [{rows}]")
+        scores = scores.contiguous()
+    dev = grad.device
+    if need_dx and dx is None:
+        dx = torch.empty(rows, C, dtype=torch.float32, device=dev)
+    if need_ds and ds is None:
+        ds = torch.empty(rows, dtype=torch.float32, device=dev)
+    if need_dx and (dx.dtype != torch.float32 or tuple(dx.shape) != (rows, C) or (C and dx.stride(1) != 1)):
+        raise ValueError(f"topk_pool_rows_backward: dx must be float32 [{rows}, {C}] with unit column stride")
+    if need_ds and (ds.dtype != torch.float32 or tuple(ds.shape) != (rows,) or not ds.is_contiguous()):
+        raise ValueError(f"topk_pool_rows_backward: ds must be contiguous float32 [{rows}]")
+    if rows == 0:
+        return (dx if need_dx else None), (ds if need_ds else None)
+    if C == 0:
+        if need_ds:
+            ds.zero_()
+        return (dx if need_dx else None), (ds if need_ds else None)
+    with torch.cuda.device(dev):
+        _check(_launch("topk_pool_rows_backward", grad,
+                       lambda: lib.gnc_topk_pool_rows_backward_f32(grad.data_ptr(), _ld(grad), n_out, x.data_ptr() if need_ds else None,
+                                                                   _ld(x) if need_ds else C,
+                                                                   scores.data_ptr() if scores is not None else None,
+                                                                   new_id.data_ptr(), rows, C, dx.data_ptr() if need_dx else None,
+                                                                   _ld(dx) if need_dx else C, ds.data_ptr() if need_ds else None,
+                                                                   _stream(grad)),
+                       float(rows * C)), "gnc_topk_pool_rows_backward_f32")
+    return (dx if need_dx else None), (ds if need_ds else None)
 
 
 # --------------------------------------------------------------------------- K16: split-K first Linear of a wide-input MLP

@@ -108,6 +108,28 @@ class GraphTopology:
                     raise IndexError(f"edge_index has node ids outside [0, {self.num_nodes})")
         self.deferred = mode == "deferred"
 
+    @classmethod
+    def from_sorted(cls, rowptr: torch.Tensor, src_sorted: torch.Tensor, dst_sorted: torch.Tensor, num_nodes: int,
+                    status: torch.Tensor, deferred: bool) -> "GraphTopology":
+        """A topology from an edge list that IS destination-sorted already (a top-K pooled graph, K20: filtering and renumbering a
+        sorted list keeps it sorted): device int32 ``rowptr`` [num_nodes + 1] and ``src_sorted`` / ``dst_sorted`` [E].  No build, no
+        sort, no host synchronisation: the "original" edge order is the sorted one, so ``perm`` is the identity; ``csc`` stays lazy.
+        ``status`` / ``deferred`` are those of the topology it was derived from: its out-of-range flags poison this one's results
+        (``_poison_if_deferred``) without a second entry in the pending list."""
+        for name, t, n in (("rowptr", rowptr, int(num_nodes) + 1), ("src_sorted", src_sorted, src_sorted.numel()),
+                           ("dst_sorted", dst_sorted, src_sorted.numel())):
+            if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_cuda:
+                raise ValueError(f"GraphTopology.from_sorted: {name} must be a device int32 [{n}], got {t.dtype} {tuple(t.shape)}")
+        self = cls.__new__(cls)
+        self.num_nodes, self.num_edges, self.device = int(num_nodes), int(src_sorted.numel()), rowptr.device
+        self.rowptr, self.src_sorted, self.dst_sorted = rowptr, src_sorted, dst_sorted
+        self.perm = torch.arange(self.num_edges, dtype=torch.int32, device=self.device)
+        self._row, self._col = None, None
+        self._row32, self._col32, self._inv_perm = src_sorted, dst_sorted, self.perm
+        self._csc = None
+        self.status, self.deferred = status, bool(deferred)
+        return self
+
     @property
     def row32(self) -> torch.Tensor:
         """int32 [E] source ids in original edge order (operator-level calls only)."""

@@ -196,6 +196,8 @@ class CapturedTrainStep:
                  forward=None, loss_scale: float = 1.0, capture_error_mode: str = "global", edge_capacity: int | None = None,
                  node_capacity: int | None = None):
         x, pos, edge_index = sample
+        from .GNN import _no_capture_with_pooling
+        _no_capture_with_pooling(model, "CapturedTrainStep")
         dev = require_gpu_param(next(model.parameters()), "CapturedTrainStep")
         fp = optimizer.fp
         self.optimizer = optimizer
@@ -416,6 +418,8 @@ class CapturedRaggedBatchStep(CapturedTrainStep):
         dev = require_gpu_param(next(model.parameters()), "CapturedRaggedBatchStep")
         if not isinstance(model, CombinedModel):
             raise TypeError("CapturedRaggedBatchStep: a CombinedModel expected")
+        from .GNN import _no_capture_with_pooling
+        _no_capture_with_pooling(model, "CapturedRaggedBatchStep")
         if any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
             raise NotImplementedError("CapturedRaggedBatchStep: not with BatchNorm layers (norm_type='BatchNorm1d')")
         self.optimizer = optimizer
@@ -785,7 +789,9 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
     # this loop steps one rank's model on its own samples: with a multi-rank process group up, a captured step would
     # record (or, under gloo, host-stage) a collective per sample that nothing here asked for
-    stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1)
+    # (a model with top-K pooling reads sizes back in its forward: no capture can record it, every step runs eagerly)
+    from .GNN import uses_node_pooling
+    stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1 and not uses_node_pooling(model))
     stepper.capture_ragged_batches = stepper.capture and capture_ragged_batches
     history = []
     # Belt and braces: the loop runs on a side stream, so that the eager steps in front of a capture never touch the
@@ -832,8 +838,8 @@ class _BatchScorer:
     ``_logits_of`` as they always did."""
 
     def __init__(self, model, dev, capture: bool):
-        from .GNN import CapturedRaggedBatchForward
-        self.model, self.dev, self.capture = model, dev, capture
+        from .GNN import CapturedRaggedBatchForward, uses_node_pooling
+        self.model, self.dev, self.capture = model, dev, capture and not uses_node_pooling(model)  # pooling: eager (no capture)
         self.ragged = _RaggedBatchCaptures(
             model, lambda batch, **capacities: CapturedRaggedBatchForward(model, batch, **capacities),
             _SampleStepper.MAX_PADDED_CAPTURES)
@@ -857,7 +863,8 @@ def _logits_of(model, sample, dev):
     if isinstance(sample, GraphBatch):
         x, pos = sample.x.to(dev, non_blocking=True), sample.pos.to(dev, non_blocking=True)
         sizes = sample.graph_ptr[1:] - sample.graph_ptr[:-1]
-        if not getattr(model, "ragged_readout", False) and bool((sizes == model.num_nodes).all()):
+        pooling = bool(getattr(getattr(model, "graph_net", None), "pooling", False))  # the flatten read-out then needs the offsets
+        if not getattr(model, "ragged_readout", False) and not pooling and bool((sizes == model.num_nodes).all()):
             return model.forward_batched(x, pos, sample.edge_index, num_graphs=sample.num_graphs)
         return model.forward_batched(x, pos, sample.edge_index, graph_ptr=sample.graph_ptr)
     if isinstance(sample, (tuple, list)) and len(sample) == 3:

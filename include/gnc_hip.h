@@ -664,6 +664,42 @@ int gnc_graph_attention_pool_backward_f32(const float* dout, int64_t ld_dout, co
 int gnc_graph_attention_weights_f32(const float* scores, const float* saved, const int64_t* graph_ptr, int64_t num_graphs,
                                     int64_t rows, float* alpha, void* stream);
 
+/* ---- K20: top-K node pooling between the GN blocks (csrc/topk_pool.hip) ----------------
+ * Graph g of a block-diagonal batch owns rows [a, b) of `graph_ptr` (DEVICE int64 [num_graphs + 1], clamped as K17's), n = b - a,
+ * and keeps k_g = min(n, max(1, ceil(ratio n))) rows (product and ceiling in double; 0 for n = 0; 0 < ratio <= 1): the first k_g
+ * of the total order "larger score first, -0.0 == +0.0, NaN below -inf, equal scores by lower row".  Kept rows keep their relative
+ * order: new id = kept rows in front.  The result is a pure function of the scores' fp32 bits: the same alone, inside any batch
+ * and twice.  No global atomics, no tickets, no memset: every output element is written by exactly one thread.
+ *
+ * gnc_topk_pool_select_f32: `scores` [rows] -> new_id int32 [rows] (-1: dropped; rows of no graph are dropped), kept int32 [N']
+ * (old ids, ascending; allocate `rows`), new_graph_ptr int64 [num_graphs + 1], counts[0] = N' (counts: DEVICE int64 [2]).
+ *
+ * gnc_topk_pool_filter_edges: over the destination-sorted edge list src_sorted / dst_sorted int32 [E] and rowptr int32 [rows + 1]:
+ * an edge survives when both endpoints are kept (an endpoint outside [0, rows) drops it and is never an index); survivors keep
+ * their order, so dst_out stays sorted.  src_out / dst_out / kept_edges (old sorted positions, ascending) int32 [E'] (allocate E),
+ * edge_new_id int32 [E] (-1: dropped), rowptr_out int32 [N' + 1] (allocate rows + 1): rowptr_out[v'] = kept edges in front of
+ * rowptr[v], rowptr_out[N'] = E'; counts[1] = E' (counts[0] is read: run the select first, on the same stream).  `workspace`:
+ * gnc_topk_pool_edge_workspace_ints(E) int32 (-1: E outside [0, 2^31)).
+ *
+ * Rows: out[i, :] = x[kept[i], :] * tanhf(scores[kept[i]]) for i < n_out (`scores` NULL: no gate, the bits of x); backward over
+ * the rows_in input rows with j = new_id[r]: dx[r, :] = tanhf(s_r) dout[j, :], ds[r] = (1 - tanhf(s_r)^2) sum_c dout[j, c] x[r, c]
+ * (the dot in a fixed lane order), exact +0.0 for a dropped row; every row of dx / ds is written once.  dx or ds may be NULL; ds
+ * needs scores and x.  Leading dimensions >= C; 16-byte accesses when C % 4 == 0 and every table's rows are 16-byte aligned.
+ * n_out is a HOST value: the caller reads counts back once per pooling layer.  Empty problems return GNC_OK.  Added without an
+ * ABI bump: a library without these symbols fails the symbol lookup of the binding. */
+int gnc_topk_pool_select_f32(const float* scores, const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, double ratio,
+                             int32_t* new_id, int32_t* kept, int64_t* new_graph_ptr, int64_t* counts, void* stream);
+int64_t gnc_topk_pool_edge_workspace_ints(int64_t num_edges);
+int gnc_topk_pool_filter_edges(const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr, int64_t num_edges,
+                               int64_t rows, const int32_t* new_id, const int32_t* kept, int64_t* counts, int32_t* src_out,
+                               int32_t* dst_out, int32_t* kept_edges, int32_t* edge_new_id, int32_t* rowptr_out, int32_t* workspace,
+                               int64_t workspace_ints, void* stream);
+int gnc_topk_pool_rows_forward_f32(const float* x, int64_t ld_x, int64_t rows_in, int64_t C, const int32_t* kept, int64_t n_out,
+                                   const float* scores, float* out, int64_t ld_out, void* stream);
+int gnc_topk_pool_rows_backward_f32(const float* dout, int64_t ld_dout, int64_t n_out, const float* x, int64_t ld_x, const float* scores,
+                                    const int32_t* new_id, int64_t rows_in, int64_t C, float* dx, int64_t ld_dx, float* ds,
+                                    void* stream);
+
 /* ---- K18: mean / max neighbourhood aggregation (csrc/segment_reduce.hip) --------------
  * The node model's aggregation with another reducer than K1's sum, over the same destination-sorted CSR and with K1's argument
  * conventions: out[v, :] reduces src[row(k), :] over the sorted positions k in [rowptr[v], rowptr[v+1]), row(k) = perm[k] or k

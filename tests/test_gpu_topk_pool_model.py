@@ -1,0 +1,263 @@
+"""GPU: ``GraphNet(pool_ratio=0.5)`` - top-K node pooling behind every GN block (K20) - under ``CombinedModel`` read-outs ``"mean"``
+and ``"attention"``, against the pooled GraphNet composed from the CPU oracle's pieces (tests/topk_pool_cases.py), its gradients
+against float64 autograd of the same composition, ``forward_batched`` against per-graph ``forward``, ``kept_nodes`` against the
+reference's set, a pooled graph without edges, the captures (which must refuse) and the eager training loop.  Graphs: the superpixel
+fixtures with 69 / 100 / 119 nodes and a batch of six.  GraphNet: ``synthetic.graphnet_kwargs(64, 2, out_channels=8)``, seeded.
+
+A fresh scorer is almost flat, so the k-th and the (k + 1)-th score of a graph can lie closer than the fp32 error of the scores, and
+the oracle and the device would then rightly keep different nodes.  Every model of this file therefore has each scorer's last weight
+multiplied by ``SHARPEN``, and the seed is chosen so that the conditions of ``seed_condition_figures`` hold at every pooling layer
+and graph; they are asserted in tests/test_topk_pool_host.py (no GPU needed) and their figures are in DESIGN.md, K20."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import graphnet_oracle as O
+from tests import topk_pool_cases as K
+from tests._util import max_abs
+from tests.test_gpu_attention_readout_model import SIX, THREE, _graph
+
+DEV = "cuda:0"
+SEED = 4
+OUT_DIM = 8
+RATIO = 0.5
+SHARPEN = 10.0
+READOUTS = ("mean", "attention")
+
+
+def _model(readout="mean", pool_ratio=RATIO, seed=SEED, **extra):
+    from graphnet_classifier_amd import synthetic
+    from graphnet_classifier_amd.GNN import CombinedModel, GraphNet
+    torch.manual_seed(seed)
+    kw = synthetic.graphnet_kwargs(64, 2, out_channels=OUT_DIM)
+    gnet = GraphNet(**kw, **extra) if pool_ratio is None else GraphNet(**kw, pool_ratio=pool_ratio, **extra)
+    m = CombinedModel(gnet, num_nodes=100, classes=2, readout=readout)
+    with torch.no_grad():
+        for pool in getattr(gnet.graph_processor, "pools", {}).values():
+            pool.gate.model[2].weight.mul_(SHARPEN)
+        if readout == "attention":
+            m.gate.model[2].weight.mul_(SHARPEN)
+    return m
+
+
+def _sd(m, dtype=torch.float32):
+    return {k: v.detach().cpu().to(dtype) for k, v in m.state_dict().items()}
+
+
+def _batch(cases):
+    from graphnet_classifier_amd.image_to_graph import collate_graphs
+    return collate_graphs([_graph(c) for c in cases])
+
+
+def _inputs():
+    """[(name, x, pos, ei, graph_ptr | None)]: the three graphs and the batch of six."""
+    out = [(f"{nodes} nodes", *_graph(case_id), None) for case_id, nodes in THREE]
+    b = _batch(SIX)
+    out.append(("batch of six", b.x, b.pos, b.edge_index, b.graph_ptr.tolist()))
+    return out
+
+
+def seed_condition_figures(seed=SEED):
+    """One dict per (read-out, input, pooling layer, graph), from the oracle alone (no GPU): ``min_gap`` - the float64 gap between
+    the k-th and the (k + 1)-th score; ``score_err`` - the measured |fp32 oracle - float64 oracle| of that layer's scores;
+    ``first_k`` - whether the kept set is just the first k rows; ``apart`` - |pooled - un-pooled logits| of that graph in float64."""
+    from tests import segment_reduce_cases as C
+    out = []
+    inputs = _inputs()
+    for readout, aggregation, cases in (("mean", "sum", inputs), ("attention", "sum", inputs), ("mean", "mean", inputs[3:])):
+        m = _model(readout, seed=seed, aggregation=aggregation)
+        sd, sd64 = _sd(m), _sd(m, torch.float64)
+        before = O._scatter
+        if aggregation != "sum":
+            O._scatter = C.ORACLE_SCATTER[aggregation]
+        try:
+            out += _figures_of(sd, sd64, readout, aggregation, cases)
+        finally:
+            O._scatter = before
+    return out
+
+
+def _figures_of(sd, sd64, readout, aggregation, cases):
+    out = []
+    for name, x, pos, ei, gp in cases:
+        rec32, rec64 = [], []
+        K.pooled_logits(sd, x, pos, ei, RATIO, (0, 1), readout, gp, record=rec32)
+        pooled, _ = K.pooled_logits(sd64, x.double(), pos.double(), ei, RATIO, (0, 1), readout, gp, record=rec64)
+        plain, _ = K.pooled_logits(sd64, x.double(), pos.double(), ei, RATIO, (), readout, gp)
+        for layer, ((s32, _, keep32), (s64, ptr, keep64)) in enumerate(zip(rec32, rec64)):
+            same = np.array_equal(keep32, keep64)
+            err = float((s32.double() - s64).abs().max()) if same and s32.shape == s64.shape else float("inf")
+            for g in range(len(ptr) - 1):
+                a, b = int(ptr[g]), int(ptr[g + 1])
+                k = K.keep_count(RATIO, b - a)
+                ranked = np.sort(s64[a:b].numpy())[::-1]
+                out.append({"readout": readout, "aggregation": aggregation, "input": name, "layer": layer, "graph": g, "n": b - a, "k": k,
+                            "min_gap": float(ranked[k - 1] - ranked[k]) if k < b - a else float("inf"), "score_err": err,
+                            "first_k": bool(keep64[a:a + k].all()), "apart": float((pooled[g] - plain[g]).abs().max())})
+    return out
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    return _inputs()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("readout", READOUTS)
+def test_logits_and_kept_nodes_match_the_composed_oracle(inputs, readout):
+    m = _model(readout).eval()
+    sd = _sd(m)
+    singles = []
+    for name, x, pos, ei, gp in inputs:
+        ref, kept_ref = K.pooled_logits(sd, x, pos, ei, RATIO, (0, 1), readout, gp)
+        with torch.no_grad():
+            if gp is None:
+                logits = m((x.to(DEV), pos.to(DEV), ei.to(DEV))).cpu()[None]
+                kept = m.kept_nodes(x.to(DEV), pos.to(DEV), ei.to(DEV))
+                assert kept.dtype == torch.int64 and kept.is_cuda and not kept.requires_grad
+                assert np.array_equal(kept.cpu().numpy(), kept_ref) and kept.numel() == m.graph_net.pooled_nodes(x.size(0))
+                singles.append(logits[0])
+            else:
+                logits = m.forward_batched(x.to(DEV), pos.to(DEV), ei.to(DEV), graph_ptr=torch.tensor(gp)).cpu()
+        print(f"{readout}, {name}: |device - oracle| = {max_abs(logits, ref):.3e}")
+        assert logits.shape == ref.shape and max_abs(logits, ref) <= 1e-5
+    # forward_batched over the three graphs equals their per-graph forward
+    b = _batch([c for c, _ in THREE])
+    with torch.no_grad():
+        batched = m.forward_batched(b.x.to(DEV), b.pos.to(DEV), b.edge_index.to(DEV), graph_ptr=b.graph_ptr).cpu()
+    assert batched.shape == (3, 2) and max_abs(batched, torch.stack(singles)) <= 1e-5
+    on_cpu = m.kept_nodes(_graph(THREE[0][0]))  # the tuple form, inputs on the CPU: the result comes back there
+    assert on_cpu.device.type == "cpu" and on_cpu.numel() == m.graph_net.pooled_nodes(69)
+
+
+@pytest.mark.gpu
+def test_mean_aggregation_on_pooled_topologies(inputs, monkeypatch):
+    from tests import segment_reduce_cases as C
+    m = _model("mean", aggregation="mean").eval()
+    sd = _sd(m)
+    monkeypatch.setattr(O, "_scatter", C.ORACLE_SCATTER["mean"])
+    name, x, pos, ei, gp = inputs[3]
+    ref, _ = K.pooled_logits(sd, x, pos, ei, RATIO, (0, 1), "mean", gp)
+    with torch.no_grad():
+        logits = m.forward_batched(x.to(DEV), pos.to(DEV), ei.to(DEV), graph_ptr=torch.tensor(gp)).cpu()
+        mx = _model("mean", aggregation="max").eval().forward_batched(x.to(DEV), pos.to(DEV), ei.to(DEV), graph_ptr=torch.tensor(gp))
+    print(f"aggregation='mean', {name}: |device - oracle| = {max_abs(logits, ref):.3e}")
+    assert max_abs(logits, ref) <= 1e-5 and bool(torch.isfinite(mx).all())
+
+
+def _assert_gradients(got, ref, what):
+    for k, r in ref.items():
+        tol = 2e-5 + 1e-4 * float(r.abs().max())
+        err = max_abs(got[k].cpu(), r.cpu())
+        assert got[k].shape == r.shape and err <= tol, f"{what}: {k} err {err:.3e} > {tol:.3e}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("readout", READOUTS)
+def test_gradients_against_float64_autograd(readout):
+    x, pos, ei = _graph(20)
+    label = torch.tensor(1)
+    m = _model(readout)
+    torch.nn.CrossEntropyLoss()(m((x.to(DEV), pos.to(DEV), ei.to(DEV))), label.to(DEV)).backward()
+    got = {k: p.grad for k, p in m.named_parameters()}
+    sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in m.state_dict().items()}
+    O.set_scatter_impl("index_add")  # the differentiable ATen form of the same sum
+    try:
+        logits, _ = K.pooled_logits(sd, x.double(), pos.double(), ei, RATIO, (0, 1), readout)
+    finally:
+        O.set_scatter_impl("sorted_loop")
+    torch.nn.functional.cross_entropy(logits, label[None]).backward()
+    ref = {k: v.grad for k, v in sd.items()}
+    # the last pool sits behind the last block: its scorer, and every scorer in front, is reached through the gate tanh(s)
+    scorers = [k for k in got if ".pools." in k]
+    assert len(scorers) == 8 and set(ref) == set(got)
+    for k in scorers:
+        assert bool(got[k].any()) and bool(ref[k].any()), k
+    _assert_gradients(got, ref, f"eager pooled step, readout={readout}")
+
+
+@pytest.mark.gpu
+def test_a_pooled_graph_without_edges_runs_the_remaining_blocks():
+    """All scores equal (each scorer's last weight zeroed, its bias a constant, so the gate tanh(s) is not zero): the lowest ids win.
+    The graph's edges lie among its HIGH ids, so the first pooling layer leaves E' = 0 and block 2 runs on an edge-less graph."""
+    rng = np.random.default_rng(2)
+    n = 40
+    x = torch.from_numpy(rng.standard_normal((n, 3)).astype(np.float32))
+    pos = torch.from_numpy(rng.standard_normal((n, 2)).astype(np.float32))
+    ei = torch.from_numpy(rng.integers(20, 40, size=(2, 90)))
+    m = _model("mean").eval()
+    with torch.no_grad():
+        for pool in m.graph_net.graph_processor.pools.values():
+            pool.gate.model[2].weight.zero_()
+            pool.gate.model[2].bias.fill_(0.7)
+    ref, kept_ref = K.pooled_logits(_sd(m), x, pos, ei, RATIO, (0, 1), "mean")
+    assert kept_ref.tolist() == list(range(10))
+    with torch.no_grad():
+        logits = m((x.to(DEV), pos.to(DEV), ei.to(DEV))).cpu()
+        kept = m.kept_nodes(x.to(DEV), pos.to(DEV), ei.to(DEV))
+    assert kept.tolist() == list(range(10)) and max_abs(logits, ref[0]) <= 1e-5
+    m.train()
+    m((x.to(DEV), pos.to(DEV), ei.to(DEV))).sum().backward()  # and the backward of the edge-less blocks
+    assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in m.parameters())
+
+
+@pytest.mark.gpu
+def test_every_capture_refuses_a_pooled_model():
+    from graphnet_classifier_amd.GNN import CapturedForward, CapturedRaggedBatchForward
+    from graphnet_classifier_amd.train import CapturedRaggedBatchStep, CapturedTrainStep, FlatParameters, FusedAdam
+    m = _model("mean")
+    sample = tuple(t.to(DEV) for t in _graph(35))
+    batch = _batch(SIX[:3]).to(DEV)
+    opt = FusedAdam(FlatParameters(m))
+    crit = torch.nn.CrossEntropyLoss()
+    loss_sum = torch.zeros((), dtype=torch.float64, device=DEV)
+    attempts = (lambda: CapturedForward(m, *sample),
+                lambda: CapturedForward(m.graph_net, *sample),
+                lambda: CapturedForward(m, *sample, edge_capacity=1024),
+                lambda: CapturedForward(m, *sample, edge_capacity=1024, node_capacity=128),
+                lambda: CapturedRaggedBatchForward(m, batch, edge_capacity=2048, node_capacity=512),
+                lambda: CapturedTrainStep(m, opt, crit, sample, torch.tensor(0), loss_sum),
+                lambda: CapturedTrainStep(m, opt, crit, sample, torch.tensor(0), loss_sum, edge_capacity=1024, node_capacity=128),
+                lambda: CapturedRaggedBatchStep(m, opt, crit, batch, torch.tensor([0, 1, 1]), loss_sum, edge_capacity=2048, node_capacity=512))
+    for attempt in attempts:
+        with pytest.raises(ValueError, match="pooling"):
+            attempt()
+
+
+@pytest.mark.gpu
+def test_train_evaluate_and_predict_take_the_eager_path(tmp_path):
+    from graphnet_classifier_amd.train import evaluate, predict, train
+    m = _model("mean")
+    sample = _graph(35)
+    dataset = [(sample, torch.tensor(k % 2)) for k in range(4)]  # one topology four times: an un-pooled model would be captured
+    history = train(m, dataset, epochs=2, output_path=str(tmp_path), capture=True)
+    assert len(history["avg_loss"]) == 2 and all(np.isfinite(v) for v in history["avg_loss"])
+    for flag in ("captured", "captured_any_topology", "captured_ragged", "captured_ragged_batch", "captured_tensor"):
+        assert history[flag] is False, flag
+    loader = [(_batch(SIX[:2]), torch.tensor([0, 1])), (_batch(SIX[2:4]), torch.tensor([1, 0]))]
+    m.eval()
+    ev_c, ev_e = evaluate(m, loader, capture=True), evaluate(m, loader, capture=False)
+    assert ev_c["count"] == 4 and ev_c["loss"] == ev_e["loss"] and torch.equal(ev_c["confusion"], ev_e["confusion"])
+    assert torch.equal(predict(m, loader, capture=True)[0], predict(m, loader, capture=False)[0])
+
+
+@pytest.mark.gpu
+def test_the_default_model_is_untouched(inputs):
+    """``pool_ratio=None`` and no argument at all: no pooling module, the same logits bit for bit, and those of the un-pooled oracle."""
+    _, x, pos, ei, _ = inputs[2]  # 100 nodes
+    a, b = _model("mean", pool_ratio=None).eval(), _model("mean", pool_ratio=None).eval()
+    from graphnet_classifier_amd.GNN import CombinedModel, GraphNet
+    from graphnet_classifier_amd import synthetic
+    torch.manual_seed(SEED)
+    c = CombinedModel(GraphNet(**synthetic.graphnet_kwargs(64, 2, out_channels=OUT_DIM)), num_nodes=100, classes=2, readout="mean").eval()
+    assert not a.graph_net.pooling and not any(".pools." in k for k in a.state_dict())
+    with torch.no_grad():
+        la, lb, lc = (mm((x.to(DEV), pos.to(DEV), ei.to(DEV))) for mm in (a, b, c))
+    assert torch.equal(la, lb) and torch.equal(la, lc)
+    ref, _ = K.pooled_logits(_sd(a), x, pos, ei, RATIO, (), "mean")
+    assert max_abs(la.cpu(), ref[0]) <= 1e-5
+    pooled = _model("mean").state_dict()
+    mine = [k for k in a.state_dict() if k.startswith("graph_net.")]  # the pools are built last IN THE GRAPHNET
+    assert len(mine) > 20 and all(torch.equal(a.state_dict()[k], pooled[k]) for k in mine)
+    with torch.no_grad():
+        assert max_abs(_model("mean").eval()((x.to(DEV), pos.to(DEV), ei.to(DEV))), la) >= 1e-4  # and pooling is not ignored

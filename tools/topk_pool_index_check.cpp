@@ -1,0 +1,244 @@
+// Host walk of K20's index arithmetic (graphnet_classifier_amd/csrc/topk_pool_index.h over csrc/pool_index.h).  For batches with
+// empty graphs, rows in front of and behind the graphs and the awkward sizes around the 256-thread chunk and the 1024-edge tile,
+// every (workgroup, thread) of the select, edge-scan and row-compaction launches is enumerated as csrc/topk_pool.hip enumerates
+// them: every address is checked against its buffer, every input must be read and every output written exactly once, and the
+// select walk - the radix passes over score_key and the admission of ties in row order - must give the kept set of a plain
+// stable sort.  The key map is checked on its own (monotone, -0.0 == +0.0, NaN lowest).  Exit status 0 = every check held.
+//   c++ -std=c++17 -O1 -fsanitize=address,undefined -I graphnet_classifier_amd/csrc tools/topk_pool_index_check.cpp \
+//       -o topk_pool_index_check && ./topk_pool_index_check
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "topk_pool_index.h"
+
+using namespace gnc_topk;
+
+static int failures = 0;
+#define CHECK(cond, ...)                       \
+  do {                                         \
+    if (!(cond)) {                             \
+      if (++failures <= 20) {                  \
+        std::printf("FAILED %s: ", #cond);     \
+        std::printf(__VA_ARGS__);              \
+        std::printf("\n");                     \
+      }                                        \
+    }                                          \
+  } while (0)
+
+static uint32_t bits_of(float f) {
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u;
+}
+
+static float float_of(uint32_t u) {
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+
+static void check_key_map() {
+  const float inf = std::numeric_limits<float>::infinity();
+  const float ladder[] = {-inf, -3.4e38f, -1.5f, -1.0f, -1e-30f, -1e-45f, 0.0f, 1e-45f, 1e-30f, 1.0f, 1.5f, 3.4e38f, inf};
+  const int n = (int)(sizeof(ladder) / sizeof(ladder[0]));
+  for (int i = 0; i + 1 < n; ++i)
+    CHECK(score_key(bits_of(ladder[i])) < score_key(bits_of(ladder[i + 1])), "key not monotone at %g < %g", ladder[i], ladder[i + 1]);
+  CHECK(score_key(0x80000000u) == score_key(0u), "-0.0 and +0.0 differ");
+  const uint32_t nans[] = {0x7fc00000u, 0xffc00000u, 0x7f800001u, 0xff800001u, 0x7fffffffu, 0xffffffffu};
+  for (uint32_t u : nans) CHECK(score_key(u) == 0u && score_key(u) < score_key(bits_of(-inf)), "NaN %08x is not the lowest key", u);
+  uint32_t x = 12345u;  // random bit patterns: the key order is the float order
+  for (int i = 0; i < 200000; ++i) {
+    x = x * 1664525u + 1013904223u;
+    const uint32_t a = x;
+    x = x * 1664525u + 1013904223u;
+    const uint32_t b = x;
+    const float fa = float_of(a), fb = float_of(b);
+    if (std::isnan(fa) || std::isnan(fb)) continue;
+    CHECK((fa < fb) == (score_key(a) < score_key(b)) && (fa == fb) == (score_key(a) == score_key(b)), "order of %08x / %08x", a, b);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- select
+struct Batch {
+  int64_t rows;
+  std::vector<int64_t> ptr;
+};
+
+static void walk_select(const Batch& B, const std::vector<float>& scores, double ratio) {
+  const int64_t rows = B.rows, G = (int64_t)B.ptr.size() - 1;
+  std::vector<int> id_writes(rows + 1, 0), kept_writes(rows + 1, 0);
+  std::vector<int32_t> new_id(rows + 1, -7);
+  std::vector<int64_t> new_ptr(G + 1, 0);
+  for (int64_t g = 0; g < G; ++g) {  // topk_offsets_kernel
+    int64_t a, b;
+    gnc_pool::graph_range(B.ptr.data(), g, rows, a, b);
+    new_ptr[g + 1] = new_ptr[g] + keep_count(ratio, b - a);
+  }
+  CHECK(new_ptr[G] <= rows, "N' %lld above rows %lld", (long long)new_ptr[G], (long long)rows);
+  for (int64_t g = 0; g < G; ++g) {  // workgroup g of topk_select_kernel
+    int64_t a, b, lo, hi, tail;
+    gnc_pool::graph_range(B.ptr.data(), g, rows, a, b);
+    gap_rows(B.ptr.data(), g, G, rows, lo, hi, tail);
+    for (int t = 0; t < kT; ++t) {
+      for (int64_t r = lo + t; r < hi; r += kT) { CHECK(r >= 0 && r < rows, "gap row %lld", (long long)r); ++id_writes[r]; new_id[r] = -1; }
+      for (int64_t r = tail + t; r < rows; r += kT) { CHECK(r >= 0, "tail row %lld", (long long)r); ++id_writes[r]; new_id[r] = -1; }
+    }
+    const int64_t n = b - a;
+    if (n == 0) continue;
+    const uint32_t k = (uint32_t)keep_count(ratio, n);
+    CHECK(k >= 1 && k <= n, "k %u of n %lld", k, (long long)n);
+    uint32_t T = 0, rem = (uint32_t)n;
+    if (k < n) {
+      uint32_t mask = 0;
+      rem = k;
+      for (int shift = 24; shift >= 0; shift -= 8) {
+        uint32_t hist[256] = {0};
+        std::vector<int> reads(n, 0);
+        for (int t = 0; t < kT; ++t)
+          for (int64_t r = a + t; r < b; r += kT) {
+            CHECK(r >= 0 && r < rows, "score %lld outside [0, %lld)", (long long)r, (long long)rows);
+            ++reads[r - a];
+            const uint32_t key = score_key(bits_of(scores[r]));
+            if ((key & mask) == T) ++hist[(key >> shift) & 255u];
+          }
+        for (int64_t i = 0; i < n; ++i) CHECK(reads[i] == 1, "pass %d read row %lld %d times", shift, (long long)(a + i), reads[i]);
+        int chosen = 0;
+        uint32_t above = 0, digit = 0, next = 0;
+        for (int t = 0; t < kT; ++t) {  // thread t owns digit 255 - t; `above` is its exclusive scan
+          const uint32_t h = hist[255 - t];
+          if (above < rem && rem <= above + h) { ++chosen; digit = 255u - t; next = rem - above; }
+          above += h;
+        }
+        CHECK(chosen == 1, "pass %d: %d threads chose a digit", shift, chosen);
+        T |= digit << shift, mask |= 255u << shift, rem = next;
+      }
+    }
+    uint32_t gt_base = 0, eq_base = 0;
+    for (int64_t c0 = 0; c0 < n; c0 += kT) {
+      uint32_t gt_run = 0, eq_run = 0;
+      for (int t = 0; t < kT && c0 + t < n; ++t) {  // thread order = scan order
+        const int64_t r = a + c0 + t;
+        const uint32_t key = score_key(bits_of(scores[r]));
+        const bool gt = key > T, eq = key == T;
+        const uint32_t gt_before = gt_base + gt_run, eq_before = eq_base + eq_run;
+        const bool keep = gt || (eq && eq_before < rem);
+        const int64_t id = new_ptr[g] + gt_before + std::min(eq_before, rem);
+        ++id_writes[r];
+        new_id[r] = keep ? (int32_t)id : -1;
+        if (keep) {
+          CHECK(id >= new_ptr[g] && id < new_ptr[g + 1], "new id %lld outside its graph's [%lld, %lld)", (long long)id,
+                (long long)new_ptr[g], (long long)new_ptr[g + 1]);
+          if (id >= 0 && id < rows) ++kept_writes[id];
+        }
+        gt_run += gt, eq_run += eq;
+      }
+      CHECK(gt_run <= 0xffffu && eq_run <= 0xffffu, "a packed count overflows 16 bits");
+      gt_base += gt_run, eq_base += eq_run;
+    }
+    // the kept set of a stable sort by (key descending, row ascending)
+    std::vector<int64_t> order(n);
+    for (int64_t i = 0; i < n; ++i) order[i] = a + i;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int64_t p, int64_t q) { return score_key(bits_of(scores[p])) > score_key(bits_of(scores[q])); });
+    std::vector<char> want(n, 0);
+    for (uint32_t i = 0; i < k; ++i) want[order[i] - a] = 1;
+    for (int64_t i = 0; i < n; ++i)
+      CHECK((new_id[a + i] >= 0) == (want[i] != 0), "graph %lld row %lld: kept %d, the sort says %d", (long long)g, (long long)(a + i),
+            new_id[a + i] >= 0, want[i]);
+  }
+  for (int64_t r = 0; r < rows; ++r) CHECK(id_writes[r] == 1, "new_id[%lld] written %d times", (long long)r, id_writes[r]);
+  for (int64_t i = 0; i < rows; ++i) CHECK(kept_writes[i] == (i < new_ptr[G] ? 1 : 0), "kept[%lld] written %d times", (long long)i, kept_writes[i]);
+  int32_t expect = 0;
+  for (int64_t r = 0; r < rows; ++r)
+    if (new_id[r] >= 0) CHECK(new_id[r] == expect++, "new ids are not the kept rows in front (row %lld)", (long long)r);
+}
+
+// ------------------------------------------------------------------------------------------------------------ edge tiles
+static void walk_edges(int64_t E) {
+  const int64_t tiles = edge_tiles(E);
+  CHECK(edge_workspace_ints(E) == tiles + E, "workspace of %lld edges", (long long)E);
+  std::vector<int> seen(E + 1, 0);
+  int64_t previous = -1;
+  for (int64_t tile = 0; tile < tiles; ++tile)
+    for (int i = 0; i < kEdgeSteps; ++i)
+      for (int t = 0; t < kT; ++t) {  // step-major, thread-minor: the order the scan numbers the kept edges in
+        const int64_t p = edge_position(tile, i, t);
+        CHECK(p == previous + 1, "edge positions are not consecutive at %lld", (long long)p);
+        previous = p;
+        if (p < E) ++seen[p];
+      }
+  CHECK(previous + 1 >= E && previous + 1 < E + kEdgeTile, "tiles cover [0, %lld) with %lld positions", (long long)E, (long long)(previous + 1));
+  for (int64_t p = 0; p < E; ++p) CHECK(seen[p] == 1, "edge %lld visited %d times", (long long)p, seen[p]);
+}
+
+// ------------------------------------------------------------------------------------------------------------- row tiles
+static void walk_rows(int64_t n_rows, int64_t C, int64_t ld, int64_t blocks) {
+  const RowGeometry geo = row_geometry(C);
+  CHECK(geo.lanes >= 1 && geo.lanes <= 64 && kT % geo.lanes == 0 && (geo.vec == 1 || C % 4 == 0), "geometry of C = %lld", (long long)C);
+  std::vector<int> writes(n_rows * ld + 1, 0);
+  const int W = geo.lanes, rpb = kT / W;
+  const int64_t per_row = C / geo.vec;
+  for (int64_t blk = 0; blk < blocks; ++blk)
+    for (int t = 0; t < kT; ++t) {
+      const int lane = t % W, sub = t / W;
+      for (int64_t i = blk * rpb + sub; i < n_rows; i += blocks * rpb)
+        for (int64_t q = lane; q < per_row; q += W)
+          for (int u = 0; u < geo.vec; ++u) {
+            const int64_t o = i * ld + q * geo.vec + u;
+            CHECK(q * geo.vec + u < C && o < n_rows * ld, "element %lld of a [%lld, %lld] table", (long long)o, (long long)n_rows, (long long)ld);
+            if (o < n_rows * ld) ++writes[o];
+          }
+      CHECK((t ^ (W >> 1)) / W == sub || W == 1, "butterfly partner of thread %d leaves its row", t);
+    }
+  for (int64_t i = 0; i < n_rows; ++i)
+    for (int64_t c = 0; c < ld; ++c)
+      CHECK(writes[i * ld + c] == (c < C ? 1 : 0), "[%lld, %lld] of C = %lld touched %d times", (long long)i, (long long)c, (long long)C, writes[i * ld + c]);
+}
+
+int main() {
+  check_key_map();
+  const double pairs[][2] = {{0.1, 10}, {0.7, 10}, {0.3, 10}, {0.6, 5}, {1e-3, 16384}, {0.5, 1}, {1.0, 7}, {0.25, 0}};
+  for (const auto& p : pairs) std::printf("keep_count %.17g %lld = %lld\n", p[0], (long long)p[1], (long long)keep_count(p[0], (int64_t)p[1]));
+
+  const int64_t sizes[] = {0, 1, 2, 3, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4097, 16384};
+  const double ratios[] = {1.0, 0.8, 0.5, 0.25, 1e-3};
+  Batch B;  // every size as one graph of a batch, an empty graph in the middle, 5 rows in front and 9 behind
+  B.ptr.push_back(5);
+  for (int64_t n : sizes) B.ptr.push_back(B.ptr.back() + n);
+  B.rows = B.ptr.back() + 9;
+  uint32_t x = 99u;
+  for (int pattern = 0; pattern < 3; ++pattern) {
+    std::vector<float> scores(B.rows);
+    for (int64_t r = 0; r < B.rows; ++r) {
+      x = x * 1664525u + 1013904223u;
+      if (pattern == 0) scores[r] = (float)(int32_t)x * 1e-9f;
+      else if (pattern == 1) scores[r] = 0.25f;                            // all equal: the ties alone decide
+      else scores[r] = (x >> 29) == 0 ? std::nanf("") : (x >> 29) == 1 ? -0.0f : (x >> 29) == 2 ? 0.0f
+                       : (x >> 29) == 3 ? -std::numeric_limits<float>::infinity() : (float)((x >> 20) & 3u);  // duplicates, specials
+    }
+    for (double ratio : ratios) walk_select(B, scores, ratio);
+  }
+  Batch outside;  // offsets outside the table read as shorter or empty graphs
+  outside.rows = 300;
+  outside.ptr = {-4, 10, 10, 290, 350};
+  walk_select(outside, std::vector<float>(300, 1.0f), 0.5);
+
+  const int64_t edges[] = {0, 1, 255, 256, 257, kEdgeTile - 1, kEdgeTile, kEdgeTile + 1, 70001};
+  for (int64_t E : edges) walk_edges(E);
+  const int64_t widths[] = {1, 3, 8, 64, 65, 128, 256};
+  for (int64_t C : widths)
+    for (int64_t n_rows : {1, 37, 300})
+      for (int64_t blocks : {1, 7}) walk_rows(n_rows, C, C + (C % 4 == 0 ? 4 : 3), blocks);
+
+  if (failures) {
+    std::printf("topk_pool_index_check: %d FAILED\n", failures);
+    return 1;
+  }
+  std::printf("topk_pool_index_check: ok\n");
+  return 0;
+}
