@@ -366,12 +366,12 @@ __global__ __launch_bounds__(FNT) void mlp_backward_fused_kernel(const gnc_mlp_d
       fmma_chunk_from_lds(a0, te, wres, (s0.width + 7) >> 3, i, h);
       chain_fence(a0);
       if constexpr (NADD > 0) add_tile_from_lds<HT>(a0, ta, i, h);
-      relu_tiles<HT>(a0);
+      relu_tiles<HT, NADD ? 0 : MFMA_STATES_F32_32X32X2>(a0);  // (behind an ADD step v_add wrote the tiles)
       BPROBE(0);  // first Linear + additive rows + ReLU
       init_bias<HT>(a1, pbuf + PSTRIDE, h);
       fmma_chunk_from_regs(a1, a0, wres + CH, d.in_dim[1], i, h);
       chain_fence(a1);
-      relu_tiles<HT>(a1);
+      relu_tiles<HT, MFMA_STATES_F32_32X32X2>(a1);
       BPROBE(1);  // second Linear + ReLU
     }
     // the third Linear (for the LayerNorm statistics).  SAVED: before the output gradient is touched, so that the

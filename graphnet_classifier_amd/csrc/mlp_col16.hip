@@ -424,7 +424,7 @@ __global__ __launch_bounds__(NT * 64) void mlp_col16_kernel(const ColPlan p) {
 
     // ---------------------------------------------------------------- hidden and output Linears
     for (int l = 1; l < L; ++l) {
-      o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+      o.x = relu_acc(o.x); o.y = relu_acc(o.y); o.z = relu_acc(o.z); o.w = relu_acc(o.w);
       float* hb = hbuf + ((l - 1) & 1) * 16 * LDH;
       *reinterpret_cast<f32x4*>(hb + j * LDH + f0) = o;
       if constexpr (SAVE) {

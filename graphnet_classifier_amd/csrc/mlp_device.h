@@ -485,11 +485,15 @@ __device__ __forceinline__ float add_quarters(float x) {
 }
 
 // LayerNorm over the out_dim features of each data row: registers + one cross-half exchange.
-// fp32 MFMA and VALU instructions do NOT overlap on a gfx950 SIMD (tools/hw_probe.hip: one 32x32x2 MFMA
-// + k VALU = 64 + ~3..5k cycles), so the instruction count here is kernel time: packed fp32 math, no
-// per-feature selects (features >= out_dim hold exact zeros - zero weight rows, zero bias - so they drop out
-// of the sum; their deviations are cleared before the variance when the width is not 32*OT), 1/n as a
-// multiplier and v_rsq_f32 (1 ulp): ~85 VALU per 32 rows instead of ~310.
+// A vector-only phase: no matrix instruction of the wave is in flight, so its instruction count is kernel time
+// whichever matrix instruction the Linears ran on.  Hence no per-feature selects (features >= out_dim hold exact
+// zeros - zero weight rows, zero bias - so they drop out of the sum; their deviations are cleared before the variance
+// when the width is not 32*OT), 1/n as a multiplier and v_rsq_f32 (1 ulp), and packed fp32 math (v_pk_add_f32,
+// v_pk_fma_f32, v_pk_mul_f32: 80 instructions per 32 rows at two tiles, ~85 VALU in all instead of ~310).  The packed
+// forms were chosen by instruction count when the SIMD mate ran fp32 matrix instructions; what one costs against its two
+// single-rate instructions beside the split class's v_mfma_f32_32x32x16_bf16 is measured by `hw_probe p`
+// (tools/hw_probe.hip, profiles/hw_probe_pk.jsonl).  The four accumulators' association -
+// sa.x, sa.y, sb.x, sb.y each over eight values in order, then (sa.x + sa.y) + (sb.x + sb.y) - is part of the bits.
 template <int OT>
 __device__ __forceinline__ void layer_norm_tiles(f32x16 (&o)[OT], const float* pg, const float* pbt, int out_dim,
                                                  float eps, int h) {
@@ -985,8 +989,53 @@ __device__ __forceinline__ void store_row_piece(float* rowp, int col, f32x4 v, b
   }
 }
 
-template <int T>
+// ReLU of one accumulator value in ONE instruction, `v_max_f32 dst, 0, src`.  fmaxf(v, 0.f) on a matrix instruction's
+// output compiles to two: hipcc cannot prove the value canonical and puts `v_max_f32 v, v, v` (quiet a signalling NaN)
+// in front of the clamp.  A matrix instruction never writes a signalling NaN, and for every other value the first
+// instruction is the identity: a quiet NaN still becomes 0, -0.0 becomes +0.0, subnormals pass.
+// The statement is invisible to the hazard recognizer, on both sides: a value that comes straight from a matrix
+// instruction goes through matrix_result_pad first, and the result is for vector code (the split of the next Linear, a
+// transpose through LDS): where the next matrix instruction takes it as an operand as it is (the fp32 class of the
+// weights-resident kernel) the clamp stays fmaxf.  tools/check_isa.py (d), (e) checks every such pair of the built code.
+__device__ __forceinline__ float relu_acc(float v) {
+  float r;
+  asm("v_max_f32_e32 %0, 0, %1" : "=v"(r) : "v"(v));
+  return r;
+}
+
+// Wait states between a matrix instruction and a VALU instruction that reads its result, as hipcc pads the readers it
+// can see on gfx950: passes + 4 behind the 16-bit blocks, passes + 2 behind the fp32 ones.
+constexpr int MFMA_STATES_BF16_32X32X16 = 12;  // v_mfma_f32_32x32x16_bf16 (8 passes): s_nop 11
+constexpr int MFMA_STATES_F32_32X32X2 = 18;    // v_mfma_f32_32x32x2_f32 (16 passes): s_nop 15, s_nop 1
+
+// STATES wait states between the matrix instructions that wrote the accumulator tiles and whatever reads them next:
+// the statement reads and writes every tile, so the data flow orders it between the two.
+template <int STATES, int T>
+__device__ __forceinline__ void matrix_result_pad(f32x16 (&acc)[T]) {
+  static_assert(T == 1 || T == 2, "one tied operand per tile");
+  static_assert(STATES >= 1 && STATES <= 32, "one or two s_nop");
+  if constexpr (T == 1 && STATES > 16) asm("s_nop 15\n\ts_nop %c[n]" : "+v"(acc[0]) : [n] "i"(STATES - 17));
+  else if constexpr (T == 1) asm("s_nop %c[n]" : "+v"(acc[0]) : [n] "i"(STATES - 1));
+  else if constexpr (STATES > 16) asm("s_nop 15\n\ts_nop %c[n]" : "+v"(acc[0]), "+v"(acc[1]) : [n] "i"(STATES - 17));
+  else asm("s_nop %c[n]" : "+v"(acc[0]), "+v"(acc[1]) : [n] "i"(STATES - 1));
+}
+
+// The kernels of one or two accumulator tiles (the weights-resident kernel and the fused backward's recompute).
+// STATES: what the matrix instructions that wrote acc ask for; 0 when a VALU instruction wrote it last (an ADD step)
+template <int T, int STATES>
 __device__ __forceinline__ void relu_tiles(f32x16 (&acc)[T]) {
+  if constexpr (STATES > 0) matrix_result_pad<STATES, T>(acc);
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = relu_acc(acc[t][r]);
+}
+
+// The two-instruction form.  The fp32 class of the weights-resident kernel keeps it (above), and so does the streaming
+// kernel (four and eight tiles): with the statements above its instances drain more waits in the tile loop and one of
+// them spills (tools/isa_budget.json).
+template <int T>
+__device__ __forceinline__ void relu_tiles_fmaxf(f32x16 (&acc)[T]) {
 #pragma unroll
   for (int t = 0; t < T; ++t)
 #pragma unroll

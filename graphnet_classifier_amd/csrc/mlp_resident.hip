@@ -558,7 +558,9 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
       compiler_lds_barrier();
       tiles_to_lds<HT>(hid, abuf, i, h);
     } else {
-      relu_tiles<HT>(hid);
+      // (after an ADD step the tiles come from v_add; the first Linear of class 2 runs on fp32 matrix instructions)
+      if constexpr (SPLIT == 0) relu_tiles_fmaxf<HT>(hid);
+      else relu_tiles<HT, NADD ? 0 : SPLIT == 1 ? MFMA_STATES_BF16_32X32X16 : MFMA_STATES_F32_32X32X2>(hid);
       // training forward (gnc_mlp_desc_t.save_act): the post-activations leave as whole rows through the wave's LDS tile,
       // which is idle between the first Linear and the epilogue (16-B pieces straight from the accumulator layout - 32 B
       // per row and instruction - measured +0.55 ms per c3 edge launch, four times the requests at the L2)
@@ -578,7 +580,8 @@ __global__ __launch_bounds__(RNT) void mlp_resident_kernel(const gnc_mlp_desc_t 
         if constexpr (PIPE) mma_chunk_from_regs_split_pipe<HT, HT, 4>(nxt, hid, wsplit(NMM + l - 1), i, h);
         else if constexpr (SPLIT != 0) mma_chunk_from_regs_split<HT, HT, SPK>(nxt, hid, wsplit(NMM + l - 1), FULL ? KC : d.in_dim[l], i, h);
         else mma_chunk_from_regs<HT, HT>(nxt, hid, wres + (NMM + l - 1) * CH, 0, FULL ? KC : d.in_dim[l], i, h);
-        relu_tiles<HT>(nxt);
+        if constexpr (SPLIT == 0) relu_tiles_fmaxf<HT>(nxt);
+        else relu_tiles<HT, MFMA_STATES_BF16_32X32X16>(nxt);
         if constexpr (SAVE) save_rows(nxt, l);
 #pragma unroll
         for (int t = 0; t < HT; ++t) hid[t] = nxt[t];

@@ -315,7 +315,7 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_stream_kernel(const gnc_mlp_de
     if (L == 1) {
       if (d.ln_gamma) layer_norm_tiles<HT>(hid, pbuf + L * PSTRIDE, pbuf + (L + 1) * PSTRIDE, out_dim, d.ln_eps, h);
     } else {
-      relu_tiles<HT>(hid);
+      relu_tiles_fmaxf<HT>(hid);
       // training forward (gnc_mlp_desc_t.save_act): the post-activations leave as whole rows, 64 columns at a time
       // through the wave's LDS tile (idle between the first Linear's staging and the epilogue)
       auto save_rows = [&](const f32x16 (&acc)[HT], int l) {
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_stream_kernel(const gnc_mlp_de
             ++q;
           }
         }
-        relu_tiles<HT>(nxt);
+        relu_tiles_fmaxf<HT>(nxt);
 #pragma unroll
         for (int t = 0; t < HT; ++t) hid[t] = nxt[t];
         if constexpr (SAVE) save_rows(hid, l);

@@ -15,7 +15,15 @@ build/csrc/*.o):
       look inside inline asm, so this is checked for EVERY such pair, counting each instruction as one wait state
       and `s_nop N` as N + 1;
   (c) scratch: `.private_segment_fixed_size` (and the spill counts behind it) per kernel may not exceed the recorded
-      budget.
+      budget;
+  (d) matrix result hazard: a VALU instruction that reads a VGPR written by a matrix instruction needs wait states in
+      between, as many as hipcc puts in front of the readers it can see on gfx950: the instruction's passes + 4 behind
+      the 16-bit blocks (12 behind the 8-pass `v_mfma_f32_32x32x16_bf16`: `s_nop 11`), passes + 2 behind the fp32 ones
+      (18 behind the 16-pass 32x32x2, 10 behind the 8-pass 16x16x4).  The one-instruction ReLU
+      of the MLP kernels (relu_acc, mlp_device.h) is inline asm, which the hazard recognizer does not see, so EVERY
+      such pair is checked, with the count of (b); an unconditional branch ends the window (nothing falls through it);
+  (e) the other side of such a statement: a matrix instruction that reads a VGPR written by a VALU instruction needs 2
+      wait states in between.
 
 Budgets live in tools/isa_budget.json (`python tools/check_isa.py --update` rewrites them from the current build;
 review the diff before committing it).
@@ -36,6 +44,8 @@ BUDGET = os.path.join(ROOT, "tools", "isa_budget.json")
 VMEM = re.compile(r"^(buffer_|global_|flat_|scratch_)(load|store|atomic)")
 HAZARD_WAIT_STATES = int(os.environ.get("GNC_ISA_HAZARD_STATES", "5"))
 SGPR_WRITERS = ("v_readlane_b32", "v_readfirstlane_b32")
+VALU_TO_MATRIX_STATES = 2
+MATRIX = re.compile(r"^v_s?mfmac?_\w+?_(\d+x\d+x\d+)_?\d*(\w+)$")
 
 
 def run(cmd, **kw):
@@ -59,6 +69,25 @@ def sgprs_of(text):
         regs.update(range(int(a), int(b) + 1))
     regs.update(int(a) for a in re.findall(r"\bs(\d+)\b", text))
     return regs
+
+
+def vgprs_of(text):
+    """VGPR numbers named in an operand string."""
+    regs = set()
+    for a, b in re.findall(r"\bv\[(\d+):(\d+)\]", text):
+        regs.update(range(int(a), int(b) + 1))
+    regs.update(int(a) for a in re.findall(r"\bv(\d+)\b", text))
+    return regs
+
+
+def matrix_read_states(op):
+    """Wait states between a matrix instruction and a VALU instruction reading its result on gfx950: the instruction's
+    passes + 4 behind a 16-bit block, passes + 2 behind an fp32 one (32x32 fp32 blocks take 16 passes, the 32x32 16-bit
+    blocks and the 16x16 blocks of this project 8, 4x4 blocks 2)."""
+    m = MATRIX.match(op)
+    shape, sixteen_bit = m.group(1), m.group(2).startswith(("bf16", "f16"))
+    passes = 2 if shape.startswith("4x4") else 8 if shape.startswith("16x16") or sixteen_bit else 16
+    return passes + (4 if sixteen_bit else 2)
 
 
 def analyse_object(obj, tmp):
@@ -140,8 +169,55 @@ def analyse_object(obj, tmp):
                         last_write[r] = 0
                 if op.startswith("s_cbranch") or op == "s_branch" or op == "s_endpgm":
                     pass  # linear scan: conservative across fall-through, branches do not shorten the distance
+            # hazard (d)
+            mfma_write = {}  # vgpr -> [wait states since a matrix instruction wrote it, states its readers need, its name]
+            min_seen = {}    # matrix instruction -> the closest VALU read of its result
+            min_operand = None  # the closest matrix read of a VALU result
+            for addr, op, args, _ in ins:
+                ops = args.split(",")
+                if op.startswith("v_") and not MATRIX.match(op):
+                    for r in vgprs_of(",".join(ops[1:])):
+                        if r in mfma_write:
+                            since, need, mop = mfma_write[r]
+                            min_seen[mop] = min(min_seen.get(mop, since), since)
+                            if since < need:
+                                hazards.append(f"{op} at 0x{addr:x} reads v{r} {since} wait states after {mop} wrote it (needs {need})")
+                step = int(args.strip() or 0) + 1 if op == "s_nop" else 1
+                for r in list(mfma_write):
+                    mfma_write[r][0] += step
+                    if mfma_write[r][0] > 24:
+                        del mfma_write[r]
+                if op.startswith("v_") or op.startswith("ds_read") or "_load" in op:  # any later write (an accumulate chain's next link included) restarts or ends the window
+                    for r in vgprs_of(ops[0]):
+                        mfma_write.pop(r, None)
+                    if MATRIX.match(op):
+                        for r in vgprs_of(ops[0]):
+                            mfma_write[r] = [0, matrix_read_states(op), op]
+                if op in ("s_branch", "s_endpgm", "s_setpc_b64"):
+                    mfma_write.clear()
+            # hazard (e)
+            valu_write = {}  # vgpr -> wait states since a VALU instruction wrote it
+            for addr, op, args, _ in ins:
+                ops = args.split(",")
+                if MATRIX.match(op):
+                    for r in vgprs_of(",".join(ops[1:])):
+                        if r in valu_write:
+                            min_operand = valu_write[r] if min_operand is None else min(min_operand, valu_write[r])
+                            if valu_write[r] < VALU_TO_MATRIX_STATES:
+                                hazards.append(f"{op} at 0x{addr:x} reads v{r} {valu_write[r]} wait states after a VALU wrote it "
+                                               f"(needs {VALU_TO_MATRIX_STATES})")
+                step = int(args.strip() or 0) + 1 if op == "s_nop" else 1
+                for r in list(valu_write):
+                    valu_write[r] += step
+                    if valu_write[r] > 4:
+                        del valu_write[r]
+                if op.startswith("v_") and not MATRIX.match(op) and not op.startswith(("v_cmp", "v_readlane", "v_readfirstlane")):
+                    for r in vgprs_of(ops[0]):
+                        valu_write[r] = 0
+                if op in ("s_branch", "s_endpgm", "s_setpc_b64"):
+                    valu_write.clear()
             m_ = meta[kname]
-            kernels[kname] = {"scratch_bytes": m_.get("private_segment_fixed_size", 0), "vgpr": m_.get("vgpr_count", 0),
+            kernels[kname] = {"min_mfma_read_states": min_seen, "min_operand_states": min_operand, "scratch_bytes": m_.get("private_segment_fixed_size", 0), "vgpr": m_.get("vgpr_count", 0),
                               "agpr": m_.get("agpr_count", 0), "sgpr_spills": m_.get("sgpr_spill_count", 0),
                               "vgpr_spills": m_.get("vgpr_spill_count", 0), "vmcnt0_in_main_loop": vm0, "hazards": hazards,
                               "instructions": len(ins)}
@@ -198,8 +274,16 @@ def main():
             print("  " + b_)
         return 1
     tot_scr = sum(1 for v in table.values() if v["scratch_bytes"])
+    closest = {}
+    for v in table.values():
+        for mop, since in v["min_mfma_read_states"].items():
+            closest[mop] = min(closest.get(mop, since), since)
+    operand = [v["min_operand_states"] for v in table.values() if v["min_operand_states"] is not None]
+    if a.verbose:
+        print("closest VALU read of a matrix result, in wait states:", closest)
+        print("closest matrix read of a VALU result, in wait states:", min(operand) if operand else None)
     print(f"check_isa: ok ({len(table)} kernels, {tot_scr} with scratch within budget, no SGPR-write -> VMEM hazards, "
-          f"no new drained waits in the main loops)")
+          f"no VALU read of a matrix result inside its wait states, no new drained waits in the main loops)")
     return 0
 
 

@@ -5,7 +5,9 @@
 //   interleave  how many VALU instructions fit in the shadow of a 64-cycle MFMA of the SAME wave?
 //               (answer on gfx950: none - fp32 MFMA time and VALU time add up)
 //   stream_read the read-only HBM ceiling (what K1 is, minus its segment logic), plain and nontemporal.
-//   hipcc --offload-arch=gfx950 -O3 tools/hw_probe.hip -o build/hw_probe && build/hw_probe [iters | r]
+//   pk_gap / pk_mate  (mode p) packed fp32 math against the two single-rate instructions of the same arithmetic, in the
+//               gaps of the wave's own bf16 MFMA stream and in a vector-only wave beside a SIMD mate that streams them.
+//   hipcc --offload-arch=gfx950 -O3 tools/hw_probe.hip -o build/hw_probe && build/hw_probe [iters | r | b | p]
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -367,6 +369,157 @@ static void run_interleave_bf16_all(int iters) {
   }
 }
 
+// Packed fp32 math (v_pk_add_f32 / v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth per instruction, issued at half rate)
+// against the two single-rate instructions that do the same arithmetic, in the two placements the split-class kernel has:
+//   gap   after every v_mfma_f32_32x32x16_bf16 of the SAME wave (two accumulator chains alternating) K packed or 2 K
+//         single instructions (inputs loop-invariant, eight result pairs in rotation);
+//   mate  waves 4-7 of a workgroup issue ONLY those vector instructions while waves 0-3 (their SIMD mates) stream the MFMAs.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// OP: 0 add, 1 fma, 2 mul
+template <int OP, bool PACKED>
+__device__ __forceinline__ void pk_or_singles(f32x2& y, const f32x2 xa, const f32x2 xb) {
+  // (the result feeds the same register pair's next turn, eight pairs in rotation: a dead result would let the register
+  // allocator write one pair over and over, and hipcc pads such a pair of statements)
+  if (PACKED) {
+    if (OP == 0) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(y) : "v"(xb));
+    else if (OP == 1) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(y) : "v"(xa), "v"(xb));
+    else asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(y) : "v"(xb));
+  } else {
+    if (OP == 0) asm volatile("v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3" : "+v"(y.x), "+v"(y.y) : "v"(xb.x), "v"(xb.y));
+    else if (OP == 1) asm volatile("v_fma_f32 %0, %2, %3, %0\n\tv_fma_f32 %1, %4, %5, %1" : "+v"(y.x), "+v"(y.y) : "v"(xa.x), "v"(xb.x), "v"(xa.y), "v"(xb.y));
+    else asm volatile("v_mul_f32 %0, %0, %2\n\tv_mul_f32 %1, %1, %3" : "+v"(y.x), "+v"(y.y) : "v"(xb.x), "v"(xb.y));
+  }
+}
+
+template <int OP, bool PACKED, int K>
+__global__ __launch_bounds__(512) void gap_pk(float* out, unsigned long long* cyc, int iters, float a0) {
+  f32x16 acc[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  const unsigned w = 0x3c003c00u + (threadIdx.x & 63);
+  const u32x4 a = {w, w, w, w}, b = {w + 1, w, w + 1, w};
+  const f32x2 xa = {a0 + threadIdx.x * 1e-6f, a0 * 2.f}, xb = {a0 * 3.f, a0 * 5.f};
+  f32x2 y[8];
+#pragma unroll
+  for (int v = 0; v < 8; ++v) y[v] = f32x2{0.f, 0.f};
+  const unsigned long long t0 = __builtin_readcyclecounter();
+  for (int it = 0; it < iters; ++it) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[k & 1]) : "v"(a), "v"(b));
+#pragma unroll
+      for (int v = 0; v < K; ++v) pk_or_singles<OP, PACKED>(y[(k * K + v) & 7], xa, xb);
+    }
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  float s = 0.f;
+#pragma unroll
+  for (int v = 0; v < 8; ++v) s += y[v].x + y[v].y;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += acc[t][r];
+  if ((threadIdx.x & 63) == 0 && blockIdx.x == 0) cyc[threadIdx.x >> 6] = t1 - t0;
+  if (s == 123.456f) out[0] = s;
+}
+
+// mfma_iters x 16 MFMAs on waves 0-3, valu_iters x 32 packed (or 64 single) instructions on waves 4-7
+template <int OP, bool PACKED>
+__global__ __launch_bounds__(512) void mate_pk(float* out, unsigned long long* cyc, int mfma_iters, int valu_iters, float a0) {
+  const int wave = threadIdx.x >> 6;
+  float s = 0.f;
+  const unsigned long long t0 = __builtin_readcyclecounter();
+  if (wave < 4) {
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    const unsigned w = 0x3c003c00u + (threadIdx.x & 63);
+    const u32x4 a = {w, w, w, w}, b = {w + 1, w, w + 1, w};
+    for (int it = 0; it < mfma_iters; ++it)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[k & 1]) : "v"(a), "v"(b));
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s += acc[t][r];
+  } else {
+    const f32x2 xa = {a0 + threadIdx.x * 1e-6f, a0 * 2.f}, xb = {a0 * 3.f, a0 * 5.f};
+    f32x2 y[8];
+#pragma unroll
+    for (int v = 0; v < 8; ++v) y[v] = f32x2{0.f, 0.f};
+    for (int it = 0; it < valu_iters; ++it)
+#pragma unroll
+      for (int v = 0; v < 32; ++v) pk_or_singles<OP, PACKED>(y[v & 7], xa, xb);
+#pragma unroll
+    for (int v = 0; v < 8; ++v) s += y[v].x + y[v].y;
+  }
+  const unsigned long long t1 = __builtin_readcyclecounter();
+  if ((threadIdx.x & 63) == 0 && blockIdx.x == 0) cyc[wave] = t1 - t0;
+  if (s == 123.456f) out[0] = s;
+}
+
+static const char* pk_name(int op, bool packed) {
+  static const char* n[2][3] = {{"2 v_add_f32", "2 v_fma_f32", "2 v_mul_f32"}, {"v_pk_add_f32", "v_pk_fma_f32", "v_pk_mul_f32"}};
+  return n[packed][op];
+}
+
+template <int OP, bool PACKED, int K>
+static void run_gap_pk(int iters, int waves) {
+  float* out;
+  unsigned long long *cyc, h[8];
+  hipMalloc(&out, 4);
+  hipMalloc(&cyc, 64);
+  gap_pk<OP, PACKED, K><<<256, waves * 64>>>(out, cyc, iters, 1e-3f);
+  hipDeviceSynchronize();
+  gap_pk<OP, PACKED, K><<<256, waves * 64>>>(out, cyc, iters, 1e-3f);
+  hipDeviceSynchronize();
+  hipMemcpy(h, cyc, 64, hipMemcpyDeviceToHost);
+  printf("{\"probe\": \"pk_gap\", \"mfma\": \"v_mfma_f32_32x32x16_bf16\", \"waves_per_simd\": %d, \"form\": \"%s\", \"pairs_per_mfma\": %d, "
+         "\"cycles_per_slot\": %.1f, \"cycles_per_slot_per_wave_on_simd\": %.1f}\n",
+         waves / 4, pk_name(OP, PACKED), K, (double)h[0] / (iters * 8.0), (double)h[0] / (iters * 8.0) / (waves / 4));
+  hipFree(out);
+  hipFree(cyc);
+}
+
+template <int OP, bool PACKED>
+static void run_mate_pk(int mfma_iters, int valu_iters) {
+  float* out;
+  unsigned long long *cyc, h[8];
+  hipMalloc(&out, 4);
+  hipMalloc(&cyc, 64);
+  mate_pk<OP, PACKED><<<256, 512>>>(out, cyc, mfma_iters, valu_iters, 1e-3f);
+  hipDeviceSynchronize();
+  mate_pk<OP, PACKED><<<256, 512>>>(out, cyc, mfma_iters, valu_iters, 1e-3f);
+  hipDeviceSynchronize();
+  hipMemcpy(h, cyc, 64, hipMemcpyDeviceToHost);
+  printf("{\"probe\": \"pk_mate\", \"mfma\": \"v_mfma_f32_32x32x16_bf16\", \"form\": \"%s\", \"mfma_iters\": %d, \"mate_iters\": %d, "
+         "\"cycles_per_mfma\": %.1f, \"cycles_per_pair\": %.2f}\n",
+         pk_name(OP, PACKED), mfma_iters, valu_iters, mfma_iters ? (double)h[0] / (mfma_iters * 16.0) : 0.0,
+         valu_iters ? (double)h[4] / (valu_iters * 32.0) : 0.0);
+  hipFree(out);
+  hipFree(cyc);
+}
+
+template <int OP>
+static void run_pk_all(int iters) {
+  for (int waves = 4; waves <= 8; waves += 4) {
+    run_gap_pk<OP, true, 2>(iters, waves);
+    run_gap_pk<OP, false, 2>(iters, waves);
+    run_gap_pk<OP, true, 4>(iters, waves);
+    run_gap_pk<OP, false, 4>(iters, waves);
+  }
+  // the mate alone, then beside an MFMA stream of about the same length (16 MFMAs = 512 cycles ~ 32 pairs x 16 cycles)
+  run_mate_pk<OP, true>(0, iters);
+  run_mate_pk<OP, false>(0, iters);
+  run_mate_pk<OP, true>(iters, iters);
+  run_mate_pk<OP, false>(iters, iters);
+}
+
 template <int NACC>
 static void run(int waves_per_cu, int iters) {
   float* out;
@@ -412,6 +565,14 @@ int main(int argc, char** argv) {
   if (argc > 1 && argv[1][0] == 'b') {  // `hw_probe b`: only the bf16 MFMA beside the split's vector work
     run_interleave_bf16_all<false>(20000);
     run_interleave_bf16_all<true>(20000);
+    return 0;
+  }
+  if (argc > 1 && argv[1][0] == 'p') {  // `hw_probe p`: packed fp32 math against its two singles, beside the bf16 MFMA
+    run_gap_pk<0, true, 0>(20000, 4);    // the bare MFMA slot, one and two waves per SIMD
+    run_gap_pk<0, true, 0>(20000, 8);
+    run_pk_all<0>(20000);
+    run_pk_all<1>(20000);
+    run_pk_all<2>(20000);
     return 0;
   }
   const int iters = argc > 1 ? atoi(argv[1]) : 100000;  // ~0.1 s of MFMA per launch

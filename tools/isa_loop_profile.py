@@ -43,6 +43,12 @@ def classify(op):
     return "salu"
 
 
+def same_sources(args):
+    """Both sources of a two-source instruction name the same register (`v1, v2, v2`)."""
+    ops = [o.strip() for o in args.split(",")]
+    return len(ops) >= 3 and ops[1] == ops[2] and ops[1].startswith("v")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("obj")
@@ -94,7 +100,12 @@ def main():
     print("  mix:", dict(sorted(hist.items(), key=lambda kv: -kv[1])), "| s_nop wait states:", nops)
     # the vector instructions that carry no arithmetic of the result: spill restores, selects, compares
     detail = collections.Counter(k for _, op, _, _ in body for k in ("v_readlane", "v_writelane", "v_cndmask", "v_cmp") if op.startswith(k))
+    # `v_max_f32 vX, vY, vY`: the canonicalising instruction hipcc puts in front of an fmaxf whose input it cannot prove
+    # canonical (a matrix instruction's output); v_pk_*: packed math (two fp32 lanes' worth per instruction)
+    same_max = sum(1 for _, op, args, _ in body if op.startswith("v_max_f32") and same_sources(args))
+    packed = sum(1 for _, op, _, _ in body if op.startswith("v_pk_"))
     print("  vector detail:", ", ".join(f"{k} {detail[k]}" for k in ("v_readlane", "v_writelane", "v_cndmask", "v_cmp")),
+          f"| same-source v_max {same_max}, v_pk_* {packed}",
           f"| s_nop instructions {hist['s_nop']} | vector (valu, no mfma) {hist['valu']}")
     inner = [l for l in loops if main_loop[0] <= l[0] and l[1] <= main_loop[1] and l != main_loop]
     print(f"  inner loops: {len(inner)}")
