@@ -163,6 +163,8 @@ _SIGNATURES = {
     "gnc_rows_div_degree_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
     "gnc_adam_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p]),
+    "gnc_adam_step_hp64_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_float, c_float,
+                                         c_void_p, c_void_p, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1998,6 +2000,7 @@ def adam_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, ex
     if step.dtype != torch.int64 or scratch.dtype != torch.float32 or scratch.numel() < 2:
         raise ValueError("adam_step: step must be int64 [1], scratch float32 [2]")
     with torch.cuda.device(param.device):
-        _check(_launch("adam_flat", param, lambda: lib.gnc_adam_step_f32(
+        # lr and the betas go down as the doubles they are: the bias corrections are then torch.optim.Adam's
+        _check(_launch("adam_flat", param, lambda: lib.gnc_adam_step_hp64_f32(
             param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, lr, beta1, beta2, eps, weight_decay,
             step.data_ptr(), scratch.data_ptr(), _stream(param)), 28.0 * n), "gnc_adam_step_f32")

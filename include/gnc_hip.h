@@ -852,10 +852,17 @@ int gnc_wide_linear_backward_f32(const float* grad_a0, int64_t ld_grad, const fl
  * so far (the call advances it first; bias corrections are derived from it on the device in double precision), so
  * the call sequence is the same on every step and can be replayed from a hipGraph.  `scratch2` is 2 floats of
  * device scratch.  All four buffers 16-B aligned.
+ * gnc_adam_step_hp64_f32 takes lr and the betas as doubles, as Python holds them: the bias corrections and the weights
+ * 1 - beta of the element update are then torch.optim.Adam's, each rounded to fp32 once (a beta rounded to fp32 first
+ * moves 1 - beta by up to 1.3e-5 and 1 - beta^t by up to 3.7e-6 of itself).  gnc_adam_step_f32 widens its floats, which
+ * is Adam with the betas' fp32 values throughout.
  */
 int gnc_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                       float beta1, float beta2, float eps, float weight_decay, int64_t* step, float* scratch2,
                       void* stream);
+int gnc_adam_step_hp64_f32(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, double lr,
+                           double beta1, double beta2, float eps, float weight_decay, int64_t* step, float* scratch2,
+                           void* stream);
 
 #ifdef __cplusplus
 }

@@ -172,16 +172,18 @@ def test_forward_batched_variable_size_readout_policy(G):
     nn_ = 156
     torch.manual_seed(8)
     m = G.CombinedModel(G.GraphNet(**S.graphnet_kwargs(32, 2)), num_nodes=nn_, classes=2)
+    w = [p.detach().cpu().double() for fc in (m.classifier.fc1, m.classifier.fc2, m.classifier.fc3) for p in (fc.weight, fc.bias)]
     with torch.no_grad():
         lb = m.forward_batched(batch.x, batch.pos, batch.edge_index, graph_ptr=batch.graph_ptr)
         assert lb.shape == (5, 2)
         for gi in range(5):
             s = batch.slice_graphs(gi, gi + 1)
             y = m.graph_net(s.x, s.pos, s.edge_index).flatten()
-            v = torch.zeros(nn_)
-            v[:min(nn_, y.numel())] = y[:nn_]
-            ref = m.classifier(v.to(DEV)).cpu()
-            assert max_abs(lb[gi], ref) < 2e-6
+            v = torch.zeros(nn_, dtype=torch.float64)
+            v[:min(nn_, y.numel())] = y[:nn_].cpu().double()
+            # the classifier by formula in float64 on the CPU: m.classifier(v) would be the read-out kernel checking itself
+            ref = w[4] @ torch.relu(w[2] @ torch.relu(w[0] @ v + w[1]) + w[3]) + w[5]
+            assert max_abs(lb[gi].cpu(), ref) < 2e-6
 
 
 def test_fused_aggregation_forward_is_bit_identical_to_separate_k1(G, monkeypatch):
