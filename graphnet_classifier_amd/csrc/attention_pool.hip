@@ -7,53 +7,28 @@
 // keeps (m_g, Z_g) per graph ([G, 2] floats); the backward recomputes alpha_v from them, no [rows] array is stored.  A non-finite
 // score stays inside its graph: fmaxf drops a NaN from m_g, expf(NaN - m_g) makes Z_g and every column of that graph NaN.
 //
-// Summation order: K17's (csrc/pool_readout.hip), for Z_g and for the weighted column sums alike - chunks of kChunkRows rows
-// counted from the graph's own first row; inside a chunk row-lane l adds rows l, l + L, ... in ascending order onto +0.0 (the
-// product e_v y[v, c] enters by ONE fmaf, in chunk_reduce, which both regimes call), the L lane sums are folded by the halving
-// tree, the chunk sums in ascending order onto +0.0.  The maximum is exact in any order.  Both regimes therefore give the same
-// bits, as does a graph pooled alone or inside any batch:
-//   * many graphs: one workgroup per (graph, column tile) forms the graph's maximum and walks its chunks itself;
-//   * few large graphs (split): a launch of one workgroup per graph forms the maxima, one workgroup per (chunk, column tile) writes
-//     its partial Z and column sums to a workspace slot, a merge launch folds each graph's slots in ascending order and divides.
-// No atomics, no ticket counters; the regime comes from gnc_graph_pool_plan (rows, C, G alone).
-#include "gnc_common.h"
+// The forward is the chunked per-graph reduction of csrc/graph_reduce.h - the summation order is defined there, for both regimes,
+// and is the one K17 sums in because it is the same code - carrying the weighted column sums and Z: AttnOp below.  The product
+// e_v y[v, c] enters by ONE fmaf.  The maximum, exact in any order, is K19's own step in front of the shared body: the graph-owned
+// workgroup forms it itself, the split regime by a launch of one workgroup per graph (attn_max_kernel).  In the split regime the
+// workspace layout is attention_pool_index.h's.
+#include "graph_reduce.h"
 #include "attention_pool_index.h"
 
 #include <math.h>
 
 namespace {
 
-using namespace gnc_pool;
+using namespace gnc_reduce;
 
-constexpr int kT = kBlockThreads;
-
-struct AttnArgs {
-  const float* y;
+struct AttnArgs : ReduceArgs {
   const float* scores;
-  const int64_t* graph_ptr;
-  int64_t rows, C, G;
   float* out;
   int64_t ld_out;
   float* saved;   // [G, 2]: (m_g, Z_g); (0, 0) for an empty graph
   float* ws_col;  // split regime: [slots, C]
   float* ws_z;    // split regime: [slots]
-  int64_t slots;
-  int32_t col_lanes, row_lanes;  // Geometry of C
-  int32_t y16;                   // y is 16-byte aligned (vec 4: one dwordx4 load per row and thread)
 };
-
-template <int VEC>
-__device__ __forceinline__ void load_cols(const float* __restrict__ p, bool p16, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    if (p16) {
-      const float4 q = *reinterpret_cast<const float4*>(p);
-      v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-      return;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < VEC; ++u) v[u] = p[u];
-}
 
 // alpha_v from the saved (m_g, Z_g): the backward and the weights launch share it
 __device__ __forceinline__ float softmax_weight(float s, float m, float Z) { return expf(s - m) / Z; }
@@ -74,80 +49,74 @@ __device__ __forceinline__ float block_score_max(const float* __restrict__ score
   return m;
 }
 
-// Z and the weighted column sums of rows [row0, row0 + nr) of the workgroup's column tile; the result is in the threads of
-// row-lane 0.  Every thread of the workgroup calls it (it synchronises); a thread whose columns lie behind C contributes nothing.
+// K19's operation (graph_reduce.h): the e-weighted sum of every column and, per thread, Z; it carries the graph's maximum m
 template <int VEC>
-__device__ __forceinline__ void chunk_reduce(const AttnArgs& a, float m, int64_t row0, int nr, int64_t col0, bool active, int rl,
-                                             float (&s_acc)[VEC][kT], float (&s_z)[kT], float (&acc)[VEC], float& z) {
-  const int t = threadIdx.x;
-  const int L = a.row_lanes, CL = a.col_lanes;
+struct AttnOp {
+  const AttnArgs& a;
+  float m;
+  struct Partial {
+    float acc[VEC], z;
+  };
+  struct Shared {
+    float acc[VEC][kT], z[kT];
+  };
+  __device__ __forceinline__ Partial identity() const {
+    Partial p;
 #pragma unroll
-  for (int u = 0; u < VEC; ++u) acc[u] = 0.f;
-  z = 0.f;
-  if (active) {
-    const float* __restrict__ base = a.y + row0 * a.C + col0;
-    const float* __restrict__ sc = a.scores + row0;
-#pragma unroll 4
-    for (int r = rl; r < nr; r += L) {
-      const float e = expf(sc[r] - m);
-      float v[VEC];
-      load_cols<VEC>(base + (int64_t)r * a.C, a.y16 != 0, v);
-      z += e;
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) acc[u] = fmaf(e, v[u], acc[u]);
-    }
+    for (int u = 0; u < VEC; ++u) p.acc[u] = 0.f;
+    p.z = 0.f;
+    return p;
   }
-  __syncthreads();  // the previous chunk's tree has been read
-#pragma unroll
-  for (int u = 0; u < VEC; ++u) s_acc[u][t] = acc[u];
-  s_z[t] = z;
-  for (int s = L >> 1; s >= 1; s >>= 1) {
-    __syncthreads();
-    if (rl < s) {
-      const int o = t + s * CL;  // row-lane rl + s, same columns
-#pragma unroll
-      for (int u = 0; u < VEC; ++u) {
-        acc[u] += s_acc[u][o];
-        s_acc[u][t] = acc[u];
-      }
-      z += s_z[o];
-      s_z[t] = z;
-    }
+  // graph-owned: the workgroup forms m_g itself and keeps it, as attn_max_kernel does for the split regime
+  __device__ __forceinline__ void graph_begin(int64_t g, int64_t ra, int64_t rb, Shared& sh) {
+    m = block_score_max(a.scores, ra, rb, sh.z);
+    if (threadIdx.x == 0 && blockIdx.y == 0) a.saved[2 * g] = rb > ra ? m : 0.f;
   }
-}
+  __device__ __forceinline__ void slot_begin(int64_t g) { m = a.saved[2 * g]; }
+  __device__ __forceinline__ void row(Partial& p, int64_t row, const float (&v)[VEC]) const {
+    const float e = expf(a.scores[row] - m);
+    p.z += e;
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) p.acc[u] = fmaf(e, v[u], p.acc[u]);
+  }
+  __device__ __forceinline__ void fold(Partial& p, const Partial& q) const {
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) p.acc[u] += q.acc[u];
+    p.z += q.z;
+  }
+  __device__ __forceinline__ void park(Shared& sh, int t, const Partial& p) const {
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) sh.acc[u][t] = p.acc[u];
+    sh.z[t] = p.z;
+  }
+  __device__ __forceinline__ Partial parked(const Shared& sh, int t) const {
+    Partial p;
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) p.acc[u] = sh.acc[u][t];
+    p.z = sh.z[t];
+    return p;
+  }
+  // out[g, col0 ...] and, from the thread of column 0, Z_g (every thread of a column holds the same Z)
+  __device__ __forceinline__ void store(int64_t g, int64_t n, int64_t col0, const Partial& p) const {
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) a.out[g * a.ld_out + col0 + u] = n > 0 ? p.acc[u] / p.z : 0.f;
+    if (col0 == 0) a.saved[2 * g + 1] = n > 0 ? p.z : 0.f;
+  }
+  __device__ __forceinline__ void store_slot(int64_t slot, int64_t col0, const Partial& p) const {
+#pragma unroll
+    for (int u = 0; u < VEC; ++u) a.ws_col[gnc_attn::ws_col_index(slot, a.C, col0 + u)] = p.acc[u];
+    if (col0 == 0) a.ws_z[slot] = p.z;
+  }
+  __device__ __forceinline__ Partial slot_partial(int64_t slot, int64_t c) const {
+    return Partial{{a.ws_col[gnc_attn::ws_col_index(slot, a.C, c)]}, a.ws_z[slot]};
+  }
+};
 
-// many graphs: workgroup (g, column tile)
 template <int VEC>
 __global__ __launch_bounds__(kT) void attn_graphs_kernel(const AttnArgs a) {
-  __shared__ float s_acc[VEC][kT];
-  __shared__ float s_z[kT];
-  const int t = threadIdx.x, cl = t % a.col_lanes, rl = t / a.col_lanes;
-  const int64_t g = blockIdx.x;
-  const int64_t col0 = ((int64_t)blockIdx.y * a.col_lanes + cl) * VEC;
-  const bool active = col0 < a.C;  // vec 4: C is a multiple of 4, so col0 + 3 < C as well
-  int64_t ra, rb;
-  graph_range(a.graph_ptr, g, a.rows, ra, rb);
-  const int64_t n = rb - ra;
-  const float m = block_score_max(a.scores, ra, rb, s_z);
-  float tot[VEC], Z = 0.f;
-#pragma unroll
-  for (int u = 0; u < VEC; ++u) tot[u] = 0.f;
-  for (int64_t k0 = 0; k0 < n; k0 += kChunkRows) {
-    const int nr = (int)(n - k0 < kChunkRows ? n - k0 : kChunkRows);
-    float acc[VEC], z;
-    chunk_reduce<VEC>(a, m, ra + k0, nr, col0, active, rl, s_acc, s_z, acc, z);
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) tot[u] += acc[u];
-    Z += z;
-  }
-  if (rl == 0 && active) {
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) a.out[g * a.ld_out + col0 + u] = n > 0 ? tot[u] / Z : 0.f;
-  }
-  if (t == 0 && blockIdx.y == 0) {  // thread 0 is row-lane 0 of column 0: always active
-    a.saved[2 * g] = n > 0 ? m : 0.f;
-    a.saved[2 * g + 1] = n > 0 ? Z : 0.f;
-  }
+  __shared__ typename AttnOp<VEC>::Shared sh;
+  AttnOp<VEC> op{a, 0.f};
+  reduce_graph<VEC>(a, op, sh);
 }
 
 // split regime, first launch: workgroup g -> m_g
@@ -160,47 +129,17 @@ __global__ __launch_bounds__(kT) void attn_max_kernel(const AttnArgs a) {
   if (threadIdx.x == 0) a.saved[2 * g] = rb > ra ? m : 0.f;
 }
 
-// split regime, second launch: workgroup (slot, column tile) -> the chunk's partials
 template <int VEC>
 __global__ __launch_bounds__(kT) void attn_chunks_kernel(const AttnArgs a) {
-  __shared__ float s_acc[VEC][kT];
-  __shared__ float s_z[kT];
-  const int t = threadIdx.x, cl = t % a.col_lanes, rl = t / a.col_lanes;
-  const int64_t slot = blockIdx.x;
-  const int64_t col0 = ((int64_t)blockIdx.y * a.col_lanes + cl) * VEC;
-  const bool active = col0 < a.C;
-  int64_t g, row0;
-  int nr;
-  if (slot >= a.slots || !slot_chunk(a.graph_ptr, a.G, a.rows, slot, g, row0, nr)) return;  // uniform over the workgroup
-  const float m = a.saved[2 * g];
-  float acc[VEC], z;
-  chunk_reduce<VEC>(a, m, row0, nr, col0, active, rl, s_acc, s_z, acc, z);
-  if (rl == 0 && active) {
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) a.ws_col[gnc_attn::ws_col_index(slot, a.C, col0 + u)] = acc[u];
-  }
-  if (t == 0 && blockIdx.y == 0) a.ws_z[slot] = z;
+  __shared__ typename AttnOp<VEC>::Shared sh;
+  AttnOp<VEC> op{a, 0.f};
+  reduce_slot<VEC>(a, op, sh);
 }
 
-// split regime, third launch: thread (g, c) folds the graph's slots in ascending order and divides
-__global__ __launch_bounds__(kT) void attn_merge_kernel(const AttnArgs a) {
-  const int64_t g = blockIdx.x;
-  const int64_t c = (int64_t)blockIdx.y * kT + threadIdx.x;
-  if (c >= a.C) return;
-  int64_t ra, rb;
-  graph_range(a.graph_ptr, g, a.rows, ra, rb);
-  const int64_t n = rb - ra;
-  const int64_t s0 = first_slot(a.graph_ptr, g, a.rows);
-  int64_t s1 = s0 + chunks_of(n);
-  if (s1 > a.slots) s1 = a.slots;  // offsets that overlap: only the slots that exist (and were written)
-  float tot = 0.f, Z = 0.f;
-  for (int64_t s = s0; s < s1; ++s) {
-    tot += a.ws_col[gnc_attn::ws_col_index(s, a.C, c)];
-    Z += a.ws_z[s];
-  }
-  a.out[g * a.ld_out + c] = n > 0 ? tot / Z : 0.f;
-  if (c == 0) a.saved[2 * g + 1] = n > 0 ? Z : 0.f;
-}
+__global__ __launch_bounds__(kT) void attn_merge_kernel(const AttnArgs a) { merge_graph(a, AttnOp<1>{a, 0.f}); }
+
+const ReduceKernels<AttnArgs> kAttnKernels = {attn_graphs_kernel<1>, attn_graphs_kernel<4>, attn_chunks_kernel<1>, attn_chunks_kernel<4>,
+                                              attn_merge_kernel,     "attn_graphs_kernel",  "attn_chunks_kernel",  "attn_merge_kernel"};
 
 struct AttnBwdArgs {
   const float* dout;
@@ -219,7 +158,8 @@ struct AttnBwdArgs {
 template <int VEC>
 __global__ __launch_bounds__(kT) void attn_backward_kernel(const AttnBwdArgs a) {
   const int W = a.lanes, rpb = kT / W;
-  const int lane = threadIdx.x % W, sub = threadIdx.x / W;
+  const RowLane x = row_lane(threadIdx.x, W);
+  const int lane = x.lane, sub = x.sub;
   const int64_t per_row = a.C / VEC;
   for (int64_t base = (int64_t)blockIdx.x * rpb; base < a.rows; base += (int64_t)gridDim.x * rpb) {
     const int64_t r = base + sub;
@@ -240,7 +180,7 @@ __global__ __launch_bounds__(kT) void attn_backward_kernel(const AttnBwdArgs a) 
           for (int u = 0; u < VEC; ++u) go[u] = a.dout[g * a.ld_dout + c0 + u];
           if (a.ds) {
             float v[VEC];
-            load_cols<VEC>(a.y + r * a.C + c0, a.y16 != 0, v);
+            load_vec<VEC>(a.y + r * a.C + c0, a.y16 != 0, v);
 #pragma unroll
             for (int u = 0; u < VEC; ++u) dot = fmaf(go[u], v[u] - a.out[g * a.ld_out + c0 + u], dot);
           }
@@ -288,7 +228,7 @@ bool unsupported(const char* who, int64_t rows, int64_t C, int64_t G, gnc_graph_
   return true;
 }
 
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+bool aligned4(const void* p) { return gnc::aligned_to(p, 4); }
 
 }  // namespace
 
@@ -306,7 +246,7 @@ extern "C" int gnc_graph_attention_pool_forward_f32(const float* y, const float*
   GNC_REQUIRE(graph_ptr && out && saved && ((y && scores) || rows == 0),
               "gnc_graph_attention_pool_forward_f32: null y / scores / graph_ptr / out / saved");
   GNC_REQUIRE(ld_out >= C, "gnc_graph_attention_pool_forward_f32: ld_out smaller than C");
-  GNC_REQUIRE(aligned4(y) && aligned4(scores) && aligned4(out) && aligned4(saved) && (reinterpret_cast<uintptr_t>(graph_ptr) & 7u) == 0,
+  GNC_REQUIRE(aligned4(y) && aligned4(scores) && aligned4(out) && aligned4(saved) && gnc::aligned_to(graph_ptr, 8),
               "gnc_graph_attention_pool_forward_f32: a pointer is not aligned to its element size");
   AttnArgs a = {};
   a.y = y, a.scores = scores, a.graph_ptr = graph_ptr, a.rows = rows, a.C = C, a.G = num_graphs;
@@ -314,27 +254,16 @@ extern "C" int gnc_graph_attention_pool_forward_f32(const float* y, const float*
   a.col_lanes = (int32_t)plan.col_lanes, a.row_lanes = (int32_t)plan.row_lanes;
   a.y16 = gnc::aligned16(y) ? 1 : 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 block(kT);
-  if (!plan.split) {
-    const dim3 grid((unsigned)num_graphs, (unsigned)plan.col_tiles);
-    if (plan.vec == 4) attn_graphs_kernel<4><<<grid, block, 0, st>>>(a);
-    else attn_graphs_kernel<1><<<grid, block, 0, st>>>(a);
-    return gnc::check_launch("attn_graphs_kernel");
-  }
+  if (!plan.split) return launch_graph_owned(kAttnKernels, a, plan, st);
   const int64_t need = gnc_attn::workspace_floats(plan.slots, C);
   GNC_REQUIRE(workspace && workspace_floats >= need && aligned4(workspace),
               "gnc_graph_attention_pool_forward_f32: the split regime needs a workspace of %lld floats", (long long)need);
   a.slots = plan.slots;
   a.ws_col = workspace;
   a.ws_z = workspace + gnc_attn::ws_z_index(plan.slots, C, 0);
-  attn_max_kernel<<<dim3((unsigned)num_graphs), block, 0, st>>>(a);
+  attn_max_kernel<<<dim3((unsigned)num_graphs), dim3(kT), 0, st>>>(a);
   if (int rc = gnc::check_launch("attn_max_kernel")) return rc;
-  const dim3 grid((unsigned)plan.slots, (unsigned)plan.col_tiles);
-  if (plan.vec == 4) attn_chunks_kernel<4><<<grid, block, 0, st>>>(a);
-  else attn_chunks_kernel<1><<<grid, block, 0, st>>>(a);
-  if (int rc = gnc::check_launch("attn_chunks_kernel")) return rc;
-  attn_merge_kernel<<<dim3((unsigned)num_graphs, (unsigned)gnc::ceil_div(C, kT)), block, 0, st>>>(a);
-  return gnc::check_launch("attn_merge_kernel");
+  return launch_split(kAttnKernels, a, plan, st);
 }
 
 extern "C" int gnc_graph_attention_pool_backward_f32(const float* dout, int64_t ld_dout, const float* y, const float* scores,
@@ -346,17 +275,15 @@ extern "C" int gnc_graph_attention_pool_backward_f32(const float* dout, int64_t 
   GNC_REQUIRE(!ds || (out && (y || rows == 0)), "gnc_graph_attention_pool_backward_f32: ds needs y and out");
   GNC_REQUIRE(ld_dout >= C && (!ds || ld_out >= C), "gnc_graph_attention_pool_backward_f32: ld_dout / ld_out smaller than C");
   GNC_REQUIRE(aligned4(dout) && aligned4(y) && aligned4(scores) && aligned4(out) && aligned4(saved) && aligned4(dy) && aligned4(ds) &&
-                  (reinterpret_cast<uintptr_t>(graph_ptr) & 7u) == 0,
+                  gnc::aligned_to(graph_ptr, 8),
               "gnc_graph_attention_pool_backward_f32: a pointer is not aligned to its element size");
   if (rows == 0) return GNC_OK;
-  const gnc_attn::RowGeometry geo = gnc_attn::row_geometry(C);
+  const RowGeometry geo = row_geometry(C);
   AttnBwdArgs a = {};
   a.dout = dout, a.y = ds ? y : nullptr, a.scores = scores, a.out = ds ? out : nullptr, a.saved = saved, a.graph_ptr = graph_ptr;
   a.rows = rows, a.C = C, a.G = num_graphs, a.ld_dout = ld_dout, a.ld_out = ld_out, a.dy = dy, a.ds = ds;
   a.lanes = geo.lanes, a.y16 = gnc::aligned16(y) ? 1 : 0, a.dy16 = gnc::aligned16(dy) ? 1 : 0;
-  int64_t blocks = gnc::ceil_div(rows, geo.rows_per_block);
-  const int64_t cap = 8ll * gnc::num_cu();
-  blocks = blocks > cap ? cap : blocks;
+  const int64_t blocks = gnc::capped_blocks(rows, geo.rows_per_block);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (geo.vec == 4) attn_backward_kernel<4><<<dim3((unsigned)blocks), dim3(kT), 0, st>>>(a);
   else attn_backward_kernel<1><<<dim3((unsigned)blocks), dim3(kT), 0, st>>>(a);
@@ -367,12 +294,10 @@ extern "C" int gnc_graph_attention_weights_f32(const float* scores, const float*
                                                int64_t rows, float* alpha, void* stream) {
   if (unsupported("gnc_graph_attention_weights_f32", rows, 1, num_graphs, nullptr)) return GNC_ERR_UNSUPPORTED;
   GNC_REQUIRE(saved && graph_ptr && ((scores && alpha) || rows == 0), "gnc_graph_attention_weights_f32: null scores / saved / graph_ptr / alpha");
-  GNC_REQUIRE(aligned4(scores) && aligned4(saved) && aligned4(alpha) && (reinterpret_cast<uintptr_t>(graph_ptr) & 7u) == 0,
+  GNC_REQUIRE(aligned4(scores) && aligned4(saved) && aligned4(alpha) && gnc::aligned_to(graph_ptr, 8),
               "gnc_graph_attention_weights_f32: a pointer is not aligned to its element size");
   if (rows == 0) return GNC_OK;
-  int64_t blocks = gnc::ceil_div(rows, kT);
-  const int64_t cap = 8ll * gnc::num_cu();
-  blocks = blocks > cap ? cap : blocks;
+  const int64_t blocks = gnc::capped_blocks(rows, kT);
   attn_weights_kernel<<<dim3((unsigned)blocks), dim3(kT), 0, static_cast<hipStream_t>(stream)>>>(scores, saved, graph_ptr, num_graphs,
                                                                                                rows, alpha);
   return gnc::check_launch("attn_weights_kernel");

@@ -27,7 +27,15 @@ int num_cu();
 constexpr int kBlock = 256;      // default workgroup: 4 waves, one per SIMD
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// `bytes` is a power of two; a null pointer is aligned to everything
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+inline bool aligned16(const void* p) { return aligned_to(p, 16); }
+// Grid of a grid-stride launch: ceil(work / per_block) workgroups, at most `per_cu` for each compute unit and at least one
+// (callers with no work at all return before they launch).
+inline int64_t capped_blocks(int64_t work, int64_t per_block, int per_cu = 8) {
+  const int64_t blocks = ceil_div(work, per_block), cap = (int64_t)per_cu * num_cu();
+  return blocks > cap ? cap : (blocks < 1 ? 1 : blocks);
+}
 
 }  // namespace gnc
 

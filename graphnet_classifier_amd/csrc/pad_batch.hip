@@ -185,9 +185,7 @@ extern "C" int gnc_pad_graph_batch(const float* x, int32_t fx, const float* pos,
   for (int g = 0; g <= G; ++g) a.graph_ptr[g] = graph_ptr[g], a.edge_ptr[g] = edge_ptr[g];
   for (int g = 0; g < G && labels; ++g) a.labels[g] = labels[g];
   const int64_t total = gnc::ceil_div(a.m_x, 4) + gnc::ceil_div(a.m_p, 4) + 2 * gnc::ceil_div(a.C, 2) + 2 * (int64_t)G + 1;
-  int64_t blocks = gnc::ceil_div(total, gnc::kBlock);
-  const int64_t cap = 4ll * gnc::num_cu();
-  blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+  const int64_t blocks = gnc::capped_blocks(total, gnc::kBlock, 4);
   pad_graph_batch_kernel<<<dim3((unsigned)blocks), dim3(gnc::kBlock), 0, static_cast<hipStream_t>(stream)>>>(a);
   return gnc::check_launch("pad_graph_batch_kernel");
 }

@@ -1,6 +1,8 @@
-// Index arithmetic of K17 (csrc/pool_readout.hip), kept apart from the kernels so that the same functions compile for the host:
-// the plan (gnc_graph_pool_plan) calls them there, and a host program can walk every (workgroup, thread) of a launch and check
-// each address against the buffers before the kernels ever run on a device.  Nothing here touches memory except `graph_ptr`.
+// Index arithmetic of the per-graph pooling kernels (K17 csrc/pool_readout.hip, K19 csrc/attention_pool.hip through
+// csrc/graph_reduce.h, the row tiling of K20 csrc/topk_pool.hip), kept apart from the kernels so that the same functions compile
+// for the host: the plan (gnc_graph_pool_plan) calls them there, and the host programs over tools/pool_walk.h walk every
+// (workgroup, thread) of a launch through the very functions the kernels call and check each address against the buffers before
+// a kernel ever runs on a device.  Nothing here touches memory except `graph_ptr`.
 #pragma once
 #include <stdint.h>
 
@@ -41,6 +43,28 @@ GNC_POOL_HD Geometry geometry(int64_t C) {
   return g;
 }
 
+// Thread t of the workgroup of column tile `tile`: its column lane, its row lane and the first of its `vec` columns (the thread
+// takes part in the row loop only when col0 < C; vec 4: C is a multiple of 4, so col0 + 3 < C as well).
+struct Tile {
+  int cl, rl;
+  int64_t col0;
+};
+
+GNC_POOL_HD Tile tile_of(int t, int64_t tile, const Geometry& geo) {
+  Tile x;
+  x.cl = t % geo.col_lanes;
+  x.rl = t / geo.col_lanes;
+  x.col0 = (tile * geo.col_lanes + x.cl) * geo.vec;
+  return x;
+}
+
+// Halving tree over the row lanes: at step s (row_lanes / 2, ..., 1) thread t of a row lane < s adds the thread of row lane
+// rl + s that owns the same columns.
+GNC_POOL_HD int tree_partner(int t, int s, const Geometry& geo) { return t + s * geo.col_lanes; }
+
+// Rows of the chunk that starts at row k0 (a multiple of kChunkRows, counted from the graph's first row) of an n-row graph.
+GNC_POOL_HD int chunk_len(int64_t n, int64_t k0) { return (int)(n - k0 < kChunkRows ? n - k0 : kChunkRows); }
+
 // Rows [a, b) of graph g, clamped into [0, rows]: offsets that point outside y read as shorter or empty graphs.
 GNC_POOL_HD void graph_range(const int64_t* graph_ptr, int64_t g, int64_t rows, int64_t& a, int64_t& b) {
   a = graph_ptr[g];
@@ -65,6 +89,17 @@ GNC_POOL_HD int64_t first_slot(const int64_t* graph_ptr, int64_t g, int64_t rows
   return cum;
 }
 
+// Split regime, merge: the rows n of graph g and the slots [s0, s1) of its chunks, in the order they are folded.  With offsets
+// that overlap the chunks can outnumber the slots: only the slots that exist (and were written) are read.
+GNC_POOL_HD void merge_slots(const int64_t* graph_ptr, int64_t g, int64_t rows, int64_t slots, int64_t& n, int64_t& s0, int64_t& s1) {
+  int64_t a, b;
+  graph_range(graph_ptr, g, rows, a, b);
+  n = b - a;
+  s0 = first_slot(graph_ptr, g, rows);
+  s1 = s0 + chunks_of(n);
+  if (s1 > slots) s1 = slots;
+}
+
 // Split regime: the chunk behind workspace slot `slot` - its graph, first row and row count (1 .. R).  false: no chunk (the
 // slots behind the last graph's last chunk).
 GNC_POOL_HD bool slot_chunk(const int64_t* graph_ptr, int64_t G, int64_t rows, int64_t slot, int64_t& g, int64_t& row0, int& nr) {
@@ -74,8 +109,7 @@ GNC_POOL_HD bool slot_chunk(const int64_t* graph_ptr, int64_t G, int64_t rows, i
     const int64_t nch = chunks_of(b - a);
     if (slot < cum + nch) {
       row0 = a + (slot - cum) * kChunkRows;
-      const int64_t left = b - row0;
-      nr = (int)(left < kChunkRows ? left : kChunkRows);
+      nr = chunk_len(b - a, row0 - a);
       return true;
     }
     cum += nch;
@@ -100,5 +134,37 @@ GNC_POOL_HD int64_t graph_of_row(const int64_t* graph_ptr, int64_t G, int64_t ro
   n = b - a;
   return lo;
 }
+
+// K17's backward: item i of a [rows, C / vec] grid-stride walk is `vec` columns from c0 of row r.
+GNC_POOL_HD void backward_item(int64_t i, int64_t per_row, int vec, int64_t& r, int64_t& c0) {
+  r = i / per_row;
+  c0 = (i - r * per_row) * vec;
+}
+
+// Row-wise launches (K19's backward, K20's row compaction): `lanes` threads side by side own ONE row (a power of two <= 64, so a
+// row never straddles a wavefront), each `vec` consecutive columns at a time (4 when C is a multiple of 4); lane l takes the
+// column groups l, l + lanes, ... in ascending order and the lanes' partial dot products are folded by a butterfly (lane l +=
+// lane l ^ s for s = lanes / 2, ..., 1).  A function of C ALONE: it fixes the order of the dot over C.
+struct RowGeometry {
+  int vec, lanes, rows_per_block;
+};
+
+GNC_POOL_HD RowGeometry row_geometry(int64_t C) {
+  RowGeometry g;
+  g.vec = (C % 4 == 0) ? 4 : 1;
+  const int64_t per_row = C / g.vec;  // column groups of a row (vec 1: C itself)
+  int lanes = 1;
+  while (lanes < 64 && lanes < per_row) lanes <<= 1;
+  g.lanes = lanes;
+  g.rows_per_block = kBlockThreads / lanes;
+  return g;
+}
+
+// Thread t of such a workgroup: its lane inside the row and which of the workgroup's rows_per_block rows it works on.
+struct RowLane {
+  int lane, sub;
+};
+
+GNC_POOL_HD RowLane row_lane(unsigned t, int lanes) { return RowLane{(int)(t % lanes), (int)(t / lanes)}; }
 
 }  // namespace gnc_pool

@@ -309,9 +309,7 @@ int launch_vec(const FwdArgs& a, hipStream_t stream) {
   if (small) {
     blocks = gnc::ceil_div((int64_t)a.n * lpr, (int64_t)gnc::kBlock);
   } else {
-    blocks = gnc::ceil_div(gnc::ceil_div(a.n, kChunk), gnc::kBlock / kWave);
-    const int64_t cap = gnc::num_cu() * 16;
-    if (blocks > cap) blocks = cap;
+    blocks = gnc::capped_blocks(gnc::ceil_div(a.n, kChunk), gnc::kBlock / kWave, 16);
   }
   const dim3 grid((unsigned)blocks);
   switch (lpr) {
@@ -336,9 +334,7 @@ int launch_forward(const FwdArgs& a, int mode, hipStream_t stream) {
     if (a.argmax) return launch_vec<HAS_PERM, kMax, true>(a, stream);
     return launch_vec<HAS_PERM, kMax, false>(a, stream);
   }
-  int64_t blocks = gnc::ceil_div(a.n, gnc::kBlock / kWave);
-  const int64_t cap = gnc::num_cu() * 16;
-  if (blocks > cap) blocks = cap;
+  const int64_t blocks = gnc::capped_blocks(a.n, gnc::kBlock / kWave, 16);
   const dim3 grid((unsigned)blocks), block(gnc::kBlock);
   if (mode == kMean)
     segment_reduce_csr_scalar<HAS_PERM, kMean><<<grid, block, 0, stream>>>(a.src, a.ld_src, a.rowptr, a.perm, a.n, a.d, a.out,
@@ -352,12 +348,9 @@ int launch_forward(const FwdArgs& a, int mode, hipStream_t stream) {
 template <int MODE>
 int launch_backward(const float* grad_out, int64_t ld_grad, const int32_t* dst_of_row, const int32_t* rowptr, const int32_t* argmax,
                     int64_t num_rows, int32_t d, float* grad_src, int64_t ld_src, hipStream_t stream) {
-  const int64_t cap = gnc::num_cu() * 16;
   if (vec4_ok(grad_out, ld_grad, d) && vec4_ok(grad_src, ld_src, d) && (MODE == kMean || gnc::aligned16(argmax))) {
     const int lpr = pow2_lanes_for(d);
-    int64_t blocks = gnc::ceil_div(num_rows, 2 * (gnc::kBlock / lpr));
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks = gnc::capped_blocks(num_rows, 2 * (gnc::kBlock / lpr), 16);
     const dim3 grid((unsigned)blocks), block(gnc::kBlock);
     switch (lpr) {
 #define GNC_CASE(L)                                                                                                            \
@@ -373,8 +366,7 @@ int launch_backward(const float* grad_out, int64_t ld_grad, const int32_t* dst_o
     }
     return gnc::check_launch("segment_reduce_backward_vec4");
   }
-  int64_t blocks = gnc::ceil_div(num_rows * d, gnc::kBlock);
-  if (blocks > cap) blocks = cap;
+  const int64_t blocks = gnc::capped_blocks(num_rows * d, gnc::kBlock, 16);
   segment_reduce_backward_scalar<MODE><<<dim3((unsigned)blocks), dim3(gnc::kBlock), 0, stream>>>(
       grad_out, ld_grad, dst_of_row, rowptr, argmax, num_rows, d, grad_src, ld_src);
   return gnc::check_launch("segment_reduce_backward_scalar");
@@ -433,9 +425,7 @@ extern "C" int gnc_rows_div_degree_f32(float* table, int64_t ld, const int32_t* 
   GNC_REQUIRE(ld >= feat_dim, "gnc_rows_div_degree_f32: leading dimension < feat_dim");
   GNC_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3u) == 0, "gnc_rows_div_degree_f32: table is not aligned to its element size");
   const bool vec = feat_dim % 4 == 0 && ld % 4 == 0 && gnc::aligned16(table);
-  int64_t blocks = gnc::ceil_div(num_nodes * (feat_dim / (vec ? 4 : 1)), gnc::kBlock);
-  const int64_t cap = gnc::num_cu() * 16;
-  if (blocks > cap) blocks = cap;
+  const int64_t blocks = gnc::capped_blocks(num_nodes * (feat_dim / (vec ? 4 : 1)), gnc::kBlock, 16);
   const dim3 grid((unsigned)blocks), block(gnc::kBlock);
   hipStream_t stream = (hipStream_t)stream_;
   if (vec) rows_div_degree_kernel<4><<<grid, block, 0, stream>>>(table, ld, rowptr, num_nodes, feat_dim);

@@ -16,8 +16,9 @@
 //            topk_tile_scan_kernel   one workgroup: exclusive scan of the tile counts in place, E' = counts[1]
 //            topk_edge_write_kernel  the tile again: src', dst', kept_edges, edge_new_id and the exclusive count at every position
 //            topk_rowptr_kernel      thread per kept node: rowptr'[v'] = exclusive count at rowptr[v]; rowptr'[N'] = E'
-//   rows     topk_rows_forward_kernel / topk_rows_backward_kernel: one streaming pass each, 16-byte accesses at C % 4 == 0
-#include "gnc_common.h"
+//   rows     topk_rows_forward_kernel / topk_rows_backward_kernel: one streaming pass each, 16-byte accesses at C % 4 == 0; the row
+//            tiling is pool_index.h's (row_geometry, row_lane), load_vec / store_vec are graph_reduce.h's
+#include "graph_reduce.h"
 #include "topk_pool_index.h"
 
 #include <math.h>
@@ -26,6 +27,10 @@ namespace {
 
 using namespace gnc_topk;
 using gnc_pool::graph_range;
+using gnc_pool::row_lane;
+using gnc_reduce::load_vec;
+using gnc_reduce::store_vec;
+using gnc::aligned_to;
 
 // Exclusive scan of `v` over the kT threads of the workgroup (thread order) and its total.  Every thread calls it (it synchronises).
 __device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t (&s_wave)[kWaves], uint32_t& total) {
@@ -246,36 +251,12 @@ struct RowsArgs {
   int32_t lanes, vec16;  // vec16: every row of every table starts on a 16-byte boundary
 };
 
-template <int VEC>
-__device__ __forceinline__ void load_vec(const float* __restrict__ p, bool p16, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    if (p16) {
-      const float4 q = *reinterpret_cast<const float4*>(p);
-      v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-      return;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < VEC; ++u) v[u] = p[u];
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_vec(float* __restrict__ p, bool p16, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    if (p16) {
-      *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-      return;
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < VEC; ++u) p[u] = v[u];
-}
-
 // out[i, :] = x[index[i], :] * tanh(scores[index[i]]) (no gate: the bits of x); `lanes` threads per row
 template <int VEC>
 __global__ __launch_bounds__(kT) void topk_rows_forward_kernel(const RowsArgs a) {
   const int W = a.lanes, rpb = kT / W;
-  const int lane = threadIdx.x % W, sub = threadIdx.x / W;
+  const gnc_pool::RowLane x = row_lane(threadIdx.x, W);
+  const int lane = x.lane, sub = x.sub;
   const int64_t per_row = a.C / VEC;
   const bool v16 = a.vec16 != 0;
   for (int64_t i = (int64_t)blockIdx.x * rpb + sub; i < a.n_out; i += (int64_t)gridDim.x * rpb) {
@@ -302,7 +283,8 @@ __global__ __launch_bounds__(kT) void topk_rows_forward_kernel(const RowsArgs a)
 template <int VEC>
 __global__ __launch_bounds__(kT) void topk_rows_backward_kernel(const RowsArgs a) {
   const int W = a.lanes, rpb = kT / W;
-  const int lane = threadIdx.x % W, sub = threadIdx.x / W;
+  const gnc_pool::RowLane x = row_lane(threadIdx.x, W);
+  const int lane = x.lane, sub = x.sub;
   const int64_t per_row = a.C / VEC;
   const bool v16 = a.vec16 != 0;
   for (int64_t base = (int64_t)blockIdx.x * rpb; base < a.rows_in; base += (int64_t)gridDim.x * rpb) {  // uniform
@@ -338,14 +320,6 @@ __global__ __launch_bounds__(kT) void topk_rows_backward_kernel(const RowsArgs a
       if (valid && lane == 0) a.ds[r] = keptrow ? (1.f - gate * gate) * dot : 0.f;
     }
   }
-}
-
-bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
-int64_t capped_blocks(int64_t work, int64_t per_block) {
-  int64_t blocks = gnc::ceil_div(work, per_block);
-  const int64_t cap = 8ll * gnc::num_cu();
-  return blocks > cap ? cap : (blocks < 1 ? 1 : blocks);
 }
 
 constexpr int64_t kMaxRows = (1ll << 31) - 1;
@@ -410,7 +384,7 @@ extern "C" int gnc_topk_pool_filter_edges(const int32_t* src_sorted, const int32
     topk_edge_write_kernel<<<dim3((unsigned)tiles), dim3(kT), 0, st>>>(a);
     if (int rc = gnc::check_launch("topk_edge_write_kernel")) return rc;
   }
-  topk_rowptr_kernel<<<dim3((unsigned)capped_blocks(rows + 1, kT)), dim3(kT), 0, st>>>(rowptr, kept, a.excl, counts, num_edges, rows,
+  topk_rowptr_kernel<<<dim3((unsigned)gnc::capped_blocks(rows + 1, kT)), dim3(kT), 0, st>>>(rowptr, kept, a.excl, counts, num_edges, rows,
                                                                                      rowptr_out);
   return gnc::check_launch("topk_rowptr_kernel");
 }
@@ -449,7 +423,7 @@ extern "C" int gnc_topk_pool_rows_forward_f32(const float* x, int64_t ld_x, int6
     return rc;
   GNC_REQUIRE((x && kept && out) || n_out == 0, "gnc_topk_pool_rows_forward_f32: null x / kept / out");
   if (n_out == 0) return GNC_OK;
-  const dim3 grid((unsigned)capped_blocks(n_out, kT / a.lanes)), block(kT);
+  const dim3 grid((unsigned)gnc::capped_blocks(n_out, kT / a.lanes)), block(kT);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (vec == 4) topk_rows_forward_kernel<4><<<grid, block, 0, st>>>(a);
   else topk_rows_forward_kernel<1><<<grid, block, 0, st>>>(a);
@@ -469,7 +443,7 @@ extern "C" int gnc_topk_pool_rows_backward_f32(const float* dout, int64_t ld_dou
   GNC_REQUIRE((new_id && (!ds || x)) || rows_in == 0, "gnc_topk_pool_rows_backward_f32: null new_id / x");
   GNC_REQUIRE(dout || n_out == 0, "gnc_topk_pool_rows_backward_f32: null dout");
   if (rows_in == 0) return GNC_OK;
-  const dim3 grid((unsigned)capped_blocks(rows_in, kT / a.lanes)), block(kT);
+  const dim3 grid((unsigned)gnc::capped_blocks(rows_in, kT / a.lanes)), block(kT);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (vec == 4) topk_rows_backward_kernel<4><<<grid, block, 0, st>>>(a);
   else topk_rows_backward_kernel<1><<<grid, block, 0, st>>>(a);

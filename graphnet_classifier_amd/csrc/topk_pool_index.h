@@ -1,5 +1,5 @@
 // Index arithmetic of K20 (csrc/topk_pool.hip): the order-preserving key of a score, the number of rows a graph keeps, the rows a
-// select workgroup marks as dropped around its graph, the edge-scan tiling and the row tiling of the compaction launches.
+// select workgroup marks as dropped around its graph, the edge-scan tiling (the row tiling of the compaction launches is pool_index.h's).
 // Host-compilable like pool_index.h, so that tools/topk_pool_index_check.cpp can walk every (workgroup, thread) of the launches
 // and check each address before a kernel runs on a device.  Nothing here touches memory except `graph_ptr`.
 #pragma once
@@ -51,22 +51,8 @@ GNC_POOL_HD int64_t edge_position(int64_t tile, int step, int t) { return tile *
 // count of kept edges at EVERY sorted position behind.
 GNC_POOL_HD int64_t edge_workspace_ints(int64_t E) { return edge_tiles(E) + E; }
 
-// Row compaction: `lanes` threads side by side own ONE row (a power of two <= 64: a row never straddles a wavefront), `vec`
-// consecutive columns at a time (4 when C is a multiple of 4); lane l takes the column groups l, l + lanes, ... and the backward's
-// dot over C is folded by a butterfly.  A function of C ALONE: it fixes the order of that dot.
-struct RowGeometry {
-  int vec, lanes, rows_per_block;
-};
-
-GNC_POOL_HD RowGeometry row_geometry(int64_t C) {
-  RowGeometry g;
-  g.vec = (C % 4 == 0) ? 4 : 1;
-  const int64_t per_row = C / g.vec;
-  int lanes = 1;
-  while (lanes < 64 && lanes < per_row) lanes <<= 1;
-  g.lanes = lanes;
-  g.rows_per_block = kT / lanes;
-  return g;
-}
+// (the row tiling of the compaction launches is pool_index.h's row_geometry / row_lane)
+using gnc_pool::RowGeometry;
+using gnc_pool::row_geometry;
 
 }  // namespace gnc_topk

@@ -1,34 +1,21 @@
 // Host walk of K20's index arithmetic (graphnet_classifier_amd/csrc/topk_pool_index.h over csrc/pool_index.h).  For batches with
 // empty graphs, rows in front of and behind the graphs and the awkward sizes around the 256-thread chunk and the 1024-edge tile,
-// every (workgroup, thread) of the select, edge-scan and row-compaction launches is enumerated as csrc/topk_pool.hip enumerates
-// them: every address is checked against its buffer, every input must be read and every output written exactly once, and the
+// every (workgroup, thread) of the select, edge-scan and row-compaction launches is enumerated (the row launches through
+// tools/pool_walk.h and the functions the kernels call): every address is checked against its buffer, every input must be read and every output written exactly once, and the
 // select walk - the radix passes over score_key and the admission of ties in row order - must give the kept set of a plain
 // stable sort.  The key map is checked on its own (monotone, -0.0 == +0.0, NaN lowest).  Exit status 0 = every check held.
-//   c++ -std=c++17 -O1 -fsanitize=address,undefined -I graphnet_classifier_amd/csrc tools/topk_pool_index_check.cpp \
+//   c++ -std=c++17 -O1 -fsanitize=address,undefined -I graphnet_classifier_amd/csrc -I tools tools/topk_pool_index_check.cpp \
 //       -o topk_pool_index_check && ./topk_pool_index_check
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <vector>
 
+#include "pool_walk.h"
 #include "topk_pool_index.h"
 
 using namespace gnc_topk;
-
-static int failures = 0;
-#define CHECK(cond, ...)                       \
-  do {                                         \
-    if (!(cond)) {                             \
-      if (++failures <= 20) {                  \
-        std::printf("FAILED %s: ", #cond);     \
-        std::printf(__VA_ARGS__);              \
-        std::printf("\n");                     \
-      }                                        \
-    }                                          \
-  } while (0)
 
 static uint32_t bits_of(float f) {
   uint32_t u;
@@ -178,23 +165,15 @@ static void walk_edges(int64_t E) {
 
 // ------------------------------------------------------------------------------------------------------------- row tiles
 static void walk_rows(int64_t n_rows, int64_t C, int64_t ld, int64_t blocks) {
-  const RowGeometry geo = row_geometry(C);
-  CHECK(geo.lanes >= 1 && geo.lanes <= 64 && kT % geo.lanes == 0 && (geo.vec == 1 || C % 4 == 0), "geometry of C = %lld", (long long)C);
   std::vector<int> writes(n_rows * ld + 1, 0);
-  const int W = geo.lanes, rpb = kT / W;
-  const int64_t per_row = C / geo.vec;
-  for (int64_t blk = 0; blk < blocks; ++blk)
-    for (int t = 0; t < kT; ++t) {
-      const int lane = t % W, sub = t / W;
-      for (int64_t i = blk * rpb + sub; i < n_rows; i += blocks * rpb)
-        for (int64_t q = lane; q < per_row; q += W)
-          for (int u = 0; u < geo.vec; ++u) {
-            const int64_t o = i * ld + q * geo.vec + u;
-            CHECK(q * geo.vec + u < C && o < n_rows * ld, "element %lld of a [%lld, %lld] table", (long long)o, (long long)n_rows, (long long)ld);
-            if (o < n_rows * ld) ++writes[o];
-          }
-      CHECK((t ^ (W >> 1)) / W == sub || W == 1, "butterfly partner of thread %d leaves its row", t);
-    }
+  pool_walk::walk_row_tiles(
+      row_geometry(C), n_rows, C, blocks,
+      [&](int64_t i, int64_t c) {
+        const int64_t o = i * ld + c;
+        CHECK(c < C && o < n_rows * ld, "element %lld of a [%lld, %lld] table", (long long)o, (long long)n_rows, (long long)ld);
+        if (o < n_rows * ld) ++writes[o];
+      },
+      [](int64_t) {});
   for (int64_t i = 0; i < n_rows; ++i)
     for (int64_t c = 0; c < ld; ++c)
       CHECK(writes[i * ld + c] == (c < C ? 1 : 0), "[%lld, %lld] of C = %lld touched %d times", (long long)i, (long long)c, (long long)C, writes[i * ld + c]);
@@ -235,10 +214,5 @@ int main() {
     for (int64_t n_rows : {1, 37, 300})
       for (int64_t blocks : {1, 7}) walk_rows(n_rows, C, C + (C % 4 == 0 ? 4 : 3), blocks);
 
-  if (failures) {
-    std::printf("topk_pool_index_check: %d FAILED\n", failures);
-    return 1;
-  }
-  std::printf("topk_pool_index_check: ok\n");
-  return 0;
+  return pool_walk::finish("topk_pool_index_check");
 }
