@@ -97,7 +97,20 @@ def scatter_max(src: Tensor, index: Tensor, dim: int = 0, dim_size: int | None =
     return (out, argmax) if out_device == dev else (out.to(out_device), argmax.to(out_device))
 
 
-AGGREGATIONS = ("sum", "mean", "max")
+def scatter_attention(src: Tensor, scores: Tensor, index: Tensor, dim: int = 0, dim_size: int | None = None) -> Tensor:
+    """``scatter_mean``'s learned sibling (same argument handling and errors): out[v] = sum of alpha_r src[r] over the rows with
+    ``index == v``, ``alpha`` the softmax of their ``scores`` (one float per row of ``src``) - in row order, +0.0 for a ``v`` without
+    rows; equal scores give ``scatter_mean``'s bits (K21)."""
+    src, csr, dim_size, out_device, dev = _scatter_args("scatter_attention", src, index, dim, dim_size)
+    if scores.numel() != src.size(0):
+        raise ValueError(f"scatter_attention: {scores.numel()} scores for {src.size(0)} rows of src")
+    scores = scores.reshape(-1).to(device=dev, dtype=torch.float32)
+    need = src.requires_grad or scores.requires_grad
+    out = Fn.segment_softmax_csr(src, scores, csr.rowptr, csr.perm, csr.col32 if need else None, dim_size)
+    return out if out_device == dev else out.to(out_device)
+
+
+AGGREGATIONS = ("sum", "mean", "max", "attention")
 
 
 def _check_aggregation(aggregation, who: str) -> str:
@@ -168,14 +181,23 @@ class EdgeProcessor(nn.Module):
 class NodeProcessor(nn.Module):
     def __init__(self, in_dim_node: int, in_dim_edge: int, hidden_dim: int = 128, hidden_layers: int = 2,
                  activation: str = "ReLU", initializer: None | str = None, norm_type: None | str = "LayerNorm",
-                 aggregation: str = "sum"):
+                 aggregation: str = "sum", attention_hidden: int | None = None):
         """models/GNN.py:69-93.  ``aggregation``: how the incoming edge latents of a node are reduced - ``"sum"`` (the reference's
-        code), ``"mean"`` (the reference's write-up) or ``"max"`` (K18).  A plain attribute: no parameter, no buffer, not in the
-        ``state_dict``."""
+        code), ``"mean"`` (the reference's write-up), ``"max"`` (K18) or ``"attention"`` (K21).  For the first three a plain
+        attribute: no parameter, no buffer, not in the ``state_dict``.  ``"attention"`` adds ``self.gate``, the score of an edge
+        latent: ``W2 relu(W1 e' + b1) + b2`` with ``attention_hidden`` (32) hidden units - ``TopKPool.gate``'s shape, on the
+        fused-MLP kernels over the E rows; a node's incoming latents are summed with the softmax of their scores."""
         super().__init__()
         self.aggregation = _check_aggregation(aggregation, "NodeProcessor")
+        if aggregation != "attention" and attention_hidden is not None:
+            raise ValueError(f"NodeProcessor: attention_hidden belongs to aggregation='attention', not {aggregation!r}")
         self.node_processor = MLP(in_dim_node + in_dim_edge, in_dim_node, hidden_dim, hidden_layers, activation,
                                   initializer, norm_type)
+        if aggregation == "attention":  # behind node_processor: it draws the random numbers it draws without the gate
+            attention_hidden = 32 if attention_hidden is None else int(attention_hidden)
+            if attention_hidden < 1:
+                raise ValueError(f"NodeProcessor: attention_hidden {attention_hidden} must be positive")
+            self.gate = MLP(in_dim_edge, 1, hidden_dim=attention_hidden, hidden_layers=1, activation="ReLU", norm_type=None)
 
     def forward(self, x: Tensor, edge_index: Tensor, edge_attr: Tensor, u=None, batch=None):
         """MetaLayer node-model contract (models/GNN.py:95-104): MLP(cat[x, scatter_sum(e, col)]) + x."""
@@ -192,11 +214,18 @@ class NodeProcessor(nn.Module):
         launch's epilogue has formed them already (sum and mean; the max has no use for them)."""
         if self.aggregation == "max":  # the winners' rows are kept only under autograd
             return Fn.segment_max_csr(edge_attr, topo.rowptr, perm, dst_of_row, topo.num_nodes)
+        if self.aggregation == "attention":  # one score per edge latent from the gate, then K21
+            scores = self.edge_scores(edge_attr)
+            return Fn.segment_softmax_csr(edge_attr, scores, topo.rowptr, perm, dst_of_row, topo.num_nodes)
         if sums is None:
             sums = Fn.scatter_sum_csr(edge_attr, topo.rowptr, perm, dst_of_row, topo.num_nodes)
         if self.aggregation == "mean":  # the sum machinery unchanged, then one launch over N rows: segment_mean_csr's bits
             return Fn.div_by_degree(sums, topo.rowptr, inplace=True)
         return sums
+
+    def edge_scores(self, edge_attr: Tensor) -> Tensor:
+        """[E] attention scores of the (updated) edge latents, in their row order (``aggregation="attention"`` only)."""
+        return self.gate.forward_segments([(edge_attr, None)]).view(-1)
 
     def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor, agg: Tensor | None = None) -> Tensor:
         """``agg`` given: the per-destination sums already formed by the edge launch's epilogue."""
@@ -238,10 +267,11 @@ class MetaLayer(nn.Module):
         if self.edge_model is not None:
             # let the edge launch form the node model's aggregate in its epilogue; with autograd on the
             # W-split Function returns both outputs and folds the aggregate's gradient (a gather) into e''s
-            # (a max aggregation has no epilogue inside the MFMA kernels: the edge launch stores e' and K18 reduces it)
+            # (a max or attention aggregation has no epilogue inside the MFMA kernels: the edge launch stores e' - also in the
+            # last block in inference - and K18 / K21 reduces it)
             if (FUSED_AGG and self.node_model is not None
                     and isinstance(self.edge_model, EdgeProcessor) and isinstance(self.node_model, NodeProcessor)
-                    and self.node_model.aggregation != "max"):
+                    and self.node_model.aggregation not in ("max", "attention")):
                 edge_attr, agg = self.edge_model.forward_sorted(x, topo, edge_attr, aggregate=True, need_edges=need_edges)
             else:
                 edge_attr = self.edge_model.forward_sorted(x, topo, edge_attr)
@@ -255,14 +285,15 @@ class MetaLayer(nn.Module):
 
 def build_GN_block(in_dim_node: int, in_dim_edge: int, hidden_dim_node: int = 128, hidden_dim_edge: int = 128,
                    hidden_layers_node: int = 2, hidden_layers_edge: int = 2, activation: str = "ReLU",
-                   initializer: None | str = None, norm_type: None | str = "LayerNorm", aggregation: str = "sum"):
-    """models/GNN.py:110-165; ``aggregation`` goes to the block's ``NodeProcessor``."""
+                   initializer: None | str = None, norm_type: None | str = "LayerNorm", aggregation: str = "sum",
+                   attention_hidden: int | None = None):
+    """models/GNN.py:110-165; ``aggregation`` and ``attention_hidden`` go to the block's ``NodeProcessor``."""
     _check_aggregation(aggregation, "build_GN_block")
     return MetaLayer(
         edge_model=EdgeProcessor(in_dim_node, in_dim_edge, hidden_dim_edge, hidden_layers_edge, activation,
                                  initializer, norm_type),
         node_model=NodeProcessor(in_dim_node, in_dim_edge, hidden_dim_node, hidden_layers_node, activation,
-                                 initializer, norm_type, aggregation=aggregation),
+                                 initializer, norm_type, aggregation=aggregation, attention_hidden=attention_hidden),
     )
 
 
@@ -270,15 +301,17 @@ def build_GN_block(in_dim_node: int, in_dim_edge: int, hidden_dim_node: int = 12
 class GraphProcessor(nn.Module):
     def __init__(self, n_iterations: int, in_dim_node: int, in_dim_edge: int, hidden_dim_node: int = 128,
                  hidden_dim_edge: int = 128, hidden_layers_node: int = 2, hidden_layers_edge: int = 2,
-                 activation: str = "ReLU", initializer: None | str = None, norm_type="LayerNorm", aggregation: str = "sum"):
-        """n_iterations GN blocks with unshared weights (models/GNN.py:168-211); ``aggregation`` is every block's."""
+                 activation: str = "ReLU", initializer: None | str = None, norm_type="LayerNorm", aggregation: str = "sum",
+                 attention_hidden: int | None = None):
+        """n_iterations GN blocks with unshared weights (models/GNN.py:168-211); ``aggregation`` (and ``attention_hidden``) is every
+        block's."""
         super().__init__()
         self.aggregation = _check_aggregation(aggregation, "GraphProcessor")
         self.blocks = nn.ModuleList()
         for _ in range(n_iterations):
             self.blocks.append(build_GN_block(in_dim_node, in_dim_edge, hidden_dim_node, hidden_dim_edge,
                                               hidden_layers_node, hidden_layers_edge, activation, initializer,
-                                              norm_type, aggregation=aggregation))
+                                              norm_type, aggregation=aggregation, attention_hidden=attention_hidden))
 
     def forward(self, x, edge_index, edge_attr):
         """models/GNN.py:213-216; ``edge_attr`` in and out in the caller's edge order."""
@@ -382,8 +415,10 @@ class GraphNet(nn.Module):
         norm_type = kwargs.get("norm_type", "LayerNorm")
         activation = kwargs.get("activation", "ReLU")
         initializer = kwargs.get("initializer", None)
-        # "sum" (the reference's code), "mean" (its write-up) or "max"; any other value is an error, never a silent sum
+        # "sum" (the reference's code), "mean" (its write-up), "max" or "attention" (K21: a gate MLP per block scores the edge
+        # latents); any other value is an error, never a silent sum
         aggregation = _check_aggregation(kwargs.get("aggregation", "sum"), "GraphNet")
+        attention_hidden = kwargs.get("attention_hidden")  # with another mode the NodeProcessor raises
         # K20: top-K node pooling behind the GN blocks (the write-up's "Pooling(h(k))").  None: no pooling, no module, no keys.
         pool_ratio, pool_after, pool_hidden = kwargs.get("pool_ratio"), kwargs.get("pool_after"), kwargs.get("pool_hidden")
         if pool_ratio is None:
@@ -412,7 +447,8 @@ class GraphNet(nn.Module):
         self.graph_processor = GraphProcessor(n_blocks, out_dim_node, out_dim_edge, hidden_dim_processor_node,
                                               hidden_dim_processor_edge, hidden_layers_processor_node,
                                               hidden_layers_processor_edge, activation=activation,
-                                              initializer=initializer, norm_type=norm_type, aggregation=aggregation)
+                                              initializer=initializer, norm_type=norm_type, aggregation=aggregation,
+                                              attention_hidden=attention_hidden)
         self.node_decoder = MLP(out_dim_node, out_dim, hidden_dim_decoder, hidden_layers_decoder, norm_type=None)
         # the pools LAST: every other parameter draws the random numbers it draws without them (graph_processor.pools.<i>.gate.*)
         self.pool_ratio, self.pool_after = pool_ratio, tuple(pool_after) if pool_ratio is not None else ()
@@ -454,6 +490,36 @@ class GraphNet(nn.Module):
         # validation not read back yet: a bad edge_index must not yield a plausible result (the ORIGINAL topology's flags)
         out = _poison_if_deferred(topo, out)
         return (out, graph_ptr, kept) if return_pooling else out
+
+    @torch.no_grad()
+    def edge_attention_weights(self, x: Tensor, pos: Tensor, edge_index: Tensor) -> list[Tensor]:
+        """``aggregation="attention"``: one ``alpha`` [E] per GN block, in the caller's edge order - the weight each edge's latent
+        has in its destination's aggregate; it sums to 1 over the incoming edges of every node that has any."""
+        if self.aggregation != "attention":
+            raise ValueError(f"GraphNet.edge_attention_weights: aggregation is {self.aggregation!r}, not 'attention'")
+        if self.pooling:
+            raise ValueError("GraphNet.edge_attention_weights: top-K pooling changes the edge set between the blocks")
+        dev = require_gpu_param(self.node_encoder.model[0].weight, "GraphNet")
+        back = x.device
+        x = x.to(device=dev, dtype=torch.float32)
+        pos = pos.to(device=dev, dtype=torch.float32)
+        topo = get_topology(edge_index, x.size(0), dev)
+        h = self.node_encoder.forward_segments([(x.view(x.size(0), -1), None)])
+        e = Fn.edge_features(pos, topo.src_sorted, topo.dst_sorted)
+        e = self.edge_encoder.forward_segments([(e, None)])
+        weights = []
+        for block in self.graph_processor.blocks:
+            e = block.edge_model.forward_sorted(h, topo, e)
+            node = block.node_model
+            scores = node.edge_scores(e)
+            agg, saved = native.segment_softmax_csr(e, scores, topo.rowptr, None, topo.num_nodes)
+            alpha = native.segment_softmax_weights(scores, saved, topo.dst_sorted)
+            alpha = alpha[topo.inv_perm.long()]  # sorted position -> the caller's edge order
+            if topo.deferred:  # flags not read back yet: a bad edge_index must not yield plausible weights
+                alpha = torch.where(topo.status.any(), torch.full_like(alpha, float("nan")), alpha)
+            weights.append(alpha)
+            h = node.node_processor.forward_segments([(h, None), (agg, None)], residual=h)
+        return [w if back == dev else w.to(back) for w in weights]
 
     def forward(self, x, pos, edge_index):
         dev = require_gpu_param(self.node_encoder.model[0].weight, "GraphNet")

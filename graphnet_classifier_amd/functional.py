@@ -107,6 +107,33 @@ def segment_max_csr(src: torch.Tensor, rowptr: torch.Tensor, perm, dst_of_row: t
     return (out, argmax) if return_argmax else out
 
 
+class _SegmentSoftmaxCSR(torch.autograd.Function):
+    """K21 (csrc/segment_softmax.hip): keeps src, scores, out and the per-destination (max, sum of exp); no [E] weights."""
+
+    @staticmethod
+    def forward(ctx, src, scores, rowptr, perm, dst_of_row, num_nodes):
+        out, saved = native.segment_softmax_csr(src, scores, rowptr, perm, num_nodes)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(src, scores, out, saved, dst_of_row)
+        ctx.scores_shape = scores.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        src, scores, out, saved, dst_of_row = ctx.saved_tensors
+        grad_src, grad_scores = native.segment_softmax_backward(grad_out, src, scores, out, saved, dst_of_row)
+        return grad_src, grad_scores.view(ctx.scores_shape), None, None, None, None
+
+
+def segment_softmax_csr(src: torch.Tensor, scores: torch.Tensor, rowptr: torch.Tensor, perm, dst_of_row: torch.Tensor, num_nodes: int):
+    """out[v] = sum_k alpha_k src[k] over the rows whose destination is v, ``alpha`` the softmax of their ``scores`` (+0.0 for no
+    rows; equal scores give the bits of ``segment_mean_csr``).  ``scores``: one float per row of ``src`` ([E] or [E, 1]), indexed as
+    ``src`` is.  Other arguments as ``scatter_sum_csr``; ``dst_of_row`` may be None when no gradient is wanted."""
+    if dst_of_row is None and (src.requires_grad or scores.requires_grad) and torch.is_grad_enabled():
+        raise ValueError("segment_softmax_csr: dst_of_row is needed for the backward")
+    return _SegmentSoftmaxCSR.apply(src, scores, rowptr, perm, dst_of_row, num_nodes)
+
+
 class _DivByDegree(torch.autograd.Function):
     """Rows of an [N, D] aggregate divided by the in-degree (gnc_rows_div_degree_f32); linear, so the same launch on the gradient."""
 

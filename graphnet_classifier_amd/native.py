@@ -161,6 +161,11 @@ _SIGNATURES = {
     "gnc_segment_reduce_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32,
                                                   c_void_p, c_int64, c_void_p]),
     "gnc_rows_div_degree_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p]),
+    "gnc_segment_softmax_csr_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64,
+                                              c_void_p, c_void_p]),
+    "gnc_segment_softmax_backward_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                                   c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "gnc_segment_softmax_weights_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "gnc_adam_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float,
                                     c_void_p, c_void_p, c_void_p]),
     "gnc_adam_step_hp64_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_float, c_float,
@@ -566,6 +571,86 @@ def rows_div_degree_(table: torch.Tensor, rowptr: torch.Tensor) -> torch.Tensor:
                        lambda: lib.gnc_rows_div_degree_f32(table.data_ptr(), _ld(table), rowptr.data_ptr(), n, d, _stream(table)),
                        8.0 * d * n + 4.0 * (n + 1)), "gnc_rows_div_degree_f32")
     return table
+
+
+# --------------------------------------------------------------------------- K21: attention aggregation
+def _scores_of(scores: torch.Tensor, rows: int, who: str) -> torch.Tensor:
+    if scores.dtype != torch.float32 or scores.numel() != rows:
+        raise ValueError(f"{who}: float32 scores with one entry per row of src ({rows}) expected, got {scores.dtype} "
+                         f"{tuple(scores.shape)}")
+    return scores.reshape(-1).contiguous()
+
+
+def segment_softmax_csr(src: torch.Tensor, scores: torch.Tensor, rowptr: torch.Tensor, perm: torch.Tensor | None, num_nodes: int):
+    """K21 forward (csrc/segment_softmax.hip): ``(out [num_nodes, D], saved [num_nodes, 2])`` - per destination the softmax of the
+    ``scores`` of its rows weighting the sum of those rows of ``src``; ``saved[v] = (max score, sum of exp)`` is what the backward and
+    ``segment_softmax_weights`` rebuild the weights from.  ``perm`` (sorted position -> row) indexes ``src`` and ``scores`` alike."""
+    lib = load_library()
+    _require_cuda(src, scores, rowptr, perm)
+    if rowptr.dtype != torch.int32 or (perm is not None and perm.dtype != torch.int32):
+        raise TypeError("segment_softmax_csr expects int32 rowptr / perm")
+    if rowptr.numel() != num_nodes + 1:
+        raise ValueError(f"segment_softmax_csr: rowptr has {rowptr.numel()} entries for {num_nodes} nodes")
+    src = _rowmajor(src)
+    e, d = src.shape
+    scores = _scores_of(scores, e, "segment_softmax_csr")
+    out = torch.empty(num_nodes, d, dtype=torch.float32, device=src.device)
+    saved = torch.empty(num_nodes, 2, dtype=torch.float32, device=src.device)
+    # algorithmic bytes (DESIGN.md, K21): K18's, plus the scores twice and (m, Z) per destination
+    work = (4.0 * d * e + 8.0 * e + 4.0 * d * num_nodes + 8.0 * num_nodes + 4.0 * (num_nodes + 1)
+            + (4.0 * e if perm is not None else 0.0))
+    with torch.cuda.device(src.device):
+        _check(_launch("segment_softmax_csr", src,
+                       lambda: lib.gnc_segment_softmax_csr_f32(src.data_ptr(), _ld(src), scores.data_ptr(), rowptr.data_ptr(),
+                                                               perm.data_ptr() if perm is not None else None, num_nodes, e, d,
+                                                               out.data_ptr(), _ld(out), saved.data_ptr(), _stream(src)), work),
+               "gnc_segment_softmax_csr_f32")
+    return out, saved
+
+
+def segment_softmax_backward(grad_out: torch.Tensor, src: torch.Tensor, scores: torch.Tensor, out: torch.Tensor, saved: torch.Tensor,
+                             dst_of_row: torch.Tensor):
+    """``(grad_src [E, D], grad_scores [E])`` of ``segment_softmax_csr`` in one pass over its rows; ``dst_of_row`` int32 [E] is the
+    destination of each row of the forward's ``src``."""
+    lib = load_library()
+    _require_cuda(grad_out, src, scores, out, saved, dst_of_row)
+    grad_out, src, out = _rowmajor(grad_out), _rowmajor(src), _rowmajor(out)
+    n, d = out.shape
+    e = src.size(0)
+    if dst_of_row.dtype != torch.int32 or dst_of_row.numel() != e:
+        raise TypeError(f"segment_softmax_backward expects an int32 dst_of_row with {e} entries")
+    if tuple(grad_out.shape) != (n, d) or src.size(1) != d:
+        raise ValueError(f"segment_softmax_backward: grad_out {tuple(grad_out.shape)}, src {tuple(src.shape)}, out {(n, d)} disagree")
+    if saved.dtype != torch.float32 or tuple(saved.shape) != (n, 2) or not saved.is_contiguous():
+        raise ValueError("segment_softmax_backward: the forward's contiguous float32 saved [N, 2] expected")
+    scores = _scores_of(scores, e, "segment_softmax_backward")
+    grad_src = torch.empty(e, d, dtype=torch.float32, device=src.device)
+    grad_scores = torch.empty(e, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _check(_launch("segment_softmax_backward", src,
+                       lambda: lib.gnc_segment_softmax_backward_f32(grad_out.data_ptr(), _ld(grad_out), src.data_ptr(), _ld(src),
+                                                                    scores.data_ptr(), out.data_ptr(), _ld(out), saved.data_ptr(),
+                                                                    dst_of_row.data_ptr(), n, e, d, grad_src.data_ptr(),
+                                                                    _ld(grad_src), grad_scores.data_ptr(), _stream(src)),
+                       8.0 * d * e + 12.0 * e + 8.0 * d * n + 8.0 * n), "gnc_segment_softmax_backward_f32")
+    return grad_src, grad_scores
+
+
+def segment_softmax_weights(scores: torch.Tensor, saved: torch.Tensor, dst_of_row: torch.Tensor) -> torch.Tensor:
+    """``alpha`` [E]: the softmax weight of every row, rebuilt from the forward's ``saved``."""
+    lib = load_library()
+    _require_cuda(scores, saved, dst_of_row)
+    e = dst_of_row.numel()
+    if dst_of_row.dtype != torch.int32:
+        raise TypeError("segment_softmax_weights expects an int32 dst_of_row")
+    if saved.dtype != torch.float32 or saved.dim() != 2 or saved.size(1) != 2 or not saved.is_contiguous():
+        raise ValueError("segment_softmax_weights: the forward's contiguous float32 saved [N, 2] expected")
+    scores = _scores_of(scores, e, "segment_softmax_weights")
+    alpha = torch.empty(e, dtype=torch.float32, device=scores.device)
+    with torch.cuda.device(scores.device):
+        _check(lib.gnc_segment_softmax_weights_f32(scores.data_ptr(), saved.data_ptr(), dst_of_row.data_ptr(), e, alpha.data_ptr(),
+                                                   _stream(scores)), "gnc_segment_softmax_weights_f32")
+    return alpha
 
 
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:

@@ -729,6 +729,31 @@ int gnc_segment_reduce_backward_f32(const float* grad_out, int64_t ld_grad, cons
                                     float* grad_src, int64_t ld_src, void* stream);
 int gnc_rows_div_degree_f32(float* table, int64_t ld, const int32_t* rowptr, int64_t num_nodes, int32_t feat_dim, void* stream);
 
+/* ---- K21: attention neighbourhood aggregation (csrc/segment_softmax.hip) --------------
+ * A softmax-weighted sum of every destination's incoming rows over K18's destination-sorted CSR, with K18's argument conventions:
+ * row(k) = perm[k], or k itself when `perm` is NULL, indexes BOTH `src` [num_edges, ld_src] and `scores` [num_edges].
+ *   m_v = max_k s_k (fmaxf from -inf: a NaN does not enter it);  e_k = expf(s_k - m_v);  Z_v = sum_k e_k;
+ *   out[v, c] = (sum_k e_k x_k[c]) / Z_v, each product entering by one fmaf, both sums from +0.0 in ascending k, a true fp32
+ *   division;  saved[v] = (m_v, Z_v), float [num_nodes, 2] contiguous.  A destination without rows gives +0.0 and saved (0, 0).
+ * With all scores of a destination equal the output row has the bits of GNC_SEGMENT_MEAN.  A NaN score makes its own destination's
+ * row (and Z) NaN and touches no other; a -inf score among finite ones adds nothing.  No atomics; two runs, a graph alone or
+ * inside a block-diagonal batch, and sorted rows or rows behind `perm` give the same bits.
+ * Backward, one pass over the num_rows rows (row r of grad_src and entry r of grad_scores belong to row r of the forward's src and
+ * scores; dst_of_row[r] = d is its destination), alpha_r = expf(s_r - m_d) / Z_d recomputed from `saved`:
+ *   grad_src[r, :] = alpha_r grad_out[d, :];   grad_scores[r] = alpha_r sum_c grad_out[d, c] (src[r, c] - out[d, c]).
+ * gnc_segment_softmax_weights_f32 writes alpha [num_rows] alone.
+ * All three: int status, no allocation, no synchronisation, no host read-back, kernel nodes under stream capture.  Added without an
+ * ABI bump: a library without these symbols fails the symbol lookup of the binding. */
+int gnc_segment_softmax_csr_f32(const float* src, int64_t ld_src, const float* scores, const int32_t* rowptr, const int32_t* perm,
+                                int64_t num_nodes, int64_t num_edges, int32_t feat_dim, float* out, int64_t ld_out, float* saved,
+                                void* stream);
+int gnc_segment_softmax_backward_f32(const float* grad_out, int64_t ld_grad, const float* src, int64_t ld_src, const float* scores,
+                                     const float* out, int64_t ld_out, const float* saved, const int32_t* dst_of_row,
+                                     int64_t num_nodes, int64_t num_rows, int32_t feat_dim, float* grad_src, int64_t ld_gsrc,
+                                     float* grad_scores, void* stream);
+int gnc_segment_softmax_weights_f32(const float* scores, const float* saved, const int32_t* dst_of_row, int64_t num_rows, float* alpha,
+                                    void* stream);
+
 /* ---- graph construction on the device ---------------------------
  * Inputs: an already resized uint8 RGB image [H, W, C] in HBM.  Outputs: the tensors
  * utils/dataloader.py:49-51 builds (x, pos float32; edge_index int64 [2, E] row-major), in the
