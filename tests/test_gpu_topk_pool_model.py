@@ -77,13 +77,14 @@ def seed_condition_figures(seed=SEED):
     return out
 
 
-def _figures_of(sd, sd64, readout, aggregation, cases):
+def _figures_of(sd, sd64, readout, aggregation, cases, logits=K.pooled_logits):
+    """``logits``: the reference, with the arguments of ``K.pooled_logits`` (tests/option_crossing_cases.py passes its own)."""
     out = []
     for name, x, pos, ei, gp in cases:
         rec32, rec64 = [], []
-        K.pooled_logits(sd, x, pos, ei, RATIO, (0, 1), readout, gp, record=rec32)
-        pooled, _ = K.pooled_logits(sd64, x.double(), pos.double(), ei, RATIO, (0, 1), readout, gp, record=rec64)
-        plain, _ = K.pooled_logits(sd64, x.double(), pos.double(), ei, RATIO, (), readout, gp)
+        logits(sd, x, pos, ei, RATIO, (0, 1), readout, gp, record=rec32)
+        pooled, _ = logits(sd64, x.double(), pos.double(), ei, RATIO, (0, 1), readout, gp, record=rec64)
+        plain, _ = logits(sd64, x.double(), pos.double(), ei, RATIO, (), readout, gp)
         for layer, ((s32, _, keep32), (s64, ptr, keep64)) in enumerate(zip(rec32, rec64)):
             same = np.array_equal(keep32, keep64)
             err = float((s32.double() - s64).abs().max()) if same and s32.shape == s64.shape else float("inf")
