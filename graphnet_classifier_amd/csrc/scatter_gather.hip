@@ -2,124 +2,49 @@
 // All three are HBM-bandwidth-bound row movers; the design rules are: 16 B per lane, whole
 // rows per lane group, several independent loads in flight per lane, no atomics.
 //
-// K1 lane mapping (D = feature width):  LPR = D/4 lanes own one destination row (one float4
-// column slice each), so a 64-lane wave works on 64/LPR destinations at once (D=64: 16 lanes
-// per row, 4 rows per wave instruction = 1 KiB per load instruction).  A wave owns a chunk of
-// 64 consecutive destinations: its lanes fetch the 65 row pointers of the chunk with one
-// coalesced load and hand them to the lane groups by cross-lane reads, then each group walks
-// its segment in ascending sorted position k (= original edge order, the sort is stable) and
-// keeps the running sum in registers.  Every destination row is written exactly once.
+// K1's lane mapping, its regimes and the order in which a destination's rows are added are segment_csr.h's; what K1 adds to the
+// skeleton is the plain sum from +0.0.  K2 is the skeleton's row pass.
 #include <stdlib.h>
 
 #include "gnc_common.h"
+#include "segment_csr.h"
 
 namespace {
 
-using gnc::kWave;
+using namespace gnc_csr;
 
-struct alignas(16) f4 { float x, y, z, w; };
-
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-// Streamed-once rows (the messages of K1): nontemporal 16-B load, so the 2.5 GB stream does not push the
-// row pointers / output lines out of L2 and MALL.  Measured at c3 size: 0.592 -> 0.529 ms per launch.
-__device__ __forceinline__ f4 ld4_stream(const float* p) {
-  typedef float v4 __attribute__((ext_vector_type(4)));
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4*>(p));
-  return f4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
 __device__ __forceinline__ void acc4(f4& a, const f4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
 
-constexpr int kChunk = 64;  // destinations per wave iteration
+// rows [start, end) of one destination added from +0.0 in ascending k, columns [col, col + 4)
+template <bool HAS_PERM, bool STREAM>
+__device__ __forceinline__ f4 sum_rows(const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ perm,
+                                       int32_t start, int32_t end, int col) {
+  f4 a = {0.f, 0.f, 0.f, 0.f};
+  walk_rows<HAS_PERM, STREAM>(src, ld_src, perm, start, end, col, no_side{}, [&](int32_t, Nothing, const f4& x) { acc4(a, x); });
+  return a;
+}
 
-// ---------------------------------------------------------------------------------------
-// K1, vectorised: feat_dim % 4 == 0, feat_dim <= 4*LPR, 16-B aligned rows.
-// ---------------------------------------------------------------------------------------
+// K1, chunk regime: feat_dim % 4 == 0, feat_dim <= 4*LPR, 16-B aligned rows.
 template <int LPR, bool HAS_PERM>
 __global__ __launch_bounds__(gnc::kBlock) void scatter_sum_csr_vec4(
     const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ perm, int32_t num_nodes, int32_t feat_dim, float* __restrict__ out,
     int64_t ld_out) {
-  constexpr int GPW = kWave / LPR;      // lane groups (destinations) per wave
-  constexpr int ROUNDS = kChunk / GPW;  // rounds to cover the 64-destination chunk
-  const int lane = threadIdx.x & (kWave - 1);
-  const int grp = lane / LPR;
-  const int col = (lane % LPR) * 4;
-  const bool col_ok = col < feat_dim;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t num_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t num_chunks = ((int64_t)num_nodes + kChunk - 1) / kChunk;
-
-  for (int64_t chunk = wave; chunk < num_chunks; chunk += num_waves) {
-    const int64_t base = chunk * kChunk;
-    // lane l holds rowptr[base + l] (clamped), lane 63's upper bound is fetched separately
-    const int64_t vl = base + lane;
-    const int32_t rp = rowptr[vl < num_nodes ? vl : num_nodes];
-    const int64_t vlast = base + kChunk;
-    const int32_t rp_last = rowptr[vlast < num_nodes ? vlast : num_nodes];
-
-#pragma unroll 1
-    for (int r = 0; r < ROUNDS; ++r) {
-      const int slot = r * GPW + grp;  // destination inside the chunk
-      const int64_t v = base + slot;
-      const int32_t start = __shfl(rp, slot, kWave);
-      const int32_t hi = __shfl(rp, (slot + 1) & (kWave - 1), kWave);
-      const int32_t end = (slot + 1 < kWave) ? hi : rp_last;
-      if (base + r * GPW >= num_nodes) break;  // wave-uniform: nothing left in this chunk
-      const bool live = (v < num_nodes) & col_ok;
-
-      f4 a = {0.f, 0.f, 0.f, 0.f};
-      if (live) {
-        int32_t k = start;
-        for (; k + 4 <= end; k += 4) {
-          int32_t i0 = k, i1 = k + 1, i2 = k + 2, i3 = k + 3;
-          if (HAS_PERM) { i0 = perm[k]; i1 = perm[k + 1]; i2 = perm[k + 2]; i3 = perm[k + 3]; }
-          const f4 r0 = ld4_stream(src + (int64_t)i0 * ld_src + col);
-          const f4 r1 = ld4_stream(src + (int64_t)i1 * ld_src + col);
-          const f4 r2 = ld4_stream(src + (int64_t)i2 * ld_src + col);
-          const f4 r3 = ld4_stream(src + (int64_t)i3 * ld_src + col);
-          acc4(a, r0); acc4(a, r1); acc4(a, r2); acc4(a, r3);  // ascending k: reference edge order
-        }
-        for (; k < end; ++k) {
-          const int32_t i0 = HAS_PERM ? perm[k] : k;
-          acc4(a, ld4_stream(src + (int64_t)i0 * ld_src + col));
-        }
-        st4(out + v * ld_out + col, a);
-      }
-    }
-  }
+  for_chunk_destinations<LPR>(rowptr, num_nodes, feat_dim, [&](int64_t v, int32_t start, int32_t end, int col) {
+    st4(out + v * ld_out + col, sum_rows<HAS_PERM, true>(src, ld_src, perm, start, end, col));
+  });
 }
 
-// K1 for a small graph (the reference's one-graph-per-call regime): the kernel above gives a wave 64 destinations and, at
-// 128 features, walks them two at a time - 32 dependent rounds of (ids, rows) per wave while most of the chip is idle
-// (1024 nodes: 16 busy waves, 25..37 us).  Here every lane group takes ONE destination, so the launch is one chain of
-// row pointers -> ids -> rows per group.  Same sums in the same order (bit-identical).
+// K1 for a small graph (the reference's one-graph-per-call regime; 1024 nodes at 128 features: 16 busy waves and 25..37 us in
+// the chunk regime).  Same sums in the same order (bit-identical).
 template <int LPR, bool HAS_PERM>
 __global__ __launch_bounds__(gnc::kBlock) void scatter_sum_csr_small(
     const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ perm, int32_t num_nodes, int32_t feat_dim, float* __restrict__ out,
     int64_t ld_out) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t v = tid / LPR;
-  const int col = (int)(tid % LPR) * 4;
-  if (v >= num_nodes || col >= feat_dim) return;
-  const int32_t start = rowptr[v], end = rowptr[v + 1];
-  f4 a = {0.f, 0.f, 0.f, 0.f};
-  int32_t k = start;
-  for (; k + 4 <= end; k += 4) {
-    int32_t i0 = k, i1 = k + 1, i2 = k + 2, i3 = k + 3;
-    if (HAS_PERM) { i0 = perm[k]; i1 = perm[k + 1]; i2 = perm[k + 2]; i3 = perm[k + 3]; }
-    const f4 r0 = ld4(src + (int64_t)i0 * ld_src + col);
-    const f4 r1 = ld4(src + (int64_t)i1 * ld_src + col);
-    const f4 r2 = ld4(src + (int64_t)i2 * ld_src + col);
-    const f4 r3 = ld4(src + (int64_t)i3 * ld_src + col);
-    acc4(a, r0); acc4(a, r1); acc4(a, r2); acc4(a, r3);  // ascending k: reference edge order
-  }
-  for (; k < end; ++k) {
-    const int32_t i0 = HAS_PERM ? perm[k] : k;
-    acc4(a, ld4(src + (int64_t)i0 * ld_src + col));
-  }
-  st4(out + v * ld_out + col, a);
+  for_small_destinations<LPR>(rowptr, num_nodes, feat_dim, [&](int64_t v, int32_t start, int32_t end, int col) {
+    st4(out + v * ld_out + col, sum_rows<HAS_PERM, false>(src, ld_src, perm, start, end, col));
+  });
 }
 
 // Fix-up of the fused aggregation epilogue (mlp_resident.hip) in ONE launch: blocks [0, fix_blocks) sum the few
@@ -190,20 +115,11 @@ __global__ __launch_bounds__(gnc::kBlock) void scatter_sum_csr_scalar(
     const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ perm, int32_t num_nodes, int32_t feat_dim, float* __restrict__ out,
     int64_t ld_out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t num_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  for (int64_t v = wave; v < num_nodes; v += num_waves) {
-    const int32_t start = rowptr[v], end = rowptr[v + 1];
-    for (int c = lane; c < feat_dim; c += kWave) {
-      float a = 0.f;
-      for (int32_t k = start; k < end; ++k) {
-        const int32_t i = HAS_PERM ? perm[k] : k;
-        a += src[(int64_t)i * ld_src + c];
-      }
-      out[v * ld_out + c] = a;
-    }
-  }
+  for_scalar_destinations(rowptr, num_nodes, feat_dim, no_side{}, [&](int64_t v, int32_t start, int32_t end, int c, Nothing) {
+    float a = 0.f;
+    walk_rows_scalar<HAS_PERM>(src, ld_src, perm, start, end, c, [&](int32_t, float x) { a += x; });
+    out[v * ld_out + c] = a;
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -215,29 +131,16 @@ __global__ __launch_bounds__(gnc::kBlock) void gather_rows_vec4(const float* __r
                                                                 int64_t num_rows, int32_t feat_dim,
                                                                 float* __restrict__ out, int64_t ld_out,
                                                                 const float* __restrict__ addend = nullptr, int64_t ld_add = 0) {
-  constexpr int RPB = gnc::kBlock / LPR;  // rows per block pass
-  const int sub = threadIdx.x % LPR;
-  const int col = sub * 4;
+  const int col = row_pass_col<LPR>();
   if (col >= feat_dim) return;
-  int64_t r = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int64_t stride = (int64_t)gridDim.x * RPB;
-  // two rows in flight per lane
-  for (; r + stride < num_rows; r += 2 * stride) {
-    const int32_t i0 = index[r], i1 = index[r + stride];
-    f4 a = ld4(table + (int64_t)i0 * ld_table + col);
-    f4 b = ld4(table + (int64_t)i1 * ld_table + col);
-    if (ADD) {
-      acc4(a, ld4_stream(addend + r * ld_add + col));
-      acc4(b, ld4_stream(addend + (r + stride) * ld_add + col));
-    }
-    st4(out + r * ld_out + col, a);
-    st4(out + (r + stride) * ld_out + col, b);
-  }
-  if (r < num_rows) {
-    f4 a = ld4(table + (int64_t)index[r] * ld_table + col);
-    if (ADD) acc4(a, ld4_stream(addend + r * ld_add + col));
-    st4(out + r * ld_out + col, a);
-  }
+  for_rows_two_in_flight<LPR>(
+      num_rows,
+      [&](int64_t r) {
+        f4 a = ld4(table + (int64_t)index[r] * ld_table + col);
+        if (ADD) acc4(a, ld4_stream(addend + r * ld_add + col));
+        return a;
+      },
+      [&](int64_t r, const f4& a) { st4(out + r * ld_out + col, a); });
 }
 
 template <bool ADD = false>
@@ -282,62 +185,22 @@ __global__ __launch_bounds__(gnc::kBlock) void edge_features_kernel(const float*
   }
 }
 
-int pow2_lanes_for(int feat_dim) {  // smallest power-of-two lane count whose float4 slices cover a row
-  int lanes = 1;
-  while (lanes * 4 < feat_dim) lanes *= 2;
-  return lanes;
-}
-
-bool vec4_ok(const void* p, int64_t ld, int feat_dim) {
-  return feat_dim % 4 == 0 && feat_dim <= 256 && ld % 4 == 0 && gnc::aligned16(p);
-}
-
 template <bool HAS_PERM>
 int launch_scatter(const float* src, int64_t ld_src, const int32_t* rowptr, const int32_t* perm, int32_t n,
                    int32_t d, float* out, int64_t ld_out, hipStream_t stream) {
-  const int64_t chunks = gnc::ceil_div(n, kChunk);
-  const int waves_per_block = gnc::kBlock / kWave;
+  const dim3 block(gnc::kBlock);
   if (vec4_ok(src, ld_src, d) && vec4_ok(out, ld_out, d)) {
-    static const bool no_small = getenv("GNC_NO_SMALL_K1") != nullptr;  // A/B switch
-    if (!no_small && n <= 64 * gnc::num_cu()) {  // a small graph: one lane group per destination
-      const int lpr = pow2_lanes_for(d);
-      const int64_t threads = (int64_t)n * lpr;
-      dim3 grid((unsigned)gnc::ceil_div(threads, (int64_t)gnc::kBlock)), block(gnc::kBlock);
-      switch (lpr) {
-#define GNC_CASE(L)                                                                                                \
-  case L:                                                                                                          \
-    scatter_sum_csr_small<L, HAS_PERM><<<grid, block, 0, stream>>>(src, ld_src, rowptr, perm, n, d, out, ld_out); \
-    break;
-        GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-        default:
-          gnc::set_error("scatter_sum: internal lane mapping error for D=%d", d);
-          return GNC_ERR_UNSUPPORTED;
-      }
-      return gnc::check_launch("scatter_sum_csr_small");
-    }
-    int64_t blocks = gnc::ceil_div(chunks, waves_per_block);
-    const int64_t cap = gnc::num_cu() * 16;
-    if (blocks > cap) blocks = cap;
-    dim3 grid((unsigned)blocks), block(gnc::kBlock);
-    switch (pow2_lanes_for(d)) {
-#define GNC_CASE(L)                                                                                               \
-  case L:                                                                                                         \
-    scatter_sum_csr_vec4<L, HAS_PERM><<<grid, block, 0, stream>>>(src, ld_src, rowptr, perm, n, d, out, ld_out); \
-    break;
-      GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-      default:
-        gnc::set_error("scatter_sum: internal lane mapping error for D=%d", d);
-        return GNC_ERR_UNSUPPORTED;
-    }
-    return gnc::check_launch("scatter_sum_csr_vec4");
+    // A/B switch of the small regime (profiles/README.md); K1 alone has it, so it stays here and not in forward_plan's rule
+    static const bool no_small = getenv("GNC_NO_SMALL_K1") != nullptr;
+    const ForwardPlan p = no_small ? forward_plan(n, d, false) : forward_plan(n, d);
+    const int rc = dispatch_lanes(p.lpr, [&](auto lanes) {
+      constexpr int L = decltype(lanes)::value;
+      if (p.small) scatter_sum_csr_small<L, HAS_PERM><<<p.grid, block, 0, stream>>>(src, ld_src, rowptr, perm, n, d, out, ld_out);
+      else scatter_sum_csr_vec4<L, HAS_PERM><<<p.grid, block, 0, stream>>>(src, ld_src, rowptr, perm, n, d, out, ld_out);
+    });
+    return rc ? rc : gnc::check_launch(p.small ? "scatter_sum_csr_small" : "scatter_sum_csr_vec4");
   }
-  int64_t blocks = gnc::ceil_div(n, waves_per_block);
-  const int64_t cap = gnc::num_cu() * 16;
-  if (blocks > cap) blocks = cap;
-  scatter_sum_csr_scalar<HAS_PERM><<<dim3((unsigned)blocks), dim3(gnc::kBlock), 0, stream>>>(src, ld_src, rowptr, perm,
-                                                                                              n, d, out, ld_out);
+  scatter_sum_csr_scalar<HAS_PERM><<<scalar_grid(n), block, 0, stream>>>(src, ld_src, rowptr, perm, n, d, out, ld_out);
   return gnc::check_launch("scatter_sum_csr_scalar");
 }
 
@@ -383,21 +246,11 @@ int launch_gather(const float* table, int64_t ld_table, const int32_t* index, co
   const int64_t cap = gnc::num_cu() * 16;
   if (vec4_ok(table, ld_table, feat_dim) && vec4_ok(out, ld_out, feat_dim) && (!ADD || vec4_ok(addend, ld_add, feat_dim))) {
     const int lpr = pow2_lanes_for(feat_dim);
-    int64_t blocks = gnc::ceil_div(num_rows, 2 * (gnc::kBlock / lpr));
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    dim3 grid((unsigned)blocks), block(gnc::kBlock);
-    switch (lpr) {
-#define GNC_CASE(L)                                                                                                            \
-  case L:                                                                                                                      \
-    gather_rows_vec4<L, ADD><<<grid, block, 0, stream>>>(table, ld_table, index, num_rows, feat_dim, out, ld_out, addend, ld_add); \
-    break;
-      GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-      default:
-        gnc::set_error("gather_rows: internal lane mapping error for D=%d", feat_dim);
-        return GNC_ERR_UNSUPPORTED;
-    }
+    const int rc = dispatch_lanes(lpr, [&](auto lanes) {
+      gather_rows_vec4<decltype(lanes)::value, ADD><<<row_pass_grid(num_rows, lpr), dim3(gnc::kBlock), 0, stream>>>(
+          table, ld_table, index, num_rows, feat_dim, out, ld_out, addend, ld_add);
+    });
+    if (rc) return rc;
     return gnc::check_launch("gather_rows_vec4");
   }
   int64_t blocks = gnc::ceil_div(num_rows * feat_dim, gnc::kBlock);

@@ -1,7 +1,6 @@
 // K18: mean and max neighbourhood aggregation over a destination-sorted CSR, their backward, and the division of an
-// aggregate's rows by the in-degree.  The lane mapping is K1's (scatter_gather.hip): LPR = D/4 lanes own one
-// destination row, 16 B per lane, no atomics; a destination's rows are walked in ascending sorted position k (= original edge
-// order, the sort is stable) and every output row is written exactly once.
+// aggregate's rows by the in-degree.  Lane mapping, regimes and the order in which a destination's rows are folded
+// are segment_csr.h's; this file holds the two folds, the division, and the backward's row.
 //
 // MEAN: the running sum exactly as K1 forms it (from +0.0, ascending k), then sum / (float)deg with a true fp32 division; a
 //       destination without rows gives +0.0.  gnc_rows_div_degree_f32 applies the same division to an [N, D] table of K1 sums,
@@ -10,27 +9,14 @@
 //       lowest sorted position, -0.0 == +0.0.  A destination without rows gives +0.0 and argmax -1.  argmax holds the row of
 //       `src` that won (perm[k], or k without a permutation) and is only written when the caller passes a pointer.
 #include "gnc_common.h"
+#include "segment_csr.h"
 
 #include <math.h>
 
 namespace {
 
-using gnc::kWave;
+using namespace gnc_csr;
 
-struct alignas(16) f4 { float x, y, z, w; };
-struct alignas(16) i4 { int32_t x, y, z, w; };
-
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-// the streamed-once message rows of the large-table kernel: nontemporal, as in K1
-__device__ __forceinline__ f4 ld4_stream(const float* p) {
-  typedef float v4 __attribute__((ext_vector_type(4)));
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4*>(p));
-  return f4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
-__device__ __forceinline__ void st4i(int32_t* p, i4 v) { *reinterpret_cast<i4*>(p) = v; }
-
-constexpr int kChunk = 64;  // destinations per wave iteration (K1's)
 constexpr int kMean = GNC_SEGMENT_MEAN;
 constexpr int kMax = GNC_SEGMENT_MAX;
 
@@ -59,36 +45,16 @@ __device__ __forceinline__ void fold4(f4& a, i4& ix, const f4& b, int32_t row) {
 
 __device__ __forceinline__ float mean_of(float sum, float deg) { return sum / deg; }  // THE division of K18 (no fast-math)
 
-// Rows [start, end) of one destination, columns [col, col + 4): four rows requested before the first is folded, folded in
-// ascending k.  Returns the finished output slice (and the winners' rows).
+// Rows [start, end) of one destination, columns [col, col + 4), folded from the mode's identity.  Returns the finished output
+// slice (and the winners' rows).
 template <bool HAS_PERM, int MODE, bool ARG, bool STREAM>
 __device__ __forceinline__ void reduce_rows(const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ perm,
                                             int32_t start, int32_t end, int col, f4& a, i4& ix) {
   const float init = MODE == kMean ? 0.f : -INFINITY;
   a = f4{init, init, init, init};
   ix = i4{-1, -1, -1, -1};
-  int32_t k = start;
-  for (; k + 4 <= end; k += 4) {
-    int32_t i0 = k, i1 = k + 1, i2 = k + 2, i3 = k + 3;
-    if (HAS_PERM) { i0 = perm[k]; i1 = perm[k + 1]; i2 = perm[k + 2]; i3 = perm[k + 3]; }
-    const float* p0 = src + (int64_t)i0 * ld_src + col;
-    const float* p1 = src + (int64_t)i1 * ld_src + col;
-    const float* p2 = src + (int64_t)i2 * ld_src + col;
-    const float* p3 = src + (int64_t)i3 * ld_src + col;
-    const f4 r0 = STREAM ? ld4_stream(p0) : ld4(p0);
-    const f4 r1 = STREAM ? ld4_stream(p1) : ld4(p1);
-    const f4 r2 = STREAM ? ld4_stream(p2) : ld4(p2);
-    const f4 r3 = STREAM ? ld4_stream(p3) : ld4(p3);
-    fold4<MODE, ARG>(a, ix, r0, i0);
-    fold4<MODE, ARG>(a, ix, r1, i1);
-    fold4<MODE, ARG>(a, ix, r2, i2);
-    fold4<MODE, ARG>(a, ix, r3, i3);
-  }
-  for (; k < end; ++k) {
-    const int32_t i0 = HAS_PERM ? perm[k] : k;
-    const float* p0 = src + (int64_t)i0 * ld_src + col;
-    fold4<MODE, ARG>(a, ix, STREAM ? ld4_stream(p0) : ld4(p0), i0);
-  }
+  walk_rows<HAS_PERM, STREAM>(src, ld_src, perm, start, end, col, no_side{},
+                              [&](int32_t row, Nothing, const f4& x) { fold4<MODE, ARG>(a, ix, x, row); });
   const int32_t deg = end - start;
   if (MODE == kMean) {
     if (deg > 0) {
@@ -100,99 +66,63 @@ __device__ __forceinline__ void reduce_rows(const float* __restrict__ src, int64
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// large tables: a wave owns chunks of 64 consecutive destinations (K1's scatter_sum_csr_vec4)
-// ---------------------------------------------------------------------------------------
-template <int LPR, bool HAS_PERM, int MODE, bool ARG>
-__global__ __launch_bounds__(gnc::kBlock) void segment_reduce_csr_vec4(
-    const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm,
-    int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out, int32_t* __restrict__ argmax) {
-  constexpr int GPW = kWave / LPR;      // lane groups (destinations) per wave
-  constexpr int ROUNDS = kChunk / GPW;  // rounds to cover the 64-destination chunk
-  const int lane = threadIdx.x & (kWave - 1);
-  const int grp = lane / LPR;
-  const int col = (lane % LPR) * 4;
-  const bool col_ok = col < feat_dim;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t num_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t num_chunks = ((int64_t)num_nodes + kChunk - 1) / kChunk;
-
-  for (int64_t chunk = wave; chunk < num_chunks; chunk += num_waves) {
-    const int64_t base = chunk * kChunk;
-    // lane l holds rowptr[base + l] (clamped), lane 63's upper bound is fetched separately
-    const int64_t vl = base + lane;
-    const int32_t rp = rowptr[vl < num_nodes ? vl : num_nodes];
-    const int64_t vlast = base + kChunk;
-    const int32_t rp_last = rowptr[vlast < num_nodes ? vlast : num_nodes];
-
-#pragma unroll 1
-    for (int r = 0; r < ROUNDS; ++r) {
-      const int slot = r * GPW + grp;  // destination inside the chunk
-      const int64_t v = base + slot;
-      const int32_t start = __shfl(rp, slot, kWave);
-      const int32_t hi = __shfl(rp, (slot + 1) & (kWave - 1), kWave);
-      const int32_t end = (slot + 1 < kWave) ? hi : rp_last;
-      if (base + r * GPW >= num_nodes) break;  // wave-uniform: nothing left in this chunk
-      if ((v < num_nodes) & col_ok) {
-        f4 a;
-        i4 ix;
-        reduce_rows<HAS_PERM, MODE, ARG, true>(src, ld_src, perm, start, end, col, a, ix);
-        st4(out + v * ld_out + col, a);
-        if (ARG) st4i(argmax + v * feat_dim + col, ix);
-      }
-    }
-  }
-}
-
-// small graphs (N <= 64 x CUs): every lane group takes ONE destination (K1's scatter_sum_csr_small); same folds, same bits
-template <int LPR, bool HAS_PERM, int MODE, bool ARG>
-__global__ __launch_bounds__(gnc::kBlock) void segment_reduce_csr_small(
-    const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm,
-    int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out, int32_t* __restrict__ argmax) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t v = tid / LPR;
-  const int col = (int)(tid % LPR) * 4;
-  if (v >= num_nodes || col >= feat_dim) return;
+// the finished slice of destination v (and its winners) stored
+template <bool HAS_PERM, int MODE, bool ARG, bool STREAM>
+__device__ __forceinline__ void reduce_and_store(const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ perm,
+                                                 int64_t v, int32_t start, int32_t end, int col, int32_t feat_dim,
+                                                 float* __restrict__ out, int64_t ld_out, int32_t* __restrict__ argmax) {
   f4 a;
   i4 ix;
-  reduce_rows<HAS_PERM, MODE, ARG, false>(src, ld_src, perm, rowptr[v], rowptr[v + 1], col, a, ix);
+  reduce_rows<HAS_PERM, MODE, ARG, STREAM>(src, ld_src, perm, start, end, col, a, ix);
   st4(out + v * ld_out + col, a);
   if (ARG) st4i(argmax + v * feat_dim + col, ix);
 }
 
-// generic: any feat_dim / alignment; one wave per destination, scalar columns (K1's scatter_sum_csr_scalar)
+// chunk regime
+template <int LPR, bool HAS_PERM, int MODE, bool ARG>
+__global__ __launch_bounds__(gnc::kBlock) void segment_reduce_csr_vec4(
+    const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm,
+    int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out, int32_t* __restrict__ argmax) {
+  for_chunk_destinations<LPR>(rowptr, num_nodes, feat_dim, [&](int64_t v, int32_t start, int32_t end, int col) {
+    reduce_and_store<HAS_PERM, MODE, ARG, true>(src, ld_src, perm, v, start, end, col, feat_dim, out, ld_out, argmax);
+  });
+}
+
+// small regime; same folds, same bits
+template <int LPR, bool HAS_PERM, int MODE, bool ARG>
+__global__ __launch_bounds__(gnc::kBlock) void segment_reduce_csr_small(
+    const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm,
+    int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out, int32_t* __restrict__ argmax) {
+  for_small_destinations<LPR>(rowptr, num_nodes, feat_dim, [&](int64_t v, int32_t start, int32_t end, int col) {
+    reduce_and_store<HAS_PERM, MODE, ARG, false>(src, ld_src, perm, v, start, end, col, feat_dim, out, ld_out, argmax);
+  });
+}
+
+// scalar regime
 template <bool HAS_PERM, int MODE>
 __global__ __launch_bounds__(gnc::kBlock) void segment_reduce_csr_scalar(
     const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ perm,
     int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out, int32_t* __restrict__ argmax) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t num_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  for (int64_t v = wave; v < num_nodes; v += num_waves) {
-    const int32_t start = rowptr[v], end = rowptr[v + 1];
+  for_scalar_destinations(rowptr, num_nodes, feat_dim, no_side{}, [&](int64_t v, int32_t start, int32_t end, int c, Nothing) {
     const int32_t deg = end - start;
-    for (int c = lane; c < feat_dim; c += kWave) {
-      float a = MODE == kMean ? 0.f : -INFINITY;
-      int32_t ai = -1;
-      for (int32_t k = start; k < end; ++k) {
-        const int32_t i = HAS_PERM ? perm[k] : k;
-        const float b = src[(int64_t)i * ld_src + c];
-        if (MODE == kMean) a += b;
-        else fold1<true>(a, ai, b, i);
-      }
-      if (MODE == kMean) {
-        if (deg > 0) a = mean_of(a, (float)deg);
-      } else if (deg <= 0) {
-        a = 0.f;
-      }
-      out[v * ld_out + c] = a;
-      if (MODE == kMax && argmax) argmax[v * feat_dim + c] = ai;
+    float a = MODE == kMean ? 0.f : -INFINITY;
+    int32_t ai = -1;
+    walk_rows_scalar<HAS_PERM>(src, ld_src, perm, start, end, c, [&](int32_t i, float b) {
+      if (MODE == kMean) a += b;
+      else fold1<true>(a, ai, b, i);
+    });
+    if (MODE == kMean) {
+      if (deg > 0) a = mean_of(a, (float)deg);
+    } else if (deg <= 0) {
+      a = 0.f;
     }
-  }
+    out[v * ld_out + c] = a;
+    if (MODE == kMax && argmax) argmax[v * feat_dim + c] = ai;
+  });
 }
 
 // ---------------------------------------------------------------------------------------
-// backward: one pass over the E rows of grad_src, in the shape of K2's gather_rows_vec4 (two rows in flight per lane)
+// backward: one row pass over the E rows of grad_src
 // ---------------------------------------------------------------------------------------
 template <int MODE>
 __device__ __forceinline__ f4 backward_row(const float* __restrict__ grad_out, int64_t ld_grad, const int32_t* __restrict__ rowptr,
@@ -210,20 +140,12 @@ template <int LPR, int MODE>
 __global__ __launch_bounds__(gnc::kBlock) void segment_reduce_backward_vec4(
     const float* __restrict__ grad_out, int64_t ld_grad, const int32_t* __restrict__ dst_of_row, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ argmax, int64_t num_rows, int32_t feat_dim, float* __restrict__ grad_src, int64_t ld_src) {
-  constexpr int RPB = gnc::kBlock / LPR;  // rows per block pass
-  const int col = (threadIdx.x % LPR) * 4;
+  const int col = row_pass_col<LPR>();
   if (col >= feat_dim) return;
-  int64_t r = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-  const int64_t stride = (int64_t)gridDim.x * RPB;
-  for (; r + stride < num_rows; r += 2 * stride) {
-    const int32_t d0 = dst_of_row[r], d1 = dst_of_row[r + stride];
-    const f4 a = backward_row<MODE>(grad_out, ld_grad, rowptr, argmax, feat_dim, d0, (int32_t)r, col);
-    const f4 b = backward_row<MODE>(grad_out, ld_grad, rowptr, argmax, feat_dim, d1, (int32_t)(r + stride), col);
-    st4(grad_src + r * ld_src + col, a);
-    st4(grad_src + (r + stride) * ld_src + col, b);
-  }
-  if (r < num_rows)
-    st4(grad_src + r * ld_src + col, backward_row<MODE>(grad_out, ld_grad, rowptr, argmax, feat_dim, dst_of_row[r], (int32_t)r, col));
+  for_rows_two_in_flight<LPR>(
+      num_rows,
+      [&](int64_t r) { return backward_row<MODE>(grad_out, ld_grad, rowptr, argmax, feat_dim, dst_of_row[r], (int32_t)r, col); },
+      [&](int64_t r, const f4& g) { st4(grad_src + r * ld_src + col, g); });
 }
 
 template <int MODE>
@@ -270,16 +192,6 @@ __global__ __launch_bounds__(gnc::kBlock) void rows_div_degree_kernel(float* __r
   }
 }
 
-int pow2_lanes_for(int feat_dim) {  // smallest power-of-two lane count whose float4 slices cover a row
-  int lanes = 1;
-  while (lanes * 4 < feat_dim) lanes *= 2;
-  return lanes;
-}
-
-bool vec4_ok(const void* p, int64_t ld, int feat_dim) {
-  return feat_dim % 4 == 0 && feat_dim <= 256 && ld % 4 == 0 && gnc::aligned16(p);
-}
-
 struct FwdArgs {
   const float* src;
   int64_t ld_src;
@@ -291,39 +203,20 @@ struct FwdArgs {
   int32_t* argmax;
 };
 
-template <int LPR, bool HAS_PERM, int MODE, bool ARG>
-void launch_vec_one(const FwdArgs& a, bool small, dim3 grid, hipStream_t stream) {
-  if (small)
-    segment_reduce_csr_small<LPR, HAS_PERM, MODE, ARG><<<grid, dim3(gnc::kBlock), 0, stream>>>(
-        a.src, a.ld_src, a.rowptr, a.perm, a.n, a.d, a.out, a.ld_out, a.argmax);
-  else
-    segment_reduce_csr_vec4<LPR, HAS_PERM, MODE, ARG><<<grid, dim3(gnc::kBlock), 0, stream>>>(
-        a.src, a.ld_src, a.rowptr, a.perm, a.n, a.d, a.out, a.ld_out, a.argmax);
-}
-
 template <bool HAS_PERM, int MODE, bool ARG>
 int launch_vec(const FwdArgs& a, hipStream_t stream) {
-  const int lpr = pow2_lanes_for(a.d);
-  const bool small = a.n <= 64 * gnc::num_cu();  // K1's threshold: one lane group per destination
-  int64_t blocks;
-  if (small) {
-    blocks = gnc::ceil_div((int64_t)a.n * lpr, (int64_t)gnc::kBlock);
-  } else {
-    blocks = gnc::capped_blocks(gnc::ceil_div(a.n, kChunk), gnc::kBlock / kWave, 16);
-  }
-  const dim3 grid((unsigned)blocks);
-  switch (lpr) {
-#define GNC_CASE(L) \
-  case L:           \
-    launch_vec_one<L, HAS_PERM, MODE, ARG>(a, small, grid, stream); \
-    break;
-    GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-    default:
-      gnc::set_error("segment_reduce: internal lane mapping error for D=%d", a.d);
-      return GNC_ERR_UNSUPPORTED;
-  }
-  return gnc::check_launch(small ? "segment_reduce_csr_small" : "segment_reduce_csr_vec4");
+  const ForwardPlan p = forward_plan(a.n, a.d);
+  const dim3 block(gnc::kBlock);
+  const int rc = dispatch_lanes(p.lpr, [&](auto lanes) {
+    constexpr int L = decltype(lanes)::value;
+    if (p.small)
+      segment_reduce_csr_small<L, HAS_PERM, MODE, ARG><<<p.grid, block, 0, stream>>>(a.src, a.ld_src, a.rowptr, a.perm, a.n, a.d,
+                                                                                      a.out, a.ld_out, a.argmax);
+    else
+      segment_reduce_csr_vec4<L, HAS_PERM, MODE, ARG><<<p.grid, block, 0, stream>>>(a.src, a.ld_src, a.rowptr, a.perm, a.n, a.d,
+                                                                                     a.out, a.ld_out, a.argmax);
+  });
+  return rc ? rc : gnc::check_launch(p.small ? "segment_reduce_csr_small" : "segment_reduce_csr_vec4");
 }
 
 template <bool HAS_PERM>
@@ -334,8 +227,7 @@ int launch_forward(const FwdArgs& a, int mode, hipStream_t stream) {
     if (a.argmax) return launch_vec<HAS_PERM, kMax, true>(a, stream);
     return launch_vec<HAS_PERM, kMax, false>(a, stream);
   }
-  const int64_t blocks = gnc::capped_blocks(a.n, gnc::kBlock / kWave, 16);
-  const dim3 grid((unsigned)blocks), block(gnc::kBlock);
+  const dim3 grid = scalar_grid(a.n), block(gnc::kBlock);
   if (mode == kMean)
     segment_reduce_csr_scalar<HAS_PERM, kMean><<<grid, block, 0, stream>>>(a.src, a.ld_src, a.rowptr, a.perm, a.n, a.d, a.out,
                                                                           a.ld_out, nullptr);
@@ -350,20 +242,11 @@ int launch_backward(const float* grad_out, int64_t ld_grad, const int32_t* dst_o
                     int64_t num_rows, int32_t d, float* grad_src, int64_t ld_src, hipStream_t stream) {
   if (vec4_ok(grad_out, ld_grad, d) && vec4_ok(grad_src, ld_src, d) && (MODE == kMean || gnc::aligned16(argmax))) {
     const int lpr = pow2_lanes_for(d);
-    const int64_t blocks = gnc::capped_blocks(num_rows, 2 * (gnc::kBlock / lpr), 16);
-    const dim3 grid((unsigned)blocks), block(gnc::kBlock);
-    switch (lpr) {
-#define GNC_CASE(L)                                                                                                            \
-  case L:                                                                                                                      \
-    segment_reduce_backward_vec4<L, MODE><<<grid, block, 0, stream>>>(grad_out, ld_grad, dst_of_row, rowptr, argmax, num_rows, d, \
-                                                                      grad_src, ld_src);                                       \
-    break;
-      GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-      default:
-        gnc::set_error("segment_reduce_backward: internal lane mapping error for D=%d", d);
-        return GNC_ERR_UNSUPPORTED;
-    }
+    const int rc = dispatch_lanes(lpr, [&](auto lanes) {
+      segment_reduce_backward_vec4<decltype(lanes)::value, MODE><<<row_pass_grid(num_rows, lpr), dim3(gnc::kBlock), 0, stream>>>(
+          grad_out, ld_grad, dst_of_row, rowptr, argmax, num_rows, d, grad_src, ld_src);
+    });
+    if (rc) return rc;
     return gnc::check_launch("segment_reduce_backward_vec4");
   }
   const int64_t blocks = gnc::capped_blocks(num_rows * d, gnc::kBlock, 16);

@@ -1,7 +1,6 @@
 // K21: attention neighbourhood aggregation over a destination-sorted CSR - a softmax-weighted sum of a destination's incoming
-// rows - its backward, and the weights themselves.  The lane mapping and the three regimes are K18's
-// (segment_reduce.hip): LPR = D/4 lanes own one destination row, 16 B per lane, no atomics; a destination's rows are walked in
-// ascending sorted position k and every output row is written exactly once.
+// rows - its backward, and the weights themselves.  Lane mapping, regimes and the order in which a destination's
+// rows are folded are segment_csr.h's; this file holds the softmax arithmetic.
 //
 // Per destination v with rows k, message rows x_k and one score s_k per row:
 //   m = max_k s_k                    first pass over the scores (fmaxf from -inf: a NaN score does not enter m)
@@ -18,25 +17,13 @@
 //   grad_src[r, :] = alpha_r grad_out[d, :]      grad_score[r] = alpha_r sum_c grad_out[d, c] (src[r, c] - out[d, c])
 // Each lane sums its four columns in order, the row's lanes are then added by a fixed xor tree (no LDS).
 #include "gnc_common.h"
+#include "segment_csr.h"
 
 #include <math.h>
 
 namespace {
 
-using gnc::kWave;
-
-struct alignas(16) f4 { float x, y, z, w; };
-
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
-// the streamed-once message rows of the large-table kernel: nontemporal, as in K1 / K18
-__device__ __forceinline__ f4 ld4_stream(const float* p) {
-  typedef float v4 __attribute__((ext_vector_type(4)));
-  const v4 v = __builtin_nontemporal_load(reinterpret_cast<const v4*>(p));
-  return f4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
-
-constexpr int kChunk = 64;  // destinations per wave iteration (K1's)
+using namespace gnc_csr;
 
 __device__ __forceinline__ float weight_of(float s, float m) { return expf(s - m); }  // e_k, unnormalised
 __device__ __forceinline__ float over(float a, float z) { return a / z; }             // THE division of K21 (no fast-math)
@@ -65,8 +52,8 @@ __device__ __forceinline__ float max_score(const float* __restrict__ scores, con
   return m;
 }
 
-// Rows [start, end) of one destination, columns [col, col + 4): four rows requested before the first is folded, folded in
-// ascending k.  Returns the finished output slice and (m, Z).
+// Rows [start, end) of one destination, columns [col, col + 4); a row's score is requested with the row.  Returns the finished
+// output slice and (m, Z).
 template <bool HAS_PERM, bool STREAM>
 __device__ __forceinline__ void softmax_rows(const float* __restrict__ src, int64_t ld_src, const float* __restrict__ scores,
                                              const int32_t* __restrict__ perm, int32_t start, int32_t end, int col, f4& a,
@@ -74,29 +61,9 @@ __device__ __forceinline__ void softmax_rows(const float* __restrict__ src, int6
   m = max_score<HAS_PERM>(scores, perm, start, end);
   a = f4{0.f, 0.f, 0.f, 0.f};
   z = 0.f;
-  int32_t k = start;
-  for (; k + 4 <= end; k += 4) {
-    int32_t i0 = k, i1 = k + 1, i2 = k + 2, i3 = k + 3;
-    if (HAS_PERM) { i0 = perm[k]; i1 = perm[k + 1]; i2 = perm[k + 2]; i3 = perm[k + 3]; }
-    const float s0 = scores[i0], s1 = scores[i1], s2 = scores[i2], s3 = scores[i3];
-    const float* p0 = src + (int64_t)i0 * ld_src + col;
-    const float* p1 = src + (int64_t)i1 * ld_src + col;
-    const float* p2 = src + (int64_t)i2 * ld_src + col;
-    const float* p3 = src + (int64_t)i3 * ld_src + col;
-    const f4 r0 = STREAM ? ld4_stream(p0) : ld4(p0);
-    const f4 r1 = STREAM ? ld4_stream(p1) : ld4(p1);
-    const f4 r2 = STREAM ? ld4_stream(p2) : ld4(p2);
-    const f4 r3 = STREAM ? ld4_stream(p3) : ld4(p3);
-    fold_row(a, z, weight_of(s0, m), r0);
-    fold_row(a, z, weight_of(s1, m), r1);
-    fold_row(a, z, weight_of(s2, m), r2);
-    fold_row(a, z, weight_of(s3, m), r3);
-  }
-  for (; k < end; ++k) {
-    const int32_t i0 = HAS_PERM ? perm[k] : k;
-    const float* p0 = src + (int64_t)i0 * ld_src + col;
-    fold_row(a, z, weight_of(scores[i0], m), STREAM ? ld4_stream(p0) : ld4(p0));
-  }
+  walk_rows<HAS_PERM, STREAM>(
+      src, ld_src, perm, start, end, col, [&](int32_t row) { return scores[row]; },
+      [&](int32_t, float s, const f4& x) { fold_row(a, z, weight_of(s, m), x); });
   if (end > start) a = f4{over(a.x, z), over(a.y, z), over(a.z, z), over(a.w, z)};
   else m = 0.f;  // no rows: out +0.0, saved (0, 0)
 }
@@ -106,98 +73,63 @@ __device__ __forceinline__ void store_saved(float* __restrict__ saved, int64_t v
   saved[2 * v + 1] = z;
 }
 
-// ---------------------------------------------------------------------------------------
-// large tables: a wave owns chunks of 64 consecutive destinations (K18's segment_reduce_csr_vec4)
-// ---------------------------------------------------------------------------------------
+// the finished slice of destination v stored; the lane of column 0 stores (m, Z)
+template <bool HAS_PERM, bool STREAM>
+__device__ __forceinline__ void softmax_and_store(const float* __restrict__ src, int64_t ld_src, const float* __restrict__ scores,
+                                                  const int32_t* __restrict__ perm, int64_t v, int32_t start, int32_t end, int col,
+                                                  float* __restrict__ out, int64_t ld_out, float* __restrict__ saved) {
+  f4 a;
+  float m, z;
+  softmax_rows<HAS_PERM, STREAM>(src, ld_src, scores, perm, start, end, col, a, m, z);
+  st4(out + v * ld_out + col, a);
+  if (col == 0) store_saved(saved, v, m, z);
+}
+
+// chunk regime
 template <int LPR, bool HAS_PERM>
 __global__ __launch_bounds__(gnc::kBlock) void segment_softmax_csr_vec4(
     const float* __restrict__ src, int64_t ld_src, const float* __restrict__ scores, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ perm, int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out,
     float* __restrict__ saved) {
-  constexpr int GPW = kWave / LPR;      // lane groups (destinations) per wave
-  constexpr int ROUNDS = kChunk / GPW;  // rounds to cover the 64-destination chunk
-  const int lane = threadIdx.x & (kWave - 1);
-  const int grp = lane / LPR;
-  const int col = (lane % LPR) * 4;
-  const bool col_ok = col < feat_dim;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t num_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  const int64_t num_chunks = ((int64_t)num_nodes + kChunk - 1) / kChunk;
-
-  for (int64_t chunk = wave; chunk < num_chunks; chunk += num_waves) {
-    const int64_t base = chunk * kChunk;
-    // lane l holds rowptr[base + l] (clamped), lane 63's upper bound is fetched separately
-    const int64_t vl = base + lane;
-    const int32_t rp = rowptr[vl < num_nodes ? vl : num_nodes];
-    const int64_t vlast = base + kChunk;
-    const int32_t rp_last = rowptr[vlast < num_nodes ? vlast : num_nodes];
-
-#pragma unroll 1
-    for (int r = 0; r < ROUNDS; ++r) {
-      const int slot = r * GPW + grp;  // destination inside the chunk
-      const int64_t v = base + slot;
-      const int32_t start = __shfl(rp, slot, kWave);
-      const int32_t hi = __shfl(rp, (slot + 1) & (kWave - 1), kWave);
-      const int32_t end = (slot + 1 < kWave) ? hi : rp_last;
-      if (base + r * GPW >= num_nodes) break;  // wave-uniform: nothing left in this chunk
-      if ((v < num_nodes) & col_ok) {
-        f4 a;
-        float m, z;
-        softmax_rows<HAS_PERM, true>(src, ld_src, scores, perm, start, end, col, a, m, z);
-        st4(out + v * ld_out + col, a);
-        if (col == 0) store_saved(saved, v, m, z);
-      }
-    }
-  }
+  for_chunk_destinations<LPR>(rowptr, num_nodes, feat_dim, [&](int64_t v, int32_t start, int32_t end, int col) {
+    softmax_and_store<HAS_PERM, true>(src, ld_src, scores, perm, v, start, end, col, out, ld_out, saved);
+  });
 }
 
-// small graphs (N <= 64 x CUs): every lane group takes ONE destination; same folds, same bits
+// small regime; same folds, same bits
 template <int LPR, bool HAS_PERM>
 __global__ __launch_bounds__(gnc::kBlock) void segment_softmax_csr_small(
     const float* __restrict__ src, int64_t ld_src, const float* __restrict__ scores, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ perm, int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out,
     float* __restrict__ saved) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t v = tid / LPR;
-  const int col = (int)(tid % LPR) * 4;
-  if (v >= num_nodes || col >= feat_dim) return;
-  f4 a;
-  float m, z;
-  softmax_rows<HAS_PERM, false>(src, ld_src, scores, perm, rowptr[v], rowptr[v + 1], col, a, m, z);
-  st4(out + v * ld_out + col, a);
-  if (col == 0) store_saved(saved, v, m, z);
+  for_small_destinations<LPR>(rowptr, num_nodes, feat_dim, [&](int64_t v, int32_t start, int32_t end, int col) {
+    softmax_and_store<HAS_PERM, false>(src, ld_src, scores, perm, v, start, end, col, out, ld_out, saved);
+  });
 }
 
-// generic: any feat_dim / alignment; one wave per destination, scalar columns
+// scalar regime
 template <bool HAS_PERM>
 __global__ __launch_bounds__(gnc::kBlock) void segment_softmax_csr_scalar(
     const float* __restrict__ src, int64_t ld_src, const float* __restrict__ scores, const int32_t* __restrict__ rowptr,
     const int32_t* __restrict__ perm, int32_t num_nodes, int32_t feat_dim, float* __restrict__ out, int64_t ld_out,
     float* __restrict__ saved) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave;
-  const int64_t num_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
-  for (int64_t v = wave; v < num_nodes; v += num_waves) {
-    const int32_t start = rowptr[v], end = rowptr[v + 1];
-    const float m = max_score<HAS_PERM>(scores, perm, start, end);
-    for (int c = lane; c < feat_dim; c += kWave) {
-      float a = 0.f, z = 0.f;
-      for (int32_t k = start; k < end; ++k) {
-        const int32_t i = HAS_PERM ? perm[k] : k;
-        const float e = weight_of(scores[i], m);
-        a = fmaf(e, src[(int64_t)i * ld_src + c], a);
-        z += e;
-      }
-      if (end > start) a = over(a, z);
-      out[v * ld_out + c] = a;
-      if (c == 0) store_saved(saved, v, end > start ? m : 0.f, z);
-    }
-  }
+  for_scalar_destinations(
+      rowptr, num_nodes, feat_dim, [&](int64_t, int32_t start, int32_t end) { return max_score<HAS_PERM>(scores, perm, start, end); },
+      [&](int64_t v, int32_t start, int32_t end, int c, float m) {
+        float a = 0.f, z = 0.f;
+        walk_rows_scalar<HAS_PERM>(src, ld_src, perm, start, end, c, [&](int32_t i, float x) {
+          const float e = weight_of(scores[i], m);
+          a = fmaf(e, x, a);
+          z += e;
+        });
+        if (end > start) a = over(a, z);
+        out[v * ld_out + c] = a;
+        if (c == 0) store_saved(saved, v, end > start ? m : 0.f, z);
+      });
 }
 
 // ---------------------------------------------------------------------------------------
-// backward: one pass over the E rows in the shape of K18's segment_reduce_backward_vec4 (two rows in flight per lane), plus the
-// dot product over the row's lanes
+// backward: one row pass over the E rows, plus the dot product over the row's lanes
 // ---------------------------------------------------------------------------------------
 struct BwdArgs {
   const float* grad_out;
@@ -256,10 +188,12 @@ __device__ __forceinline__ void finish_row(const BwdArgs& a, const BwdRow& w, in
 }
 
 // (a lane whose columns lie beyond feat_dim stays in the loop with zeros: its group's tree reads it)
+// The row pass written out, not for_rows_two_in_flight (segment_csr.h says why): through the helper this loop came out five
+// scalar instructions longer and measured 0.9 % slower at c3 size.
 template <int LPR>
 __global__ __launch_bounds__(gnc::kBlock) void segment_softmax_backward_vec4(const BwdArgs a) {
   constexpr int RPB = gnc::kBlock / LPR;  // rows per block pass
-  const int col = (threadIdx.x % LPR) * 4;
+  const int col = row_pass_col<LPR>();
   const bool col_ok = col < a.feat_dim;
   int64_t r = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
   const int64_t stride = (int64_t)gridDim.x * RPB;
@@ -299,16 +233,6 @@ __global__ __launch_bounds__(gnc::kBlock) void segment_softmax_weights_kernel(co
     alpha[r] = alpha_of(scores, saved, r, dst_of_row[r]);
 }
 
-int pow2_lanes_for(int feat_dim) {  // smallest power-of-two lane count whose float4 slices cover a row
-  int lanes = 1;
-  while (lanes * 4 < feat_dim) lanes *= 2;
-  return lanes;
-}
-
-bool vec4_ok(const void* p, int64_t ld, int feat_dim) {
-  return feat_dim % 4 == 0 && feat_dim <= 256 && ld % 4 == 0 && gnc::aligned16(p);
-}
-
 bool aligned4(const void* p) { return gnc::aligned_to(p, 4); }
 
 struct FwdArgs {
@@ -323,39 +247,23 @@ struct FwdArgs {
   float* saved;
 };
 
-template <int LPR, bool HAS_PERM>
-void launch_vec_one(const FwdArgs& a, bool small, dim3 grid, hipStream_t stream) {
-  if (small)
-    segment_softmax_csr_small<LPR, HAS_PERM><<<grid, dim3(gnc::kBlock), 0, stream>>>(a.src, a.ld_src, a.scores, a.rowptr, a.perm,
-                                                                                     a.n, a.d, a.out, a.ld_out, a.saved);
-  else
-    segment_softmax_csr_vec4<LPR, HAS_PERM><<<grid, dim3(gnc::kBlock), 0, stream>>>(a.src, a.ld_src, a.scores, a.rowptr, a.perm,
-                                                                                    a.n, a.d, a.out, a.ld_out, a.saved);
-}
-
 template <bool HAS_PERM>
 int launch_forward(const FwdArgs& a, hipStream_t stream) {
+  const dim3 block(gnc::kBlock);
   if (vec4_ok(a.src, a.ld_src, a.d) && vec4_ok(a.out, a.ld_out, a.d)) {
-    const int lpr = pow2_lanes_for(a.d);
-    const bool small = a.n <= 64 * gnc::num_cu();  // K1's threshold: one lane group per destination
-    const int64_t blocks = small ? gnc::ceil_div((int64_t)a.n * lpr, (int64_t)gnc::kBlock)
-                                 : gnc::capped_blocks(gnc::ceil_div(a.n, kChunk), gnc::kBlock / kWave, 16);
-    const dim3 grid((unsigned)blocks);
-    switch (lpr) {
-#define GNC_CASE(L) \
-  case L:           \
-    launch_vec_one<L, HAS_PERM>(a, small, grid, stream); \
-    break;
-      GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-      default:
-        gnc::set_error("segment_softmax: internal lane mapping error for D=%d", a.d);
-        return GNC_ERR_UNSUPPORTED;
-    }
-    return gnc::check_launch(small ? "segment_softmax_csr_small" : "segment_softmax_csr_vec4");
+    const ForwardPlan p = forward_plan(a.n, a.d);
+    const int rc = dispatch_lanes(p.lpr, [&](auto lanes) {
+      constexpr int L = decltype(lanes)::value;
+      if (p.small)
+        segment_softmax_csr_small<L, HAS_PERM><<<p.grid, block, 0, stream>>>(a.src, a.ld_src, a.scores, a.rowptr, a.perm, a.n, a.d,
+                                                                             a.out, a.ld_out, a.saved);
+      else
+        segment_softmax_csr_vec4<L, HAS_PERM><<<p.grid, block, 0, stream>>>(a.src, a.ld_src, a.scores, a.rowptr, a.perm, a.n, a.d,
+                                                                            a.out, a.ld_out, a.saved);
+    });
+    return rc ? rc : gnc::check_launch(p.small ? "segment_softmax_csr_small" : "segment_softmax_csr_vec4");
   }
-  const int64_t blocks = gnc::capped_blocks(a.n, gnc::kBlock / kWave, 16);
-  segment_softmax_csr_scalar<HAS_PERM><<<dim3((unsigned)blocks), dim3(gnc::kBlock), 0, stream>>>(
+  segment_softmax_csr_scalar<HAS_PERM><<<scalar_grid(a.n), block, 0, stream>>>(
       a.src, a.ld_src, a.scores, a.rowptr, a.perm, a.n, a.d, a.out, a.ld_out, a.saved);
   return gnc::check_launch("segment_softmax_csr_scalar");
 }
@@ -365,23 +273,13 @@ int launch_backward(const BwdArgs& a, hipStream_t stream) {
   if (vec4_ok(a.grad_out, a.ld_grad, d) && vec4_ok(a.src, a.ld_src, d) && vec4_ok(a.out, a.ld_out, d) &&
       vec4_ok(a.grad_src, a.ld_gsrc, d)) {
     const int lpr = pow2_lanes_for(d);
-    const int64_t blocks = gnc::capped_blocks(a.num_rows, 2 * (gnc::kBlock / lpr), 16);
-    const dim3 grid((unsigned)blocks), block(gnc::kBlock);
-    switch (lpr) {
-#define GNC_CASE(L) \
-  case L:           \
-    segment_softmax_backward_vec4<L><<<grid, block, 0, stream>>>(a); \
-    break;
-      GNC_CASE(1) GNC_CASE(2) GNC_CASE(4) GNC_CASE(8) GNC_CASE(16) GNC_CASE(32) GNC_CASE(64)
-#undef GNC_CASE
-      default:
-        gnc::set_error("segment_softmax_backward: internal lane mapping error for D=%d", d);
-        return GNC_ERR_UNSUPPORTED;
-    }
+    const int rc = dispatch_lanes(lpr, [&](auto lanes) {
+      segment_softmax_backward_vec4<decltype(lanes)::value><<<row_pass_grid(a.num_rows, lpr), dim3(gnc::kBlock), 0, stream>>>(a);
+    });
+    if (rc) return rc;
     return gnc::check_launch("segment_softmax_backward_vec4");
   }
-  const int64_t blocks = gnc::capped_blocks(a.num_rows, gnc::kBlock / kWave, 16);
-  segment_softmax_backward_scalar<<<dim3((unsigned)blocks), dim3(gnc::kBlock), 0, stream>>>(a);
+  segment_softmax_backward_scalar<<<scalar_grid(a.num_rows), dim3(gnc::kBlock), 0, stream>>>(a);
   return gnc::check_launch("segment_softmax_backward_scalar");
 }
 

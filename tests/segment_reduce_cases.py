@@ -114,7 +114,8 @@ SMALL_N, SMALL_E, HUB = 37, 211, 70
 # destination degrees of the small regime: the unrolled-by-four loop (4, 5, 9, 70), its tail (1, 3, 5, 9, 70), the empty row (0)
 SMALL_DEGREES = (0,) * 3 + (1,) * 6 + (3,) * 6 + (4,) * 8 + (5,) * 8 + (9,) * 5 + (HUB,)
 SMALL_WIDTHS = (3, 8, 64, 128, 256)
-CHUNK_WIDTHS = (64, 128)
+# the chunk walker's corners: one lane per row (4), 64 lanes per row (256), lane groups with idle lanes (12, 100)
+CHUNK_WIDTHS = (4, 12, 64, 100, 128, 256)
 
 
 def small_index(seed: int = 0) -> torch.Tensor:

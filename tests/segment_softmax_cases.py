@@ -22,6 +22,8 @@ U = 2.0 ** -24
 SCALES = (1, 3, 8)
 SMALL_N, SMALL_E, SMALL_WIDTHS, CHUNK_WIDTHS = R.SMALL_N, R.SMALL_E, R.SMALL_WIDTHS, R.CHUNK_WIDTHS
 small_index, chunk_index, values, degrees = R.small_index, R.chunk_index, R.values, R.degrees
+# the backward's xor tree over a row's lanes also reads the idle lanes of a group: 12 is 4 lanes with one idle, 100 is 32 with seven
+BACKWARD_WIDTHS = SMALL_WIDTHS + (12, 100)
 
 
 def scores_for(rows: int, scale: float, seed: int) -> torch.Tensor:

@@ -205,6 +205,27 @@ def test_scatter_sum_bit_exact(native, d, use_perm):
     assert torch.equal(out, out2)
 
 
+@pytest.mark.parametrize("d", [4, 12, 64, 100, 256])
+@pytest.mark.parametrize("use_perm", [True, False])
+def test_scatter_sum_chunk_regime_bit_exact(native, d, use_perm):
+    """64 destinations per wave (N > 64 x CUs) at every corner of the chunk walker: one lane per row (D = 4: slot 63 takes its
+    upper bound in the round in which slot 0 starts), 64 lanes per row (D = 256: 64 rounds of one destination), lane groups with
+    idle lanes (D = 12, 100).  N = 64 x CUs + 65: the last chunk holds ONE destination, which has rows; E = 4 N."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 64 * cus + 65
+    assert n > 64 * cus and n % 64 == 1
+    index = torch.randint(0, n, (4 * n,), generator=torch.Generator().manual_seed(d))
+    index[-3:] = n - 1
+    src = torch.randn(index.numel(), d, generator=torch.Generator().manual_seed(1000 + d), dtype=torch.float32)
+    rowptr, perm, _ = native.csr_build(index.to(DEV), n)
+    if use_perm:
+        out = native.scatter_sum_csr(src.to(DEV), rowptr, perm, n)
+    else:  # messages already in destination-sorted order
+        out = native.scatter_sum_csr(src.to(DEV)[perm.long()], rowptr, None, n)
+    ref = O.scatter_sum_fast(src, index, n)
+    assert torch.equal(out.cpu(), ref) and bool(ref[n - 1].any())
+
+
 def test_scatter_sum_golden_g1(native):
     g = load_golden("g1_scatter.npz")
     src, index = t(g["src"], DEV), t(g["index"], DEV)

@@ -4,7 +4,8 @@ tests/segment_reduce_cases.py, at the smallest shapes that reach each kernel.
 Small regime (one lane group per destination): N = 37, E = 211 with destination degrees 0, 1, 3, 4, 5, 9 and a hub of 70 - the
 unrolled-by-four loop, its tail, the empty row - at D in {3, 8, 64, 128, 256} with and without ``perm``; D = 3 and a
 column-offset view of a wider table (``ld_src != D``, unaligned base) run the scalar kernel.  Chunk regime (64 destinations per
-wave): N = 64 x CUs + 65, so the last chunk holds ONE destination; E = 4 N; D in {64, 128}.
+wave): N = 64 x CUs + 65, so the last chunk holds ONE destination; E = 4 N; D in {4, 12, 64, 100, 128, 256}: one lane per row,
+64 lanes per row and lane groups with idle lanes (12, 100) besides the widths in use.
 
 Bars: max, argmax and the max backward are exact.  Mean: the worst case of fp32 recursive summation, (deg - 1) 2^-24 sum|x| / deg,
 plus one rounding of the quotient (2^-24 |mean|) - the form of the K17 bound in tests/test_gpu_pool_readout.py - and bit-equal to

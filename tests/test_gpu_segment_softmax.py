@@ -4,7 +4,8 @@ the error bars of tests/segment_softmax_cases.py, at the smallest shapes that re
 Small regime (one lane group per destination): N = 37, E = 211 with destination degrees 0, 1, 3, 4, 5, 9 and a hub of 70 at D in
 {3, 8, 64, 128, 256}, scores randn x {1, 3, 8}, with and without ``perm``; D = 3 and a column-offset view of a wider table run
 the scalar kernel.  Chunk regime (64 destinations per wave): N = 64 x CUs + 65, so the last chunk holds ONE destination; E = 4 N;
-D in {64, 128}.
+D in {4, 12, 64, 100, 128, 256}: one lane per row, 64 lanes per row and lane groups with idle lanes (12, 100) besides the widths
+in use.  The backward also runs at D = 12 and 100, where the idle lanes of a group feed zeros into its xor tree.
 
 Bars (tests/segment_softmax_cases.py): u = 2^-24, c_v = 2 deg_v + 2 dmax_v + 12;
   forward |err| <= c_v u sum_k alpha_k |x_k|;  saved: m bit for bit, Z within (deg + 2 dmax + 8) u Z;
@@ -210,7 +211,7 @@ def test_non_finite_scores_stay_inside_their_destination():
     assert float(alpha[rows[17]]) == 0.0 and not bool(torch.signbit(alpha[rows[17]]))
 
 
-@pytest.mark.parametrize("width", C.SMALL_WIDTHS)
+@pytest.mark.parametrize("width", C.BACKWARD_WIDTHS)
 def test_backward_and_weights(width):
     """Through autograd (``functional.segment_softmax_csr``) with ``perm`` and on sorted rows; the weights kernel."""
     from graphnet_classifier_amd import functional as Fn

@@ -112,7 +112,7 @@ def test_small_cases_have_the_degrees_and_the_bars_are_finite():
     assert torch.equal(c, 2 * deg + 2 * dmax + 12) and float(dmax.max()) > 8 and bool((dmax[deg <= 1] == 0).all())
 
 
-@pytest.mark.parametrize("width", C.SMALL_WIDTHS)
+@pytest.mark.parametrize("width", C.BACKWARD_WIDTHS)
 def test_seed_condition_fp32_evaluation_stays_within_half_of_each_bar(width):
     """The project's seed-condition pattern: an fp32 torch evaluation of the same formulas on the CPU uses at most HALF of every
     bar on every small case (if a case fails this, the case changes, not the bar)."""
