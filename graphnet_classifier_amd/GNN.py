@@ -333,13 +333,18 @@ class GraphProcessor(nn.Module):
         return x, edge_attr
 
     def forward_sorted(self, x, topo: GraphTopology, edge_attr, need_edges: bool = True, graph_ptr: Tensor | None = None,
-                       return_pooling: bool = False):
+                       return_pooling: bool = False, compose_kept: bool = True):
         """``need_edges=False``: the caller drops the edge output; the last block may then return None for it.
 
         With pooling layers (``self.pools``, attached by ``GraphNet(pool_ratio=...)``): behind block k its ``TopKPool`` erases
         nodes, and the blocks after it run on the pooled rows and the pooled topology.  ``graph_ptr``: DEVICE int64 [G + 1]
         (None = all rows are one graph).  ``return_pooling=True``: ``(x, edge_attr, graph_ptr', kept)`` with the offsets of the
-        pooled graphs and ``kept`` int32 [N'], the survivors' ORIGINAL rows (composed over the layers; None without pooling)."""
+        pooled graphs and ``kept`` int32 [N'], the survivors' ORIGINAL rows (composed over the layers; None without pooling).
+
+        Padded pooling layers (``TopKPool(padded=True)``) return everything at the input's sizes and read nothing back: ``x`` keeps
+        its row count and ``edge_attr`` its edge count through all blocks, ``graph_ptr'`` ends at the device count N', and ``kept``
+        [rows] holds -1 behind N'.  ``compose_kept=False``: the same tuple with ``kept`` None - the layers' lists are not composed (a
+        read-out needs ``graph_ptr'`` alone)."""
         pools = getattr(self, "pools", None)
         last = len(self.blocks) - 1
         kept = None
@@ -352,8 +357,13 @@ class GraphProcessor(nn.Module):
                 x, edge_attr, pooled_topo, graph_ptr, here = pools[str(k)].forward_sorted(x, topo, edge_attr, graph_ptr,
                                                                                           need_edges=need_edges or k < last)
                 topo = pooled_topo if pooled_topo is not None else topo
-                if return_pooling:
-                    kept = here if kept is None else kept[here.long()]
+                if return_pooling and compose_kept:
+                    if kept is None:
+                        kept = here
+                    elif pools[str(k)].padded:  # -1 marks a slack entry: it must not index (it would wrap around to the last row)
+                        kept = torch.where(here >= 0, kept[here.clamp(min=0).long()], here)
+                    else:
+                        kept = kept[here.long()]
         if return_pooling:
             return x, edge_attr, graph_ptr, kept
         return x, edge_attr
@@ -364,28 +374,51 @@ class TopKPool(nn.Module):
     """The pooling layer of the write-up's GN block (K20): ``score(v) = W2 relu(W1 h_v + b1) + b2`` from ``self.gate`` - an
     ``MLP(in_dim, 1, hidden_dim=hidden)`` with one hidden layer and no norm, on the fused-MLP kernels over all rows - then, per
     graph, the ``k = min(n, max(1, ceil(ratio n)))`` best nodes are kept in their old order and gated, ``h'_v = h_v tanh(score(v))``
-    (``functional.topk_pool``).  One host read-back of the pooled sizes per call."""
+    (``functional.topk_pool``).  One host read-back of the pooled sizes per call - none with ``padded=True``, the capacity-padded
+    form whose outputs keep the input's sizes (a plain attribute: no parameter, no ``state_dict`` key)."""
 
-    def __init__(self, in_dim: int, ratio: float, hidden: int = 32):
+    def __init__(self, in_dim: int, ratio: float, hidden: int = 32, padded: bool = False):
         super().__init__()
         self.ratio = native._check_ratio(ratio, "TopKPool")
+        self.padded = bool(padded)
         self.gate = MLP(in_dim, 1, hidden_dim=int(hidden), hidden_layers=1, activation="ReLU", norm_type=None)
 
     def forward_sorted(self, x: Tensor, topo: GraphTopology, edge_attr: Tensor | None, graph_ptr: Tensor, need_edges: bool = True):
         """``(x', edge_attr', topo', graph_ptr', kept)`` on a prepared topology; ``edge_attr`` in its sorted edge order."""
         scores = self.gate.forward_segments([(x, None)]).view(-1)
-        return Fn.topk_pool(x, scores, topo, graph_ptr, self.ratio, edge_attr if need_edges else None, need_edges=need_edges)
+        return Fn.topk_pool(x, scores, topo, graph_ptr, self.ratio, edge_attr if need_edges else None, need_edges=need_edges,
+                            padded=self.padded)
 
 
 def uses_node_pooling(model: nn.Module) -> bool:
-    """True when ``model`` holds a ``TopKPool``: its forward reads sizes back from the device, so it cannot be captured."""
+    """True when ``model`` holds a ``TopKPool`` (of either form; ``pooling_reads_sizes_back`` tells them apart)."""
     return any(isinstance(m, TopKPool) for m in model.modules())
 
 
+def pooling_reads_sizes_back(model: nn.Module) -> bool:
+    """True when ``model`` holds a ``TopKPool`` that is not padded: its forward reads sizes back from the device, so it cannot be
+    captured."""
+    return any(isinstance(m, TopKPool) and not m.padded for m in model.modules())
+
+
+def pooling_prevents_capture(model: nn.Module) -> bool:
+    """True when no hipGraph capture takes ``model`` because of its top-K pooling: a sized pooling layer reads sizes back, and
+    behind padded layers only a pooled read-out (a ``CombinedModel`` with ``readout`` other than ``"flatten"``) takes the graphs'
+    rows through the device ``graph_ptr'`` - the flatten read-out and a bare ``GraphNet`` would have to narrow to N' on the host."""
+    if not uses_node_pooling(model):
+        return False
+    return pooling_reads_sizes_back(model) or not (isinstance(model, CombinedModel) and model.pooled)
+
+
 def _no_capture_with_pooling(model: nn.Module, who: str) -> None:
-    if uses_node_pooling(model):
+    if pooling_reads_sizes_back(model):
         raise ValueError(f"{who}: top-K node pooling (GraphNet(pool_ratio=...)) reads the pooled node and edge counts back from the "
-                         f"device in every pooling layer, which a hipGraph capture cannot record; run this model eagerly")
+                         f"device in every pooling layer, which a hipGraph capture cannot record; run this model eagerly, or build "
+                         f"it with pool_padded=True")
+    if pooling_prevents_capture(model):
+        raise ValueError(f"{who}: padded top-K node pooling (GraphNet(pool_padded=True)) is captured under a pooled read-out alone "
+                         f"(CombinedModel(readout='mean' / 'max' / 'sum' / 'hybrid' / 'attention')): the flatten read-out and a "
+                         f"bare GraphNet narrow the rows to N' on the host")
 
 
 # --------------------------------------------------------------------------- a7 GraphNet
@@ -421,10 +454,15 @@ class GraphNet(nn.Module):
         attention_hidden = kwargs.get("attention_hidden")  # with another mode the NodeProcessor raises
         # K20: top-K node pooling behind the GN blocks (the write-up's "Pooling(h(k))").  None: no pooling, no module, no keys.
         pool_ratio, pool_after, pool_hidden = kwargs.get("pool_ratio"), kwargs.get("pool_after"), kwargs.get("pool_hidden")
+        # pool_padded: the capacity-padded pooling layers (no read-back, capturable).  No parameter, no key.
+        pool_padded = bool(kwargs.get("pool_padded", False))
         if pool_ratio is None:
-            if pool_after is not None or pool_hidden is not None:
-                raise ValueError("GraphNet: pool_after / pool_hidden belong to pool_ratio, which is None")
+            if pool_after is not None or pool_hidden is not None or pool_padded:
+                raise ValueError("GraphNet: pool_after / pool_hidden / pool_padded belong to pool_ratio, which is None")
         else:
+            if pool_padded and norm_type == "BatchNorm1d":
+                # batch statistics span ALL rows: the slack rows behind N' would enter them (LayerNorm is per row and unaffected)
+                raise NotImplementedError("GraphNet(pool_padded=True): not with norm_type='BatchNorm1d'")
             pool_ratio = native._check_ratio(pool_ratio, "GraphNet(pool_ratio=...)")
             pool_after = list(range(n_blocks)) if pool_after is None else list(pool_after)
             if any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < n_blocks for i in pool_after) \
@@ -452,8 +490,10 @@ class GraphNet(nn.Module):
         self.node_decoder = MLP(out_dim_node, out_dim, hidden_dim_decoder, hidden_layers_decoder, norm_type=None)
         # the pools LAST: every other parameter draws the random numbers it draws without them (graph_processor.pools.<i>.gate.*)
         self.pool_ratio, self.pool_after = pool_ratio, tuple(pool_after) if pool_ratio is not None else ()
+        self.pool_padded = pool_padded and bool(self.pool_after)
         if pool_ratio is not None and self.pool_after:
-            self.graph_processor.pools = nn.ModuleDict({str(i): TopKPool(out_dim_node, pool_ratio, pool_hidden) for i in self.pool_after})
+            self.graph_processor.pools = nn.ModuleDict({str(i): TopKPool(out_dim_node, pool_ratio, pool_hidden, padded=pool_padded)
+                                                        for i in self.pool_after})
 
     @property
     def pooling(self) -> bool:
@@ -468,12 +508,15 @@ class GraphNet(nn.Module):
         return n
 
     def forward_device(self, x: Tensor, pos: Tensor, topo: GraphTopology, graph_ptr: Tensor | None = None,
-                       return_pooling: bool = False):
+                       return_pooling: bool = False, compose_kept: bool = True):
         """GraphNet.forward on device tensors with a prepared topology (models/GNN.py:297-309).  ``graph_ptr``: DEVICE int64
         [G + 1] offsets of the graphs, read by the pooling layers alone (None = one graph; rows of no graph are erased by the first
         pooling layer).  ``return_pooling=True``: ``(out, graph_ptr', kept)`` - the offsets of the rows of ``out`` (``graph_ptr``
         itself without pooling) and the ORIGINAL rows of the survivors, int32 ascending (None without pooling).  With pooling every
-        pooling layer reads two sizes back from the device (one host synchronisation each)."""
+        pooling layer reads two sizes back from the device (one host synchronisation each) - unless the layers are padded
+        (``pool_padded=True``): then nothing is read back, ``out`` keeps all ``rows`` rows, of which those at or behind
+        ``graph_ptr'[-1]`` = N' are unspecified, and ``kept`` int32 [rows] holds -1 behind N'.  ``compose_kept=False``:
+        ``(out, graph_ptr', None)`` - ``kept`` is not composed over the layers (what a read-out needs)."""
         out = self.node_encoder.forward_segments([(x.view(x.size(0), -1), None)])         # :305
         # :299-302 + :306: K6 as the prologue of the edge encoder's launch where a kernel offers it (inference, large batches)
         edge_attr = self.edge_encoder.forward_edge_features(pos, topo.src_sorted, topo.dst_sorted)
@@ -482,8 +525,10 @@ class GraphNet(nn.Module):
             edge_attr = self.edge_encoder.forward_segments([(edge_attr, None)])           # :306
         kept = None
         if self.pooling:
+            # the sized layers compose ``kept`` as they always did; behind padded layers only a caller that takes it pays for it
+            compose = compose_kept and (return_pooling or not self.pool_padded)
             out, _, graph_ptr, kept = self.graph_processor.forward_sorted(out, topo, edge_attr, need_edges=not DROP_DEAD_EDGE_STORE,
-                                                                          graph_ptr=graph_ptr, return_pooling=True)
+                                                                          graph_ptr=graph_ptr, return_pooling=True, compose_kept=compose)
         else:
             out, _ = self.graph_processor.forward_sorted(out, topo, edge_attr, need_edges=not DROP_DEAD_EDGE_STORE)  # :307
         out = self.node_decoder.forward_segments([(out, None)])                           # :308
@@ -527,7 +572,11 @@ class GraphNet(nn.Module):
         x = x.to(device=dev, dtype=torch.float32)
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
-        out = self.forward_device(x, pos, topo)
+        if self.pool_padded:  # the public shape is the sized mode's: ONE read of N' narrows the padded rows
+            out, graph_ptr, _ = self.forward_device(x, pos, topo, return_pooling=True, compose_kept=False)
+            out = out[:int(graph_ptr[-1].item())]
+        else:
+            out = self.forward_device(x, pos, topo)
         return out if back == dev else out.to(back)
 
 
@@ -578,9 +627,15 @@ class CapturedForward:
             self.pos = pos.to(device=dev, dtype=torch.float32).clone()
             self.topo = get_topology(edge_index, self.x.size(0), dev)  # host sync happens here, outside the capture
 
-            whole = torch.tensor([0, self.num_nodes], dtype=torch.int64, device=dev) if pooled else None
+            # [0, N], a pooled read-out's (and the pooling layers') graph_ptr.  Kept on the object: the hipGraph records its
+            # ADDRESS, and a buffer that only ``run`` held would go back to the allocator with it - the next small allocation
+            # would then land on the offsets that every later replay reads.
+            whole = self._whole = torch.tensor([0, self.num_nodes], dtype=torch.int64, device=dev) if pooled else None
 
             def run():
+                if pooled and gnet.pooling:  # padded top-K pooling: the read-out takes the POOLED graph's rows [0, N')
+                    y, ptr, _ = gnet.forward_device(self.x, self.pos, self.topo, graph_ptr=whole, return_pooling=True, compose_kept=False)
+                    return model.readout_logits(y, ptr)[0]
                 y = gnet.forward_device(self.x, self.pos, self.topo)
                 if pooled:
                     return model.readout_logits(y, whole)[0]
@@ -613,6 +668,11 @@ class CapturedForward:
             def run():
                 topo = GraphTopology(self.edge_index, rows, device=dev, validate="deferred")  # never the cache
                 self._status = topo.status  # the capture's own flags: every replay rewrites them
+                if pooled and gnet.pooling:  # padded top-K pooling: the first layer erases the slots and the dummies with the
+                    # rows of no graph, and the read-out takes the POOLED graph's rows [0, N')
+                    y, ptr, _ = gnet.forward_device(self.x, self.pos, topo, graph_ptr=self._graph_ptr, return_pooling=True,
+                                                    compose_kept=False)
+                    return model.readout_logits(y, ptr)[0]
                 y = gnet.forward_device(self.x, self.pos, topo)
                 if pooled:  # rows [0, valid_nodes): the slots behind them and the dummies are outside the graph
                     return model.readout_logits(y, self._graph_ptr)[0]
@@ -932,7 +992,11 @@ class CombinedModel(nn.Module):
         with torch.no_grad():
             x = x.to(device=dev, dtype=torch.float32)
             pos = pos.to(device=dev, dtype=torch.float32)
-            y = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev))  # (pooled GraphNet: the survivors)
+            # (pooled GraphNet: the survivors; padded layers: the rows in front of N', one read-back)
+            y, ptr, _ = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev), return_pooling=True,
+                                                      compose_kept=False)
+            if self.graph_net.pool_padded:
+                y = y[:int(ptr[-1].item())]
             whole = torch.arange(2, dtype=torch.int64, device=dev) * y.size(0)  # [0, N], built on the device
             _, alpha = Fn.graph_attention_pool(y, self.gate.forward_segments([(y, None)]).view(-1), whole, return_weights=True)
         return alpha if back == dev else alpha.to(back)
@@ -950,7 +1014,9 @@ class CombinedModel(nn.Module):
         with torch.no_grad():
             x = x.to(device=dev, dtype=torch.float32)
             pos = pos.to(device=dev, dtype=torch.float32)
-            _, _, kept = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev), return_pooling=True)
+            _, ptr, kept = self.graph_net.forward_device(x, pos, get_topology(edge_index, x.size(0), dev), return_pooling=True)
+            if self.graph_net.pool_padded:  # the N' survivors in front of the -1 tail: one read-back
+                kept = kept[:int(ptr[-1].item())]
         kept = kept.long()
         return kept if back == dev else kept.to(back)
 
@@ -963,7 +1029,14 @@ class CombinedModel(nn.Module):
         x = x.to(device=dev, dtype=torch.float32)
         pos = pos.to(device=dev, dtype=torch.float32)
         topo = get_topology(edge_index, x.size(0), dev)
-        y = self.graph_net.forward_device(x, pos, topo)  # (a pooled GraphNet: the survivors' rows, one graph)
+        if self.graph_net.pool_padded:  # padded top-K pooling: all rows come back, graph_ptr' = [0, N'] says which are the graph's
+            y, ptr, _ = self.graph_net.forward_device(x, pos, topo, return_pooling=True, compose_kept=False)
+            if self.pooled:  # no read-back: the read-out takes rows through the device offsets
+                logits = self.readout_logits(y, ptr)[0]
+                return logits if back == dev else logits.to(back)
+            y = y[:int(ptr[-1].item())]  # the flatten read-out is sized on the host: one read of N'
+        else:
+            y = self.graph_net.forward_device(x, pos, topo)  # (a pooled GraphNet: the survivors' rows, one graph)
         if self.pooled:
             logits = self.readout_logits(y, torch.arange(2, dtype=torch.int64, device=dev) * y.size(0))[0]  # [0, N], built on the device
             return logits if back == dev else logits.to(back)
@@ -1010,7 +1083,8 @@ class CombinedModel(nn.Module):
         if self.graph_net.pooling:  # K20: the read-out takes the POOLED graphs' offsets
             if graph_ptr is None:
                 raise ValueError("forward_batched_device: behind top-K pooling (pool_ratio) the flatten read-out needs graph_ptr")
-            y, graph_ptr, _ = self.graph_net.forward_device(x, pos, topo, graph_ptr=graph_ptr, return_pooling=True)
+            y, graph_ptr, _ = self.graph_net.forward_device(x, pos, topo, graph_ptr=graph_ptr, return_pooling=True,
+                                                            compose_kept=not self.graph_net.pool_padded)
             return self.readout_logits(y, graph_ptr)
         y = self.graph_net.forward_device(x, pos, topo)  # [N_total, out_dim]
         return self.readout_logits(y, graph_ptr, num_graphs)

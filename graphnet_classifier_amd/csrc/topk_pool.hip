@@ -18,6 +18,12 @@
 //            topk_rowptr_kernel      thread per kept node: rowptr'[v'] = exclusive count at rowptr[v]; rowptr'[N'] = E'
 //   rows     topk_rows_forward_kernel / topk_rows_backward_kernel: one streaming pass each, 16-byte accesses at C % 4 == 0; the row
 //            tiling is pool_index.h's (row_geometry, row_lane), load_vec / store_vec are graph_reduce.h's
+//
+// The capacity-padded form (gnc_topk_pool_select_padded_f32 / gnc_topk_pool_filter_edges_padded; the layout is topk_pool_index.h's)
+// is the same launches with `padded` set, none added: every array is written over its whole length, so nothing behind N' / E' is
+// left to a host read-back.  The select workgroups write kept[N', rows) = -1 between them; topk_edge_write_kernel writes, for each
+// of its positions p >= E', the slack self-loop at p and kept_edges[p] = -1 (counts[1] is final before it starts);
+// topk_rowptr_kernel covers all rows + 1 entries.  The row launches then run with n_out = rows / E: a -1 id gives a +0.0 row.
 #include "graph_reduce.h"
 #include "topk_pool_index.h"
 
@@ -84,7 +90,7 @@ __device__ __forceinline__ uint32_t key_at(const float* __restrict__ scores, int
 // workgroup g: the kept set of graph g
 __global__ __launch_bounds__(kT) void topk_select_kernel(const float* __restrict__ scores, const int64_t* __restrict__ graph_ptr, int64_t G,
                                                          int64_t rows, double ratio, const int64_t* __restrict__ new_ptr,
-                                                         int32_t* __restrict__ new_id, int32_t* __restrict__ kept) {
+                                                         int32_t* __restrict__ new_id, int32_t* __restrict__ kept, int padded) {
   __shared__ uint32_t s_hist[256];
   __shared__ uint32_t s_wave[kWaves];
   __shared__ uint32_t s_sel[2];
@@ -96,6 +102,10 @@ __global__ __launch_bounds__(kT) void topk_select_kernel(const float* __restrict
   gap_rows(graph_ptr, g, G, rows, lo, hi, tail);
   for (int64_t r = lo + t; r < hi; r += kT) new_id[r] = -1;
   for (int64_t r = tail + t; r < rows; r += kT) new_id[r] = -1;
+  if (padded) {  // uniform; new_ptr[G] = N' is the offsets launch's
+    const int64_t n_out = slack_of(new_ptr[G], 0, rows, 0).n_out;
+    for (int64_t r = kept_tail_first(n_out, g, t); r < rows; r += kept_tail_stride(G)) kept[r] = -1;
+  }
   const int64_t n = b - a;
   if (n == 0) return;  // uniform
   const uint32_t k = (uint32_t)keep_count(ratio, n);
@@ -159,6 +169,7 @@ struct EdgeArgs {
   int32_t* dst_out;
   int32_t* kept_edges;
   int32_t* edge_new_id;
+  const int64_t* counts;  // padded form: [N', E'] (NULL: the sized form, nothing is written at or behind E')
 };
 
 // new endpoints of the edge at sorted position p; false: dropped (an endpoint erased, or outside [0, rows): never an index)
@@ -201,6 +212,8 @@ __global__ __launch_bounds__(kT) void topk_tile_scan_kernel(int32_t* __restrict_
 __global__ __launch_bounds__(kT) void topk_edge_write_kernel(const EdgeArgs a) {
   __shared__ uint32_t s_wave[kWaves];
   uint32_t base = (uint32_t)a.tile[blockIdx.x];
+  const bool padded = a.counts != nullptr;  // uniform
+  const Slack slack = padded ? slack_of(a.counts[0], a.counts[1], a.rows, a.E) : Slack{};
 #pragma unroll 1
   for (int i = 0; i < kEdgeSteps; ++i) {  // uniform: positions behind E take part in the scan with a zero
     const int64_t p = edge_position(blockIdx.x, i, threadIdx.x);
@@ -216,20 +229,27 @@ __global__ __launch_bounds__(kT) void topk_edge_write_kernel(const EdgeArgs a) {
         a.dst_out[j] = d;
         a.kept_edges[j] = (int32_t)p;
       }
+      if (padded && p >= slack.e_out) {  // j <= E' - 1 for every kept edge: the slack positions are written here alone
+        const int32_t row = (int32_t)slack_edge_row(slack, a.rows, p - slack.e_out);  // in [0, rows): the launcher requires rows >= 1
+        a.src_out[p] = row;
+        a.dst_out[p] = row;
+        a.kept_edges[p] = -1;
+      }
     }
     base += total;
   }
 }
 
-// thread i < N': rowptr'[i] = kept edges in front of rowptr[kept[i]]; thread N': E'
+// thread i < N': rowptr'[i] = kept edges in front of rowptr[kept[i]]; thread N': E'; padded: threads N' < i <= rows, the slack rows' offsets
 __global__ __launch_bounds__(kT) void topk_rowptr_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ kept,
                                                          const int32_t* __restrict__ excl, const int64_t* __restrict__ counts, int64_t E,
-                                                         int64_t rows, int32_t* __restrict__ rowptr_out) {
+                                                         int64_t rows, int32_t* __restrict__ rowptr_out, int padded) {
   int64_t n_out = counts[0];
   n_out = n_out < 0 ? 0 : (n_out > rows ? rows : n_out);
   const int32_t e_out = (int32_t)counts[1];
-  for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i <= n_out; i += (int64_t)gridDim.x * kT) {
-    int32_t value = e_out;
+  const int64_t first = (int64_t)blockIdx.x * kT + threadIdx.x, stride = (int64_t)gridDim.x * kT;
+  for (int64_t i = first; i <= n_out; i += stride) {
+    int32_t value = padded && i == rows ? (int32_t)E : e_out;  // (padded, every row kept: the list still ends at E)
     if (i < n_out) {
       const int32_t v = kept[i];
       const int64_t p = (uint64_t)(int64_t)v < (uint64_t)rows ? (int64_t)rowptr[v] : E;
@@ -238,6 +258,9 @@ __global__ __launch_bounds__(kT) void topk_rowptr_kernel(const int32_t* __restri
     }
     rowptr_out[i] = value;
   }
+  if (!padded) return;  // uniform
+  const Slack slack = slack_of(n_out, counts[1], rows, E);
+  for (int64_t i = n_out + 1 + first; i <= rows; i += stride) rowptr_out[i] = (int32_t)slack_rowptr(slack, rows, E, i);  // arithmetic alone
 }
 
 struct RowsArgs {
@@ -326,54 +349,73 @@ constexpr int64_t kMaxRows = (1ll << 31) - 1;
 
 }  // namespace
 
-extern "C" int gnc_topk_pool_select_f32(const float* scores, const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, double ratio,
-                                        int32_t* new_id, int32_t* kept, int64_t* new_graph_ptr, int64_t* counts, void* stream) {
+namespace {
+
+int select_launch(const char* who, const float* scores, const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, double ratio, int32_t* new_id,
+                  int32_t* kept, int64_t* new_graph_ptr, int64_t* counts, void* stream, int padded) {
   GNC_REQUIRE(rows >= 0 && rows <= kMaxRows && num_graphs >= 1 && num_graphs <= kMaxRows,
-              "gnc_topk_pool_select_f32: rows %lld / graphs %lld outside the supported set (0 <= rows < 2^31, 1 <= graphs < 2^31)",
+              "%s: rows %lld / graphs %lld outside the supported set (0 <= rows < 2^31, 1 <= graphs < 2^31)", who,
               (long long)rows, (long long)num_graphs);
-  GNC_REQUIRE(ratio > 0.0 && ratio <= 1.0, "gnc_topk_pool_select_f32: ratio %g is not in (0, 1]", ratio);
+  GNC_REQUIRE(ratio > 0.0 && ratio <= 1.0, "%s: ratio %g is not in (0, 1]", who, ratio);
   GNC_REQUIRE(graph_ptr && new_graph_ptr && counts && ((scores && new_id && kept) || rows == 0),
-              "gnc_topk_pool_select_f32: null scores / graph_ptr / new_id / kept / new_graph_ptr / counts");
+              "%s: null scores / graph_ptr / new_id / kept / new_graph_ptr / counts", who);
   GNC_REQUIRE(aligned_to(scores, 4) && aligned_to(new_id, 4) && aligned_to(kept, 4) && aligned_to(graph_ptr, 8) &&
                   aligned_to(new_graph_ptr, 8) && aligned_to(counts, 8),
-              "gnc_topk_pool_select_f32: a pointer is not aligned to its element size");
+              "%s: a pointer is not aligned to its element size", who);
   hipStream_t st = static_cast<hipStream_t>(stream);
   topk_offsets_kernel<<<dim3(1), dim3(kT), 0, st>>>(graph_ptr, num_graphs, rows, ratio, new_graph_ptr, counts);
   if (int rc = gnc::check_launch("topk_offsets_kernel")) return rc;
   if (rows == 0) return GNC_OK;
   topk_select_kernel<<<dim3((unsigned)num_graphs), dim3(kT), 0, st>>>(scores, graph_ptr, num_graphs, rows, ratio, new_graph_ptr, new_id,
-                                                                       kept);
+                                                                       kept, padded);
   return gnc::check_launch("topk_select_kernel");
+}
+
+}  // namespace
+
+extern "C" int gnc_topk_pool_select_f32(const float* scores, const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, double ratio,
+                                        int32_t* new_id, int32_t* kept, int64_t* new_graph_ptr, int64_t* counts, void* stream) {
+  return select_launch("gnc_topk_pool_select_f32", scores, graph_ptr, num_graphs, rows, ratio, new_id, kept, new_graph_ptr, counts, stream, 0);
+}
+
+// The padded form: the same two launches; kept[N', rows) = -1 as well, so all `rows` entries of `kept` are defined.
+extern "C" int gnc_topk_pool_select_padded_f32(const float* scores, const int64_t* graph_ptr, int64_t num_graphs, int64_t rows,
+                                               double ratio, int32_t* new_id, int32_t* kept, int64_t* new_graph_ptr, int64_t* counts,
+                                               void* stream) {
+  return select_launch("gnc_topk_pool_select_padded_f32", scores, graph_ptr, num_graphs, rows, ratio, new_id, kept, new_graph_ptr, counts, stream,
+                       1);
 }
 
 extern "C" int64_t gnc_topk_pool_edge_workspace_ints(int64_t num_edges) {
   return num_edges < 0 || num_edges > kMaxRows ? -1 : edge_workspace_ints(num_edges);
 }
 
-extern "C" int gnc_topk_pool_filter_edges(const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr, int64_t num_edges,
-                                          int64_t rows, const int32_t* new_id, const int32_t* kept, int64_t* counts, int32_t* src_out,
-                                          int32_t* dst_out, int32_t* kept_edges, int32_t* edge_new_id, int32_t* rowptr_out,
-                                          int32_t* workspace, int64_t workspace_ints, void* stream) {
+namespace {
+
+int filter_launch(const char* who, const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr, int64_t num_edges, int64_t rows,
+                  const int32_t* new_id, const int32_t* kept, int64_t* counts, int32_t* src_out, int32_t* dst_out, int32_t* kept_edges,
+                  int32_t* edge_new_id, int32_t* rowptr_out, int32_t* workspace, int64_t workspace_ints, void* stream, int padded) {
   GNC_REQUIRE(rows >= 0 && rows <= kMaxRows && num_edges >= 0 && num_edges <= kMaxRows,
-              "gnc_topk_pool_filter_edges: rows %lld / edges %lld outside the supported set (both in [0, 2^31))", (long long)rows,
+              "%s: rows %lld / edges %lld outside the supported set (both in [0, 2^31))", who, (long long)rows,
               (long long)num_edges);
   GNC_REQUIRE(counts && rowptr_out && ((rowptr && new_id && kept) || rows == 0),
-              "gnc_topk_pool_filter_edges: null rowptr / new_id / kept / counts / rowptr_out");
+              "%s: null rowptr / new_id / kept / counts / rowptr_out", who);
   GNC_REQUIRE((src_sorted && dst_sorted && src_out && dst_out && kept_edges && edge_new_id) || num_edges == 0,
-              "gnc_topk_pool_filter_edges: null src_sorted / dst_sorted / src_out / dst_out / kept_edges / edge_new_id");
+              "%s: null src_sorted / dst_sorted / src_out / dst_out / kept_edges / edge_new_id", who);
   const int64_t need = edge_workspace_ints(num_edges);
-  GNC_REQUIRE(need == 0 || (workspace && workspace_ints >= need), "gnc_topk_pool_filter_edges: the workspace needs %lld ints",
-              (long long)need);
+  GNC_REQUIRE(need == 0 || (workspace && workspace_ints >= need), "%s: the workspace needs %lld ints", who, (long long)need);
   GNC_REQUIRE(aligned_to(src_sorted, 4) && aligned_to(dst_sorted, 4) && aligned_to(rowptr, 4) && aligned_to(new_id, 4) && aligned_to(kept, 4) &&
                   aligned_to(src_out, 4) && aligned_to(dst_out, 4) && aligned_to(kept_edges, 4) && aligned_to(edge_new_id, 4) &&
                   aligned_to(rowptr_out, 4) && aligned_to(workspace, 4) && aligned_to(counts, 8),
-              "gnc_topk_pool_filter_edges: a pointer is not aligned to its element size");
+              "%s: a pointer is not aligned to its element size", who);
+  if (padded && rows == 0) return GNC_OK;  // no row a slack edge could loop on: nothing is launched
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t tiles = edge_tiles(num_edges);
   EdgeArgs a = {};
   a.src = src_sorted, a.dst = dst_sorted, a.new_id = new_id, a.E = num_edges, a.rows = rows;
   a.tile = workspace, a.excl = workspace ? workspace + tiles : nullptr;
   a.src_out = src_out, a.dst_out = dst_out, a.kept_edges = kept_edges, a.edge_new_id = edge_new_id;
+  a.counts = padded ? counts : nullptr;
   if (tiles > 0) {
     topk_edge_count_kernel<<<dim3((unsigned)tiles), dim3(kT), 0, st>>>(a);
     if (int rc = gnc::check_launch("topk_edge_count_kernel")) return rc;
@@ -385,8 +427,29 @@ extern "C" int gnc_topk_pool_filter_edges(const int32_t* src_sorted, const int32
     if (int rc = gnc::check_launch("topk_edge_write_kernel")) return rc;
   }
   topk_rowptr_kernel<<<dim3((unsigned)gnc::capped_blocks(rows + 1, kT)), dim3(kT), 0, st>>>(rowptr, kept, a.excl, counts, num_edges, rows,
-                                                                                     rowptr_out);
+                                                                                     rowptr_out, padded);
   return gnc::check_launch("topk_rowptr_kernel");
+}
+
+}  // namespace
+
+extern "C" int gnc_topk_pool_filter_edges(const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr, int64_t num_edges,
+                                          int64_t rows, const int32_t* new_id, const int32_t* kept, int64_t* counts, int32_t* src_out,
+                                          int32_t* dst_out, int32_t* kept_edges, int32_t* edge_new_id, int32_t* rowptr_out,
+                                          int32_t* workspace, int64_t workspace_ints, void* stream) {
+  return filter_launch("gnc_topk_pool_filter_edges", src_sorted, dst_sorted, rowptr, num_edges, rows, new_id, kept, counts, src_out, dst_out,
+                       kept_edges, edge_new_id, rowptr_out, workspace, workspace_ints, stream, 0);
+}
+
+// The padded form: the same four launches; src_out / dst_out / kept_edges are written over all E entries (slack self-loops and -1
+// at and behind E') and rowptr_out over all rows + 1, ending at E.  `kept` is gnc_topk_pool_select_padded_f32's.
+extern "C" int gnc_topk_pool_filter_edges_padded(const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr,
+                                                 int64_t num_edges, int64_t rows, const int32_t* new_id, const int32_t* kept,
+                                                 int64_t* counts, int32_t* src_out, int32_t* dst_out, int32_t* kept_edges,
+                                                 int32_t* edge_new_id, int32_t* rowptr_out, int32_t* workspace, int64_t workspace_ints,
+                                                 void* stream) {
+  return filter_launch("gnc_topk_pool_filter_edges_padded", src_sorted, dst_sorted, rowptr, num_edges, rows, new_id, kept, counts, src_out,
+                       dst_out, kept_edges, edge_new_id, rowptr_out, workspace, workspace_ints, stream, 1);
 }
 
 namespace {

@@ -51,6 +51,45 @@ GNC_POOL_HD int64_t edge_position(int64_t tile, int step, int t) { return tile *
 // count of kept edges at EVERY sorted position behind.
 GNC_POOL_HD int64_t edge_workspace_ints(int64_t E) { return edge_tiles(E) + E; }
 
+// ---- the capacity-padded layout: a pooling layer's outputs keep the input's sizes, `rows` node rows and E edges.
+// Behind the N' kept rows lie S_R = rows - N' SLACK rows (zero rows of no graph), behind the E' kept edges S_E = E - E' slack
+// edges, each a self-loop of a slack row, spread evenly: slack edge t (position E' + t) belongs to slack row floor(t S_R / S_E), so
+// the list stays destination-sorted, slack row u owns the edges [ceil(u S_E / S_R), ceil((u + 1) S_E / S_R)) and none owns more
+// than ceil(S_E / S_R).  Products of two values below 2^31: 64 bits hold them.
+struct Slack {
+  int64_t n_out, e_out;  // N', E': the device counts, clamped into [0, rows] / [0, E]
+  int64_t s_r, s_e;      // slack rows, slack edges
+};
+
+GNC_POOL_HD Slack slack_of(int64_t n_count, int64_t e_count, int64_t rows, int64_t E) {
+  Slack s;
+  s.n_out = n_count < 0 ? 0 : (n_count > rows ? rows : n_count);
+  s.e_out = e_count < 0 ? 0 : (e_count > E ? E : e_count);
+  s.s_r = rows - s.n_out;
+  s.s_e = E - s.e_out;
+  return s;
+}
+
+// Row of slack edge t, 0 <= t < S_E (rows >= 1).  S_R == 0 - every row was kept, so a dropped edge had an endpoint outside
+// [0, rows) and the source topology's flags are set: the result is poisoned, and the loops go to the last row so that no index
+// leaves the table.
+GNC_POOL_HD int64_t slack_edge_row(const Slack& s, int64_t rows, int64_t t) {
+  return s.s_r > 0 ? s.n_out + (int64_t)((uint64_t)t * (uint64_t)s.s_r / (uint64_t)s.s_e) : rows - 1;
+}
+
+// rowptr'[i] for N' < i <= rows: E' + ceil((i - N') S_E / S_R); rowptr'[rows] = E (also with S_R == 0, where the last row takes
+// the poisoned result's slack loops).
+GNC_POOL_HD int64_t slack_rowptr(const Slack& s, int64_t rows, int64_t E, int64_t i) {
+  if (i >= rows) return E;
+  const uint64_t u = (uint64_t)(i - s.n_out);
+  return s.e_out + (int64_t)((u * (uint64_t)s.s_e + (uint64_t)s.s_r - 1) / (uint64_t)s.s_r);
+}
+
+// The tail kept[N', rows) = -1 is written by the select workgroups together: workgroup g, thread t takes N' + g kT + t, then
+// strides by G kT.
+GNC_POOL_HD int64_t kept_tail_first(int64_t n_out, int64_t g, int t) { return n_out + g * kT + t; }
+GNC_POOL_HD int64_t kept_tail_stride(int64_t G) { return G * kT; }
+
 // (the row tiling of the compaction launches is pool_index.h's row_geometry / row_lane)
 using gnc_pool::RowGeometry;
 using gnc_pool::row_geometry;

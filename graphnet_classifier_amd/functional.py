@@ -850,7 +850,7 @@ class _TopKEdgeRows(torch.autograd.Function):
 
 
 def topk_pool(x: torch.Tensor, scores: torch.Tensor, topo, graph_ptr: torch.Tensor, ratio: float, edge_attr: torch.Tensor | None = None,
-              need_edges: bool = True):
+              need_edges: bool = True, padded: bool = False):
     """Top-K node pooling (K20): per graph of ``graph_ptr`` (device int64 [G + 1]) keep the ``k = min(n, max(1, ceil(ratio n)))``
     rows with the best ``scores`` [rows] - larger first, ``-0.0 == +0.0``, NaN last, ties by lower row - IN THEIR OLD ORDER, gate
     them (``x' = x tanh(s)``, so the scorer receives a gradient), and keep the edges of ``topo`` between two kept nodes, renumbered
@@ -860,10 +860,26 @@ def topk_pool(x: torch.Tensor, scores: torch.Tensor, topo, graph_ptr: torch.Tens
 
     ONE host synchronisation per call: the sizes N' and E' are read back from the device (a single read of both) to size the
     outputs, so this cannot run inside a hipGraph capture.  ``need_edges=False`` (nothing reads the pooled edges, e.g. behind the
-    last GN block): nodes only, ``topo'`` is None and the read-back is of N' alone - still one."""
+    last GN block): nodes only, ``topo'`` is None and the read-back is of N' alone - still one.
+
+    ``padded=True``: the capacity-padded form, NO host synchronisation, so a hipGraph capture can record it.  Every result keeps
+    the input's size: ``x'`` [rows, C] and ``kept`` int32 [rows], ``edge_attr'`` [E, De], ``topo'`` over ``rows`` nodes and E edges.
+    The first N' rows / E' edges are the sized form's; behind them ``x'`` and ``edge_attr'`` hold exact +0.0 rows, ``kept`` holds -1,
+    and the slack edges are self-loops spread evenly over the slack rows ``[N', rows)``.  ``graph_ptr'`` ends at N', so the slack rows
+    belong to no graph: a read-out ignores them, a later pooling layer erases them (and its edge filter their loops) again.  The
+    blocks behind the layer run on all ``rows`` / E again - that is the price of the replay."""
     from .topology import GraphTopology
     scores = scores.reshape(-1)
-    new_id, kept, gp_out, counts = native.topk_pool_select(scores.detach(), graph_ptr, ratio)
+    new_id, kept, gp_out, counts = native.topk_pool_select(scores.detach(), graph_ptr, ratio, padded=padded)
+    if padded:  # counts stays on the device; the row launches run over the whole tables (a -1 id gives a +0.0 row)
+        x_out = _TopKNodeRows.apply(x, scores, kept, new_id)
+        if not need_edges:
+            return x_out, None, None, gp_out, kept
+        src, dst, kept_edges, edge_new_id, rowptr = native.topk_pool_filter_edges(topo.src_sorted, topo.dst_sorted, topo.rowptr, new_id,
+                                                                                 kept, counts, padded=True)
+        topo_out = GraphTopology.from_sorted(rowptr, src, dst, x.size(0), topo.status, topo.deferred)
+        e_rows = _TopKEdgeRows.apply(edge_attr, kept_edges, edge_new_id) if edge_attr is not None else None
+        return x_out, e_rows, topo_out, gp_out, kept
     if need_edges:
         src, dst, kept_edges, edge_new_id, rowptr = native.topk_pool_filter_edges(topo.src_sorted, topo.dst_sorted, topo.rowptr, new_id, kept,
                                                                                  counts)

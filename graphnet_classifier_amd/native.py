@@ -153,6 +153,10 @@ _SIGNATURES = {
     "gnc_topk_pool_edge_workspace_ints": (c_int64, [c_int64]),
     "gnc_topk_pool_filter_edges": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gnc_topk_pool_select_padded_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
+    "gnc_topk_pool_filter_edges_padded": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnc_topk_pool_rows_forward_f32": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "gnc_topk_pool_rows_backward_f32": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                                   c_int64, c_void_p, c_void_p]),
@@ -1230,13 +1234,16 @@ def _check_ratio(ratio, who: str) -> float:
     return float(ratio)
 
 
-def topk_pool_select(scores: torch.Tensor, graph_ptr: torch.Tensor, ratio: float):
+def topk_pool_select(scores: torch.Tensor, graph_ptr: torch.Tensor, ratio: float, padded: bool = False):
     """Per graph of ``graph_ptr`` (DEVICE int64 [G + 1], never read on the host), the ``k = min(n, max(1, ceil(ratio n)))`` rows
     with the best ``scores`` [rows] (float32): larger first, ``-0.0 == +0.0``, NaN below ``-inf``, ties by lower row.  Returns
     ``(new_id, kept, graph_ptr_out, counts)``, all on the device and allocated at their upper bounds: ``new_id`` int32 [rows] (-1 =
     dropped), ``kept`` int32 [rows] of which the first N' hold the survivors' old ids in ascending order, ``graph_ptr_out`` int64
     [G + 1], ``counts`` int64 [2] whose first entry is N' (the second is ``topk_pool_filter_edges``'s E').  No host
-    synchronisation here: the caller reads ``counts`` back ONCE per pooling layer and narrows with views."""
+    synchronisation here: the caller reads ``counts`` back ONCE per pooling layer and narrows with views.
+
+    ``padded=True`` (``gnc_topk_pool_select_padded_f32``, the same launches): ``kept[N':]`` holds -1 as well, so every entry of every
+    result is defined and nobody has to read ``counts``."""
     lib = load_library()
     ratio = _check_ratio(ratio, "topk_pool_select")
     _require_cuda(scores, graph_ptr)
@@ -1250,21 +1257,28 @@ def topk_pool_select(scores: torch.Tensor, graph_ptr: torch.Tensor, ratio: float
     kept = torch.empty(rows, dtype=torch.int32, device=dev)
     gp_out = torch.empty(G + 1, dtype=torch.int64, device=dev)
     counts = torch.empty(2, dtype=torch.int64, device=dev)
+    name = "gnc_topk_pool_select_padded_f32" if padded else "gnc_topk_pool_select_f32"
+    fn = getattr(lib, name)
     with torch.cuda.device(dev):
         _check(_launch("topk_pool_select", scores,
-                       lambda: lib.gnc_topk_pool_select_f32(scores.data_ptr(), gp.data_ptr(), G, rows, ratio, new_id.data_ptr(),
-                                                            kept.data_ptr(), gp_out.data_ptr(), counts.data_ptr(), _stream(scores)),
-                       float(rows)), "gnc_topk_pool_select_f32")
+                       lambda: fn(scores.data_ptr(), gp.data_ptr(), G, rows, ratio, new_id.data_ptr(), kept.data_ptr(), gp_out.data_ptr(),
+                                  counts.data_ptr(), _stream(scores)),
+                       float(rows)), name)
     return new_id, kept, gp_out, counts
 
 
 def topk_pool_filter_edges(src_sorted: torch.Tensor, dst_sorted: torch.Tensor, rowptr: torch.Tensor, new_id: torch.Tensor,
-                           kept: torch.Tensor, counts: torch.Tensor):
+                           kept: torch.Tensor, counts: torch.Tensor, padded: bool = False):
     """Stream compaction of a destination-sorted edge list (int32 [E] each, ``rowptr`` int32 [rows + 1]) to the edges whose two
     endpoints ``topk_pool_select`` kept, renumbered; the order is kept, so the result is still destination-sorted.  Returns
     ``(src, dst, kept_edges, edge_new_id, rowptr_out)`` at their upper bounds (E, E, E, E, rows + 1): the first E' entries of the
     first three and the first N' + 1 of ``rowptr_out`` are written, ``edge_new_id`` [E] holds -1 for a dropped edge; ``counts[1]``
-    receives E'.  No host synchronisation here (see ``topk_pool_select``)."""
+    receives E'.  No host synchronisation here (see ``topk_pool_select``).
+
+    ``padded=True`` (``gnc_topk_pool_filter_edges_padded``, the same launches, behind the padded select): all E entries of ``src`` /
+    ``dst`` / ``kept_edges`` and all rows + 1 of ``rowptr_out`` are written - behind E' the evenly spread self-loops of the slack
+    rows ``[N', rows)`` and ``kept_edges = -1``, ``rowptr_out[rows] = E`` - so the results describe a destination-sorted graph of
+    ``rows`` nodes and E edges whatever the counts are."""
     lib = load_library()
     _require_cuda(src_sorted, dst_sorted, rowptr, new_id, kept, counts)
     rows, E = new_id.numel(), src_sorted.numel()
@@ -1281,13 +1295,25 @@ def topk_pool_filter_edges(src_sorted: torch.Tensor, dst_sorted: torch.Tensor, r
     if need < 0:
         raise RuntimeError(f"topk_pool_filter_edges: {E} edges outside the kernel's set")
     ws = torch.empty(max(need, 1), dtype=torch.int32, device=dev)
+    if padded and rows == 0:
+        # no row a slack edge could loop on, so the library would launch nothing: the empty layout, written here.  No edge is
+        # kept (E' = 0, every id -1) and the one row pointer is 0; an edge list over no rows does not exist, so with E > 0 (only
+        # out-of-range endpoints: the source topology's flags are set) ``src`` / ``dst`` are zeros that nobody may index with.
+        for t in (src, dst):
+            t.zero_()
+        for t in (kept_edges, edge_new_id):
+            t.fill_(-1)
+        rowptr_out.zero_()
+        counts[1:].zero_()
+        return src, dst, kept_edges, edge_new_id, rowptr_out
+    name = "gnc_topk_pool_filter_edges_padded" if padded else "gnc_topk_pool_filter_edges"
+    fn = getattr(lib, name)
     with torch.cuda.device(dev):
         _check(_launch("topk_pool_filter_edges", new_id,
-                       lambda: lib.gnc_topk_pool_filter_edges(src_sorted.data_ptr(), dst_sorted.data_ptr(), rowptr.data_ptr(), E, rows,
-                                                              new_id.data_ptr(), kept.data_ptr(), counts.data_ptr(), src.data_ptr(),
-                                                              dst.data_ptr(), kept_edges.data_ptr(), edge_new_id.data_ptr(),
-                                                              rowptr_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(new_id)),
-                       float(E)), "gnc_topk_pool_filter_edges")
+                       lambda: fn(src_sorted.data_ptr(), dst_sorted.data_ptr(), rowptr.data_ptr(), E, rows, new_id.data_ptr(),
+                                  kept.data_ptr(), counts.data_ptr(), src.data_ptr(), dst.data_ptr(), kept_edges.data_ptr(),
+                                  edge_new_id.data_ptr(), rowptr_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(new_id)),
+                       float(E)), name)
     return src, dst, kept_edges, edge_new_id, rowptr_out
 
 

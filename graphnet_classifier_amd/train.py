@@ -265,6 +265,11 @@ class CapturedTrainStep:
             def padded_forward(mod, xx, pp, ee):
                 topo = GraphTopology(ee, xx.size(0), device=dev, validate="deferred")  # never the cache: built in every step
                 self._status = topo.status  # the capture's own flags: every replay rewrites them
+                if pooled and mod.graph_net.pooling:  # padded top-K pooling: the first layer erases the slots and the dummies with
+                    # the rows of no graph; the read-out takes the POOLED graph's rows [0, N') through the device graph_ptr'
+                    y, ptr, _ = mod.graph_net.forward_device(xx, pp, topo, graph_ptr=self._graph_ptr, return_pooling=True,
+                                                             compose_kept=False)
+                    return mod.readout_logits(y, ptr)[0]
                 y = mod.graph_net.forward_device(xx, pp, topo)
                 if pooled:  # graph_ptr = [0, valid_nodes]: slots behind the sample's nodes and the dummies get zero gradient
                     return mod.readout_logits(y, self._graph_ptr)[0]
@@ -789,9 +794,10 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
     # this loop steps one rank's model on its own samples: with a multi-rank process group up, a captured step would
     # record (or, under gloo, host-stage) a collective per sample that nothing here asked for
-    # (a model with top-K pooling reads sizes back in its forward: no capture can record it, every step runs eagerly)
-    from .GNN import uses_node_pooling
-    stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1 and not uses_node_pooling(model))
+    # (a model whose top-K pooling reads sizes back in its forward: no capture can record it, every step runs eagerly; padded
+    # pooling layers under a pooled read-out are captured like an un-pooled model)
+    from .GNN import pooling_prevents_capture
+    stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1 and not pooling_prevents_capture(model))
     stepper.capture_ragged_batches = stepper.capture and capture_ragged_batches
     history = []
     # Belt and braces: the loop runs on a side stream, so that the eager steps in front of a capture never touch the
@@ -838,8 +844,9 @@ class _BatchScorer:
     ``_logits_of`` as they always did."""
 
     def __init__(self, model, dev, capture: bool):
-        from .GNN import CapturedRaggedBatchForward, uses_node_pooling
-        self.model, self.dev, self.capture = model, dev, capture and not uses_node_pooling(model)  # pooling: eager (no capture)
+        from .GNN import CapturedRaggedBatchForward, pooling_prevents_capture
+        # pooling that reads sizes back: eager (no capture)
+        self.model, self.dev, self.capture = model, dev, capture and not pooling_prevents_capture(model)
         self.ragged = _RaggedBatchCaptures(
             model, lambda batch, **capacities: CapturedRaggedBatchForward(model, batch, **capacities),
             _SampleStepper.MAX_PADDED_CAPTURES)

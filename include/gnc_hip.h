@@ -700,6 +700,24 @@ int gnc_topk_pool_rows_backward_f32(const float* dout, int64_t ld_dout, int64_t 
                                     const int32_t* new_id, int64_t rows_in, int64_t C, float* dx, int64_t ld_dx, float* ds,
                                     void* stream);
 
+/* The capacity-padded forms: the same arguments and the same launches, but every output is written over its
+ * whole ALLOCATED length, so that a caller never reads counts back (a hipGraph capture can record the layer).  With N' / E' the
+ * device counts, S_R = rows - N' and S_E = E - E':
+ *   gnc_topk_pool_select_padded_f32    as the select, and kept[N', rows) = -1;
+ *   gnc_topk_pool_filter_edges_padded  as the filter (run behind the padded select), and kept_edges[E', E) = -1; the edge at E' + t
+ *     (0 <= t < S_E) is a self-loop of slack row N' + floor(t S_R / S_E) in src_out and dst_out (still destination-sorted, at most
+ *     ceil(S_E / S_R) loops per slack row); rowptr_out[N' + u] = E' + ceil(u S_E / S_R) for 0 <= u <= S_R, so rowptr_out[rows] = E.
+ *     S_R == 0 with S_E > 0 (only an edge with an endpoint outside [0, rows) can be dropped when every row is kept; the source
+ *     topology's flags are set then): the slack loops go to row rows - 1 and rowptr_out[rows] = E.  rows == 0: nothing is launched.
+ * The row launches then take n_out = rows (nodes) / E (edges): an id of -1 gives an exact +0.0 row, and the backward ignores
+ * gradient rows that no new_id names.  Added without an ABI bump. */
+int gnc_topk_pool_select_padded_f32(const float* scores, const int64_t* graph_ptr, int64_t num_graphs, int64_t rows, double ratio,
+                                    int32_t* new_id, int32_t* kept, int64_t* new_graph_ptr, int64_t* counts, void* stream);
+int gnc_topk_pool_filter_edges_padded(const int32_t* src_sorted, const int32_t* dst_sorted, const int32_t* rowptr, int64_t num_edges,
+                                      int64_t rows, const int32_t* new_id, const int32_t* kept, int64_t* counts, int32_t* src_out,
+                                      int32_t* dst_out, int32_t* kept_edges, int32_t* edge_new_id, int32_t* rowptr_out,
+                                      int32_t* workspace, int64_t workspace_ints, void* stream);
+
 /* ---- K18: mean / max neighbourhood aggregation (csrc/segment_reduce.hip) --------------
  * The node model's aggregation with another reducer than K1's sum, over the same destination-sorted CSR and with K1's argument
  * conventions: out[v, :] reduces src[row(k), :] over the sorted positions k in [rowptr[v], rowptr[v+1]), row(k) = perm[k] or k
