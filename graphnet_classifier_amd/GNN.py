@@ -580,169 +580,125 @@ class GraphNet(nn.Module):
         return out if back == dev else out.to(back)
 
 
-class CapturedForward:
-    """A GraphNet / CombinedModel forward for ONE fixed topology captured into a hipGraph.
+def _has_batchnorm(model: nn.Module) -> bool:
+    """Batch statistics span ALL rows of a launch: the dummy rows of a padded feed would enter them."""
+    return any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules())
 
-    The reference's training and inference loops run one small graph per call (main.py:60,
-    utils/inference.py:59); at ~1000 nodes the ~30 kernel launches of a forward are launch-bound (about 1 ms
-    eager).  For pixel / patch graphs the topology is the same for every image of a given size
-    (optimized.py:42-47), so the whole launch sequence can be recorded once and replayed: new ``x`` / ``pos``
-    are copied into the captured input buffers, one ``hipGraphLaunch`` runs every kernel.  Inference only
-    (no autograd through a replay).
 
-    ``edge_capacity`` given: ANY topology over the same node count (superpixel graphs: a new region adjacency per image,
-    utils/image_to_graph/image_to_graph_superpixel.py:31-66).  The captured buffers hold extra dummy nodes with zero
-    features and ``edge_capacity`` edge slots, the unused tail of which are self-loops of the dummies (at most 8 each, so
-    no destination becomes a hub); the topology build - device flags, no host sync - is part of the graph, so a replay
-    sorts whatever edge list the buffer holds.  Dummy rows only talk to dummies and are dropped from the result, which is
-    therefore the plain forward's, bit for bit.  ``check()`` reads the flags of the last replay (ids outside the graph).
+def _same_topology(a: Tensor, b: Tensor) -> bool:
+    return a is b or (a.shape == b.shape and a.dtype == b.dtype and a.device == b.device and bool(torch.equal(a, b)))
 
-    ``node_capacity`` given as well (a ``CombinedModel`` with ``ragged_readout``): any graph of at most ``node_capacity``
-    nodes and ``edge_capacity`` edges (superpixel graphs: SLIC returns another number of segments per image).  The buffers
-    hold ``node_capacity`` node slots in front of the dummies (and at least the read-out's ``num_nodes`` rows); the slots
-    behind a sample's own nodes are isolated zero-feature nodes, and inside the graph the read-out takes rows
-    ``[0, num_nodes)`` and zeroes those at or behind a device-side count that every call writes in front of the replay -
-    the rule of ``CombinedModel.ragged_readout``.  A pooled ``CombinedModel`` (``readout="mean"`` ...) pools rows
-    ``[0, count)`` instead: its ``graph_ptr`` is the device buffer ``[0, count]`` that holds the count.
-    """
 
-    def __init__(self, model: nn.Module, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int | None = None,
-                 node_capacity: int | None = None):
-        gnet = model.graph_net if isinstance(model, CombinedModel) else model
-        _no_capture_with_pooling(model, "CapturedForward")
-        dev = require_gpu_param(next(model.parameters()), "CapturedForward")
-        self.model, self.device = model, dev
-        self.edge_capacity, self.num_nodes = edge_capacity, int(x.size(0))
-        self.node_capacity = node_capacity
-        pooled = isinstance(model, CombinedModel) and model.pooled  # its read-out takes the graph's rows through a device graph_ptr
-        if node_capacity is not None:
-            if edge_capacity is None:
-                raise ValueError("CapturedForward: node_capacity requires edge_capacity")
-            if not (isinstance(model, CombinedModel) and model.ragged_readout):
-                raise TypeError("CapturedForward(node_capacity=...): a CombinedModel with ragged_readout = True expected")
-            if self.num_nodes > node_capacity:
-                raise ValueError(f"CapturedForward: {self.num_nodes} nodes exceed node_capacity {node_capacity}")
-        if edge_capacity is None:
-            self.x = x.to(device=dev, dtype=torch.float32).clone()
-            self.pos = pos.to(device=dev, dtype=torch.float32).clone()
-            self.topo = get_topology(edge_index, self.x.size(0), dev)  # host sync happens here, outside the capture
+class FixedGraphFeed:
+    """The input buffers of a hipGraph captured for ONE topology: ``x`` / ``pos`` of the sample's shape, its edge list on the
+    device with the topology built from it (the build's host sync happens here, outside the capture), and ``graph_ptr`` = [0, N]
+    (``_whole``) for the pooling layers and a pooled read-out.  A call is two copies."""
 
-            # [0, N], a pooled read-out's (and the pooling layers') graph_ptr.  Kept on the object: the hipGraph records its
-            # ADDRESS, and a buffer that only ``run`` held would go back to the allocator with it - the next small allocation
-            # would then land on the offsets that every later replay reads.
-            whole = self._whole = torch.tensor([0, self.num_nodes], dtype=torch.int64, device=dev) if pooled else None
+    edge_capacity = node_capacity = None
 
-            def run():
-                if pooled and gnet.pooling:  # padded top-K pooling: the read-out takes the POOLED graph's rows [0, N')
-                    y, ptr, _ = gnet.forward_device(self.x, self.pos, self.topo, graph_ptr=whole, return_pooling=True, compose_kept=False)
-                    return model.readout_logits(y, ptr)[0]
-                y = gnet.forward_device(self.x, self.pos, self.topo)
-                if pooled:
-                    return model.readout_logits(y, whole)[0]
-                return model.classifier(y.flatten()) if isinstance(model, CombinedModel) else y
-        else:
-            n, e = self.num_nodes, int(edge_index.size(1))
-            if e > edge_capacity:
-                raise ValueError(f"CapturedForward: {e} edges exceed edge_capacity {edge_capacity}")
-            if model.training and any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
-                # batch statistics span ALL rows: the dummy rows would enter them (eval mode normalises row by row)
-                raise NotImplementedError("CapturedForward(edge_capacity=...): a BatchNorm model must be in eval() mode")
-            dummies = max(1, (edge_capacity + 7) // 8)
-            slots = n if node_capacity is None else node_capacity  # node slots in front of the dummies
-            rows = slots + dummies if node_capacity is None or pooled else max(slots + dummies, model.num_nodes)
-            self.x = torch.zeros(rows, *x.shape[1:], dtype=torch.float32, device=dev)
-            self.pos = torch.zeros(rows, *pos.shape[1:], dtype=torch.float32, device=dev)
-            self._tail = slots + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies
-            self.edge_index = self._tail.repeat(2, 1)
-            self.x[:n].copy_(x)
-            self.pos[:n].copy_(pos)
-            self.edge_index[:, :e].copy_(edge_index)
-            self.topo, self._status = None, None
-            self._range_flag = torch.zeros((), dtype=torch.bool, device=dev)
-            self._filled = n                                                        # rows of x / pos that hold a sample
-            # [0, n]: a pooled read-out's graph_ptr; its second entry is the node count every call writes in front of the replay
-            # (node_capacity form).  ONE persistent buffer read inside the graph: nothing is concatenated in there.
-            self._graph_ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
-            self.valid_nodes = self._graph_ptr[1]
+    def __init__(self, x: Tensor, pos: Tensor, edge_index: Tensor, device):
+        self.x = x.to(device=device, dtype=torch.float32).clone()
+        self.pos = pos.to(device=device, dtype=torch.float32).clone()
+        self.edge_index, self._given = edge_index.to(device), edge_index
+        self.num_nodes = int(x.size(0))
+        self.topo = get_topology(self.edge_index, self.num_nodes, device)
+        self.graph_ptr = self._whole = torch.tensor([0, self.num_nodes], dtype=torch.int64, device=device)
 
-            def run():
-                topo = GraphTopology(self.edge_index, rows, device=dev, validate="deferred")  # never the cache
-                self._status = topo.status  # the capture's own flags: every replay rewrites them
-                if pooled and gnet.pooling:  # padded top-K pooling: the first layer erases the slots and the dummies with the
-                    # rows of no graph, and the read-out takes the POOLED graph's rows [0, N')
-                    y, ptr, _ = gnet.forward_device(self.x, self.pos, topo, graph_ptr=self._graph_ptr, return_pooling=True,
-                                                    compose_kept=False)
-                    return model.readout_logits(y, ptr)[0]
-                y = gnet.forward_device(self.x, self.pos, topo)
-                if pooled:  # rows [0, valid_nodes): the slots behind them and the dummies are outside the graph
-                    return model.readout_logits(y, self._graph_ptr)[0]
-                if node_capacity is not None:
-                    return model.classifier(masked_readout_rows(y, model.num_nodes, self.valid_nodes).flatten())
-                y = y[:n]
-                return model.classifier(y.flatten()) if isinstance(model, CombinedModel) else y
+    def matches(self, sample) -> bool:
+        x, pos, edge_index = sample
+        return x.shape == self.x.shape and pos.shape == self.pos.shape and _same_topology(edge_index, self._given)
 
-        self._capture(run)
+    def __call__(self, x: Tensor, pos: Tensor | None = None, edge_index: Tensor | None = None) -> None:
+        self.x.copy_(x, non_blocking=True)
+        if pos is not None:
+            self.pos.copy_(pos, non_blocking=True)
 
-    def _capture(self, run) -> None:
-        """Warm ``run`` up on a side stream, then record it: ``self.graph`` replays it, ``self.out`` is its result."""
-        dev = self.device
-        with torch.no_grad():
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                for _ in range(2):  # warm-up: kernel attributes, allocator pools, padded-weight cache
-                    run()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = run()
+    def check(self, status: Tensor | None) -> None:
+        pass
 
-    def __call__(self, x: Tensor, pos: Tensor | None = None, edge_index: Tensor | None = None) -> Tensor:
-        if self.edge_capacity is None:
-            self.x.copy_(x, non_blocking=True)
-            if pos is not None:
-                self.pos.copy_(pos, non_blocking=True)
-        else:
-            n = self.num_nodes
-            if self.node_capacity is None:
-                if x.size(0) != n:
-                    raise ValueError(f"CapturedForward: {x.size(0)} nodes, captured for {n}")
-            else:
-                n = self.num_nodes = int(x.size(0))
-                if n > self.node_capacity:
-                    raise ValueError(f"CapturedForward: {n} nodes exceed node_capacity {self.node_capacity}")
-                if edge_index is None or pos is None:
-                    raise ValueError("CapturedForward(node_capacity=...): every call needs x, pos and edge_index")
-                if int(edge_index.size(1)) > self.edge_capacity:
-                    raise ValueError(f"CapturedForward: {int(edge_index.size(1))} edges exceed edge_capacity {self.edge_capacity}")
-                if n < self._filled:  # a smaller graph after a larger one: its slots become isolated zero nodes again
-                    self.x[n:self._filled].zero_()
-                    self.pos[n:self._filled].zero_()
-                self._filled = n
-                self.valid_nodes.fill_(n)
-            self.x[:n].copy_(x, non_blocking=True)
-            if pos is not None:
-                self.pos[:n].copy_(pos, non_blocking=True)
-            if edge_index is not None:
-                e = int(edge_index.size(1))
-                if e > self.edge_capacity:
-                    raise ValueError(f"CapturedForward: {e} edges exceed edge_capacity {self.edge_capacity}")
-                # ids in [n, n + dummies) would pass the topology build's range check but are not nodes of THIS graph
-                if e and not edge_index.is_cuda:
-                    if int(edge_index.max()) >= n or int(edge_index.min()) < 0:
-                        raise IndexError(f"edge_index has node ids outside [0, {n})")
-                elif e:
-                    self._range_flag |= (edge_index >= n).any()
-                self.edge_index[:, :e].copy_(edge_index, non_blocking=True)
-                self.edge_index[:, e:].copy_(self._tail[e:])
-        self.graph.replay()
-        return self.out
 
-    def check(self) -> None:
-        """``edge_capacity`` form: read the device flags of the last replayed topology build (one host sync) and raise the
-        IndexError of models/GNN.py:18-20 for node ids outside the graph (the output of such a replay is NaN)."""
-        status = getattr(self, "_status", None)
-        if status is not None and bool((status.any() | self._range_flag).item()):
+class PaddedGraphFeed:
+    """The fixed input buffers of a hipGraph captured for ANY single graph that fits them (superpixel graphs: a new region adjacency
+    per image, utils/image_to_graph/image_to_graph_superpixel.py:31-66, and with ``node_capacity`` another segment count too), and
+    the copies that fill them.  Pure torch: it runs on any device.
+
+    With ``C = edge_capacity``, ``D = dummies = max(1, ceil(C / 8))`` and ``S`` node slots (``node_capacity``, or the sample's node
+    count when that is None: every graph then has that many nodes): ``x`` / ``pos`` hold ``rows = max(S + D, min_rows)`` rows - a
+    sample's n rows, isolated zero rows up to S, D zero dummy rows that are never written; ``edge_index`` [2, C] holds a sample's
+    edges and, behind them, self-loops of the dummies, spread round-robin (at most 8 each: ONE dummy would be a hub of hundreds of
+    rows that the per-destination kernels walk serially, 0.95 ms per step against 0.6).  Dummies only talk to dummies, so whatever
+    reads rows ``[0, n)`` alone sees the plain graph's result, bit for bit, and the rest gets exact zero gradients.
+    ``graph_ptr`` = [0, n] is a pooled read-out's offsets; ``valid_nodes`` is its second entry, the SAME storage, which a call
+    under ``node_capacity`` rewrites in front of the replay.  The range flag is sticky: a call sets it when a DEVICE edge list
+    names a row at or behind n (ids in ``[n, rows)`` pass the topology build's range check but are not nodes of this graph;
+    reading them here would synchronise), and only ``check`` clears it.  A HOST edge list is checked in the call itself.
+
+    ``keep_missing``: in the ``edge_capacity``-only form a call may pass ``pos=None`` / ``edge_index=None`` and keep the buffer's
+    contents (``CapturedForward``)."""
+
+    def __init__(self, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int, node_capacity: int | None = None, *,
+                 device, min_rows: int = 0, keep_missing: bool = False, who: str = "PaddedGraphFeed"):
+        self.who, self.keep_missing = who, keep_missing
+        self.edge_capacity, self.node_capacity = C, M = int(edge_capacity), node_capacity
+        self.num_nodes = self._filled = n = int(x.size(0))  # of the sample fed last; rows of x / pos that hold a sample
+        self._require_fit(n, int(edge_index.size(1)))
+        self.dummies = dummies = max(1, (C + 7) // 8)
+        slots = n if M is None else M
+        self.rows = max(slots + dummies, min_rows)
+        self.x = torch.zeros(self.rows, *x.shape[1:], dtype=torch.float32, device=device)
+        self.pos = torch.zeros(self.rows, *pos.shape[1:], dtype=torch.float32, device=device)
+        self._tail = slots + torch.arange(C, dtype=torch.int64, device=device) % dummies  # slot k's dummy self-loop
+        self.edge_index = self._tail.repeat(2, 1)
+        self.graph_ptr = torch.tensor([0, n], dtype=torch.int64, device=device)
+        self.valid_nodes = self.graph_ptr[1]
+        self._range_flag = torch.zeros((), dtype=torch.bool, device=device)
+        self.x[:n].copy_(x)
+        self.pos[:n].copy_(pos)
+        self.edge_index[:, :edge_index.size(1)].copy_(edge_index)
+
+    def _nodes_fit(self, n: int) -> bool:
+        return n == self.num_nodes if self.node_capacity is None else n <= self.node_capacity
+
+    def matches(self, sample) -> bool:
+        x, pos, edge_index = sample
+        return (self._nodes_fit(x.size(0)) and x.shape[1:] == self.x.shape[1:] and pos.shape[1:] == self.pos.shape[1:]
+                and edge_index.dim() == 2 and edge_index.size(1) <= self.edge_capacity)
+
+    def _require_fit(self, n: int, e: int) -> None:
+        if not self._nodes_fit(n) or e > self.edge_capacity:
+            nodes = self.num_nodes if self.node_capacity is None else f"at most {self.node_capacity}"
+            raise ValueError(f"{self.who}: a sample with {n} nodes / {e} edges does not fit the captured {nodes} nodes / "
+                             f"at most {self.edge_capacity} edges")
+
+    def __call__(self, x: Tensor, pos: Tensor | None, edge_index: Tensor | None) -> None:
+        if (pos is None or edge_index is None) and not (self.keep_missing and self.node_capacity is None):
+            form = "" if self.node_capacity is None else "(node_capacity=...)"
+            raise ValueError(f"{self.who}{form}: every call needs x, pos and edge_index")
+        n, e = int(x.size(0)), 0 if edge_index is None else int(edge_index.size(1))
+        self._require_fit(n, e)
+        if self.node_capacity is not None:
+            if n < self._filled:  # a smaller graph after a larger one: its slots become isolated zero nodes again
+                self.x[n:self._filled].zero_()
+                self.pos[n:self._filled].zero_()
+            self.num_nodes = self._filled = n
+            self.valid_nodes.fill_(n)
+        self.x[:n].copy_(x, non_blocking=True)
+        if pos is not None:
+            self.pos[:n].copy_(pos, non_blocking=True)
+        if edge_index is None:
+            return
+        if e and not edge_index.is_cuda:
+            if int(edge_index.max()) >= n or int(edge_index.min()) < 0:
+                raise IndexError(f"edge_index has node ids outside [0, {n})")
+        elif e:
+            self._range_flag |= (edge_index >= n).any()
+        self.edge_index[:, :e].copy_(edge_index, non_blocking=True)
+        self.edge_index[:, e:].copy_(self._tail[e:])
+
+    def check(self, status: Tensor | None) -> None:
+        """One host sync for the sticky flag and ``status`` (the flags of the LAST replayed topology build); clears the sticky
+        flag and raises the IndexError of models/GNN.py:18-20 when either is set (the output of such a replay is NaN)."""
+        if bool((self._range_flag if status is None else self._range_flag | status.any()).item()):
             self._range_flag.zero_()
             raise IndexError(f"edge_index has node ids outside [0, {self.num_nodes})")
 
@@ -813,50 +769,150 @@ class RaggedBatchFeed:
             raise IndexError(f"edge_index has node ids outside their graph's node range (batch of {self.num_nodes} nodes)")
 
 
-def _has_batchnorm(model: nn.Module) -> bool:
-    return any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules())
+def graph_logits(mod: nn.Module, feed):
+    """``(logits, status)`` of the single graph in a ``FixedGraphFeed`` or ``PaddedGraphFeed``, for ``mod`` a ``CombinedModel`` or a
+    bare ``GraphNet`` (whose "logits" are its node rows).  Over a padded feed the topology is built HERE, from whatever edge list
+    the buffer holds (deferred validation: device flags, no host sync, never the cache), so it is part of whatever records this
+    call; ``status`` are that build's flags, for the feed's ``check`` (None over a fixed feed, whose topology was validated)."""
+    if feed.edge_capacity is None:
+        topo, status = feed.topo, None
+    else:
+        topo = GraphTopology(feed.edge_index, feed.rows, device=feed.x.device, validate="deferred")
+        status = topo.status
+    gnet = getattr(mod, "graph_net", mod)
+    pooled = bool(getattr(mod, "pooled", False))  # a read-out that takes the graph's rows through a device graph_ptr
+    if pooled and gnet.pooling:  # padded top-K pooling: the first layer erases the slots and the dummies with the rows of no
+        # graph, and the read-out takes the POOLED graph's rows [0, N')
+        y, ptr, _ = gnet.forward_device(feed.x, feed.pos, topo, graph_ptr=feed.graph_ptr, return_pooling=True, compose_kept=False)
+        return mod.readout_logits(y, ptr)[0], status
+    y = gnet.forward_device(feed.x, feed.pos, topo)
+    if pooled:  # rows [0, valid_nodes): the slots behind them and the dummies are outside the graph
+        return mod.readout_logits(y, feed.graph_ptr)[0], status
+    if feed.node_capacity is not None:
+        return mod.classifier(masked_readout_rows(y, mod.num_nodes, feed.valid_nodes).flatten()), status
+    y = y[:feed.num_nodes]
+    return (y if gnet is mod else mod.classifier(y.flatten())), status
+
+
+def ragged_batch_logits(mod: nn.Module, feed: RaggedBatchFeed):
+    """``(logits [G, classes], status)`` of the mini-batch in a ``RaggedBatchFeed``: ``graph_logits``' padded form for G graphs."""
+    topo = GraphTopology(feed.edge_index, feed.rows, device=feed.x.device, validate="deferred")
+    return mod.forward_batched_device(feed.x, feed.pos, topo, graph_ptr=feed.graph_ptr), topo.status
+
+
+def flatten_readout_rows(model: nn.Module, node_capacity: int | None, pooled: bool) -> int:
+    """``min_rows`` of a ``PaddedGraphFeed`` for ``model``: the flatten read-out of the ``node_capacity`` form takes rows
+    ``[0, model.num_nodes)`` whatever the capacity is."""
+    return int(model.num_nodes) if node_capacity is not None and not pooled and hasattr(model, "num_nodes") else 0
+
+
+class _Captured:
+    """A feed, a closure over the feed's buffers, and the hipGraph that recorded the closure: what every capture class is.
+    ``matches`` and ``check`` are the feed's, and so is every attribute the capture does not set itself: ``x`` / ``pos`` /
+    ``edge_index`` (the very tensors the graph reads), ``num_nodes``, ``valid_nodes``, the capacities, ``num_graphs``."""
+
+    def __getattr__(self, name):
+        if name == "feed":
+            raise AttributeError(name)
+        return getattr(self.feed, name)
+
+    def _record(self, device, fn, warmups: int, warm=None, capture_error_mode: str = "global"):
+        """Runs ``warm`` (default: ``fn``) ``warmups`` times on a side stream - kernel attributes, allocator pools, lazily built CSR
+        forms - then records ``fn`` into ``self.graph`` and returns what the recorded call returned.
+
+        **Who keeps a recorded buffer alive.**  A hipGraph records ADDRESSES.  A tensor that ``fn`` reads and that was allocated
+        outside the recording must therefore live as long as the graph does, or its memory goes back to the allocator, the next
+        small allocation lands on it, and every later replay reads those bytes.  The rule: the capture object owns the closure
+        it recorded (``self._recorded``), and through it everything the closure holds - the feed, the model, a caller's
+        ``forward=`` and whatever THAT closes over.  No caller and no subclass has to keep anything alive by hand.  (Tensors
+        allocated inside the recording live in the graph's own pool.)"""
+        self._recorded = fn
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for _ in range(warmups):
+                (warm or fn)()
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
+            return fn()
+
+    def matches(self, *sample) -> bool:
+        return self.feed.matches(*sample)
+
+    def check(self) -> None:
+        """One host sync: the feed's sticky flag and the flags of the last replayed topology build; raises the IndexError of
+        models/GNN.py:18-20 for node ids outside the graph."""
+        self.feed.check(self._status)
+
+
+class CapturedForward(_Captured):
+    """A GraphNet / CombinedModel forward captured into a hipGraph.  Inference only (no autograd through a replay).
+
+    The reference's training and inference loops run one small graph per call (main.py:60, utils/inference.py:59); at ~1000 nodes
+    the ~30 kernel launches of a forward are launch-bound (about 1 ms eager).  A call copies its arguments into the feed's
+    buffers, one ``hipGraphLaunch`` runs every kernel, and ``out`` is the result buffer (rewritten by the next call).
+
+    The feed decides what a call may bring: ONE topology (``FixedGraphFeed``: pixel / patch graphs, the same edge list for every
+    image of a size, optimized.py:42-47; the edge list of a call is not read); with ``edge_capacity``, ANY edge list over the
+    sample's node count; with ``node_capacity`` as well, for a ``CombinedModel`` with ``ragged_readout``, any graph that fits both
+    (``PaddedGraphFeed``).  Over a padded feed the read-out follows ``graph_logits``: the flatten read-out takes rows
+    ``[0, num_nodes)`` and zeroes those at or behind the device count ``valid_nodes`` - the rule of
+    ``CombinedModel.ragged_readout`` - and a pooled one (``readout="mean"`` ...) pools rows ``[0, valid_nodes)``."""
+
+    def __init__(self, model: nn.Module, x: Tensor, pos: Tensor, edge_index: Tensor, edge_capacity: int | None = None,
+                 node_capacity: int | None = None):
+        who = "CapturedForward"
+        _no_capture_with_pooling(model, who)
+        dev = require_gpu_param(next(model.parameters()), who)
+        combined = isinstance(model, CombinedModel)
+        if node_capacity is not None:
+            if edge_capacity is None:
+                raise ValueError(f"{who}: node_capacity requires edge_capacity")
+            if not (combined and model.ragged_readout):
+                raise TypeError(f"{who}(node_capacity=...): a CombinedModel with ragged_readout = True expected")
+        if edge_capacity is None:
+            feed = FixedGraphFeed(x, pos, edge_index, dev)
+        else:
+            if model.training and _has_batchnorm(model):  # eval mode normalises row by row
+                raise NotImplementedError(f"{who}(edge_capacity=...): a BatchNorm model must be in eval() mode")
+            feed = PaddedGraphFeed(x, pos, edge_index, edge_capacity, node_capacity, device=dev, keep_missing=True, who=who,
+                                   min_rows=flatten_readout_rows(model, node_capacity, combined and model.pooled))
+        self._init(model, feed, graph_logits)
+
+    def _init(self, model: nn.Module, feed, logits) -> None:
+        self.model, self.feed, self.device = model, feed, feed.x.device
+        with torch.no_grad():
+            self.out, self._status = self._record(self.device, lambda: logits(model, feed), 2)
+
+    def __call__(self, x: Tensor, pos: Tensor | None = None, edge_index: Tensor | None = None) -> Tensor:
+        self.feed(x, pos, edge_index)
+        self.graph.replay()
+        return self.out
 
 
 class CapturedRaggedBatchForward(CapturedForward):
     """``CombinedModel.forward_batched(graph_ptr=...)`` for ANY mini-batch of G graphs with at most ``node_capacity`` nodes and
-    ``edge_capacity`` edges in all, captured into a hipGraph: ``CapturedForward``'s padded form extended to G graphs.  A call is
-    the feed launch (``RaggedBatchFeed``) and the replay; inside the graph run the topology build over the padded buffers
-    (deferred validation: device flags, no host sync), ``GraphNet.forward_device`` and the batched read-out with the DEVICE
-    ``graph_ptr``.  Slack and dummy rows only talk to dummies and belong to no graph, so the logits [G, classes] are those of
-    the eager call.  G is fixed per capture; ``matches(batch)`` says whether a batch fits, a call with one that does not raises
-    ValueError.  ``check()``: one host sync, raises IndexError when an edge list fed since the last check left its graph."""
+    ``edge_capacity`` edges in all: ``CapturedForward`` over a ``RaggedBatchFeed`` and ``ragged_batch_logits``.  A call is the feed
+    launch and the replay.  Slack and dummy rows only talk to dummies and belong to no graph, so the logits [G, classes] are those
+    of the eager call.  G is fixed per capture; a call with a batch that does not ``matches`` raises ValueError."""
 
     def __init__(self, model: nn.Module, batch, edge_capacity: int, node_capacity: int):
+        who = "CapturedRaggedBatchForward"
         if not isinstance(model, CombinedModel):
-            raise TypeError("CapturedRaggedBatchForward: a CombinedModel expected")
-        _no_capture_with_pooling(model, "CapturedRaggedBatchForward")
-        dev = require_gpu_param(next(model.parameters()), "CapturedRaggedBatchForward")
-        if model.training and _has_batchnorm(model):
-            # batch statistics span ALL rows: the dummy rows would enter them (eval mode normalises row by row)
-            raise NotImplementedError("CapturedRaggedBatchForward: a BatchNorm model must be in eval() mode")
-        self.model, self.device = model, dev
-        self.feed = RaggedBatchFeed(batch, edge_capacity, node_capacity, dev, with_labels=False, who="CapturedRaggedBatchForward")
-        self.edge_capacity, self.node_capacity, self.num_graphs = self.feed.edge_capacity, self.feed.node_capacity, self.feed.num_graphs
-        self._status = None
-        self.feed(batch)
-        feed = self.feed
-
-        def run():
-            topo = GraphTopology(feed.edge_index, feed.rows, device=dev, validate="deferred")  # never the cache
-            self._status = topo.status  # the capture's own flags: every replay rewrites them
-            return model.forward_batched_device(feed.x, feed.pos, topo, graph_ptr=feed.graph_ptr)
-        self._capture(run)
-
-    def matches(self, batch) -> bool:
-        return self.feed.matches(batch)
+            raise TypeError(f"{who}: a CombinedModel expected")
+        _no_capture_with_pooling(model, who)
+        dev = require_gpu_param(next(model.parameters()), who)
+        if model.training and _has_batchnorm(model):  # eval mode normalises row by row
+            raise NotImplementedError(f"{who}: a BatchNorm model must be in eval() mode")
+        feed = RaggedBatchFeed(batch, edge_capacity, node_capacity, dev, with_labels=False, who=who)
+        feed(batch)
+        self._init(model, feed, ragged_batch_logits)
 
     def __call__(self, batch) -> Tensor:
         self.feed(batch)
         self.graph.replay()
         return self.out
-
-    def check(self) -> None:
-        self.feed.check(self._status)
 
 
 # --------------------------------------------------------------------------- a8 read-out

@@ -36,6 +36,9 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import native
+from .GNN import (CapturedRaggedBatchForward, CombinedModel, FixedGraphFeed, PaddedGraphFeed, RaggedBatchFeed, _Captured,
+                  _has_batchnorm, _no_capture_with_pooling, _same_topology, flatten_readout_rows, graph_logits,
+                  pooling_prevents_capture, ragged_batch_logits)
 from .MLP import require_gpu_param
 from .sharding import FlatGradAllReduce
 from .synthetic import GraphBatch
@@ -124,10 +127,6 @@ class FusedAdam:
             dst.copy_(src)
 
 
-def _same_topology(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return a is b or (a.shape == b.shape and a.dtype == b.dtype and a.device == b.device and bool(torch.equal(a, b)))
-
-
 def padded_capacity(needed: int, current: int = 0, quantum: int = 256) -> int:
     """Capacity of a padded capture for ``needed`` edges (or nodes): ``current`` while that still fits, otherwise half as
     much again as needed, rounded up to ``quantum`` - room to spare, so that a data set whose sizes vary around a typical
@@ -144,21 +143,21 @@ def _world(group=None) -> int:
 
 
 class _Through(nn.Module):
-    """``functional_call`` target: runs ``fn(model, *args)`` with the model's parameters swapped for the given ones."""
+    """``functional_call`` target: runs ``fn(model)`` with the model's parameters swapped for the given ones."""
 
     def __init__(self, model: nn.Module, fn):
         super().__init__()
         self.model, self.fn = model, fn
 
-    def forward(self, *args):
-        return self.fn(self.model, *args)
+    def forward(self):
+        return self.fn(self.model)
 
 
-class CapturedTrainStep:
-    """One training step (utils/train_model.py:37-42: forward, CE loss, zero_grad, backward, Adam) for ONE fixed
-    topology, captured into a hipGraph and replayed per sample.  The loss of every replay is added to ``loss_sum``
-    (device float64) inside the graph.  Warm-up steps run before the capture; parameters, optimizer state, module
-    buffers and the loss accumulator are restored afterwards, so constructing this object does not train.
+class CapturedTrainStep(_Captured):
+    """One training step (utils/train_model.py:37-42: forward, CE loss, zero_grad, backward, Adam) captured into a hipGraph and
+    replayed per sample.  The loss of every replay is added to ``loss_sum`` (device float64) inside the graph.  Warm-up steps run
+    before the capture; parameters, optimizer state, module buffers and the loss accumulator are restored afterwards, so
+    constructing this object does not train.
 
     **Safe whatever the caller ran before.**  A parameter's ``AccumulateGrad`` node remembers the stream that was
     current when the node was created, and the node lives as long as ANY autograd graph that reached the parameter
@@ -172,122 +171,55 @@ class CapturedTrainStep:
     autograd nodes are born on the warm-up / capture stream and die with each step's graph, and hands their gradients
     to the reducer's pack.  Nothing of the caller's autograd history is reachable from the capture.
 
-    ``forward(model, x, pos, edge_index) -> logits`` replaces the default ``model((x, pos, edge_index))`` (a batched
-    read-out, for instance); ``loss_scale`` multiplies the loss (``1 / global graph count`` of a sharded batch).
-    With a process group of more than one rank the graph holds forward + backward + gradient pack, and every call
-    issues the ONE all-reduce and the fused Adam launch directly after the replay.
+    The feed decides what a call may bring (``matches``): ONE topology (``GNN.FixedGraphFeed``); with ``edge_capacity=C``, ANY edge
+    list of at most C edges over the sample's node count; with ``node_capacity=M`` as well, for a ``CombinedModel`` with
+    ``ragged_readout``, ANY graph of at most M nodes and C edges (``GNN.PaddedGraphFeed``; logits by ``GNN.graph_logits``; not with
+    BatchNorm layers, whose statistics the dummy rows would enter).
 
-    ``edge_capacity=C``: the step is captured for ANY edge list of at most C edges over the sample's node count (a new
-    topology per sample: superpixel graphs) - see the comment in ``__init__``.  A custom ``forward`` then receives the PADDED
-    buffers (``x`` / ``pos`` with the dummy rows behind the first ``num_nodes``, ``edge_index`` [2, C]); it must build its
-    topology from them in every call (``GraphTopology(..., validate="deferred")``, never the cache) and read out the first
-    ``num_nodes`` rows only.  ``check()`` raises the IndexError of a replayed edge list with ids outside the graph.
-
-    ``node_capacity=M`` with it: ANY graph of at most M nodes and C edges (superpixel graphs: SLIC hands out another number
-    of segments per image), for a ``CombinedModel`` with ``ragged_readout`` set.  The buffers hold M node slots in front of
-    the dummies (and at least the read-out's ``num_nodes`` rows); slots behind a sample's own nodes are isolated zero nodes,
-    and the captured read-out takes rows ``[0, num_nodes)`` and zeroes those at or behind the device count ``valid_nodes``
-    that every call writes in front of the replay (``GNN.masked_readout_rows``), so unused rows contribute exact zeros to
-    the logits and to every gradient, as the dummies do.  A pooled ``CombinedModel`` (``readout="mean"`` ...) pools rows
-    ``[0, valid_nodes)`` instead, through ``readout_logits`` with the device buffer ``[0, valid_nodes]`` as ``graph_ptr``.  A
-    custom ``forward`` reads ``valid_nodes`` itself."""
+    ``forward(model, x, pos, edge_index) -> logits`` replaces the default (a batched read-out, for instance) and receives the
+    feed's buffers.  Over a padded feed it must build its topology from them in every call
+    (a ``GraphTopology`` with deferred validation, never the cache), read out the first ``num_nodes`` rows only, and read
+    ``valid_nodes`` itself; ``check()`` then sees the feed's flag alone.  ``loss_scale`` multiplies the loss
+    (``1 / global graph count`` of a sharded batch).  With a process group of more than one rank the graph holds forward +
+    backward + gradient pack, and every call issues the ONE all-reduce and the fused Adam launch directly after the replay."""
 
     def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, sample, label, loss_sum: torch.Tensor, *,
                  forward=None, loss_scale: float = 1.0, capture_error_mode: str = "global", edge_capacity: int | None = None,
                  node_capacity: int | None = None):
+        who = "CapturedTrainStep"
         x, pos, edge_index = sample
-        from .GNN import _no_capture_with_pooling
-        _no_capture_with_pooling(model, "CapturedTrainStep")
-        dev = require_gpu_param(next(model.parameters()), "CapturedTrainStep")
-        fp = optimizer.fp
-        self.optimizer = optimizer
-        self.edge_index_host = edge_index
-        self.edge_capacity = edge_capacity
-        self.node_capacity = node_capacity
-        self.num_nodes = int(x.size(0))
+        _no_capture_with_pooling(model, who)
+        dev = require_gpu_param(next(model.parameters()), who)
         if node_capacity is not None:
             if edge_capacity is None:
-                raise ValueError("CapturedTrainStep: node_capacity requires edge_capacity")
+                raise ValueError(f"{who}: node_capacity requires edge_capacity")
             if forward is None and not getattr(model, "ragged_readout", False):
-                raise TypeError("CapturedTrainStep(node_capacity=...): a CombinedModel with ragged_readout = True (or forward=) expected")
-            if self.num_nodes > node_capacity:
-                raise ValueError(f"CapturedTrainStep: {self.num_nodes} nodes exceed node_capacity {node_capacity}")
-        self.label = torch.as_tensor(label).to(dev).clone()
-        self.loss_sum = loss_sum
-        self.collective_outside = _world(fp.reducer.group) > 1
-        pooled = forward is None and bool(getattr(model, "pooled", False))  # a CombinedModel with a pooling read-out (K17)
-        from .GNN import masked_readout_rows
-        from .topology import GraphTopology, get_topology
+                raise TypeError(f"{who}(node_capacity=...): a CombinedModel with ragged_readout = True (or forward=) expected")
         if edge_capacity is None:
-            self.x = x.to(device=dev, dtype=torch.float32).clone()
-            self.pos = pos.to(device=dev, dtype=torch.float32).clone()
-            self.edge_index = edge_index.to(dev)
-            # the build's host sync happens here, outside the capture; the reference keeps the CSR arrays alive for the graph
-            self.topo = get_topology(self.edge_index, self.x.size(0), dev)
-            fwd = forward if forward is not None else (lambda mod, xx, pp, ee: mod((xx, pp, ee)))
+            feed = FixedGraphFeed(x, pos, edge_index, dev)
+            logits = lambda mod: (mod((feed.x, feed.pos, feed.edge_index)), None)
         else:
-            # ANY topology over the same node count (the reference's superpixel graphs: a new region adjacency per image,
-            # utils/image_to_graph/image_to_graph_superpixel.py:31-66, one graph per optimizer step, main.py:60): the captured
-            # buffers hold extra DUMMY nodes with zero features and ``edge_capacity`` edges, the unused tail of which are
-            # self-loops of the dummies (spread round-robin, at most 8 each: ONE dummy would be a hub of hundreds of rows
-            # that the per-destination kernels - K1, the topology build's in-destination ranking - walk serially: 0.95 ms
-            # per step against 0.6).  Those rows only ever talk to dummies, whose outputs the read-out never sees, so
-            # they contribute exact zeros to the logits and to every gradient; the topology build (device flags, no host
-            # sync) is PART of the captured step, so a replay sorts whatever edge list the buffer holds.
-            n, e = self.num_nodes, int(edge_index.size(1))
-            if e > edge_capacity:
-                raise ValueError(f"CapturedTrainStep: {e} edges exceed edge_capacity {edge_capacity}")
-            if any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
-                # batch statistics span ALL rows: the dummy rows would enter them (LayerNorm is per row and unaffected)
-                raise NotImplementedError("CapturedTrainStep(edge_capacity=...): not with BatchNorm layers (norm_type='BatchNorm1d')")
+            if _has_batchnorm(model):  # LayerNorm is per row and unaffected
+                raise NotImplementedError(f"{who}(edge_capacity=...): not with BatchNorm layers (norm_type='BatchNorm1d')")
             if forward is None and not (hasattr(model, "graph_net") and hasattr(model, "classifier")):
-                raise TypeError("CapturedTrainStep(edge_capacity=...): pass forward= for a module that is not a CombinedModel")
-            dummies = max(1, (edge_capacity + 7) // 8)
-            slots = n if node_capacity is None else node_capacity  # node slots in front of the dummies
-            rows = slots + dummies
-            if node_capacity is not None and hasattr(model, "num_nodes") and not pooled:
-                rows = max(rows, int(model.num_nodes))  # the flatten read-out takes rows [0, num_nodes)
-            self.x = torch.zeros(rows, *x.shape[1:], dtype=torch.float32, device=dev)
-            self.pos = torch.zeros(rows, *pos.shape[1:], dtype=torch.float32, device=dev)
-            self._tail = slots + torch.arange(edge_capacity, dtype=torch.int64, device=dev) % dummies  # slot k's dummy self-loop
-            self.edge_index = self._tail.repeat(2, 1)
-            self.x[:n].copy_(x)
-            self.pos[:n].copy_(pos)
-            self.edge_index[:, :e].copy_(edge_index)
-            self.topo, self._status = None, None
-            self._range_flag = torch.zeros((), dtype=torch.bool, device=dev)
-            self._filled = n                                                        # rows of x / pos that hold a sample
-            # [0, n]: a pooled read-out's graph_ptr; its second entry is the node count every call writes in front of the replay
-            # (node_capacity form).  ONE persistent buffer read inside the graph: nothing is concatenated in there.
-            self._graph_ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
-            self.valid_nodes = self._graph_ptr[1]
+                raise TypeError(f"{who}(edge_capacity=...): pass forward= for a module that is not a CombinedModel")
+            pooled = forward is None and bool(getattr(model, "pooled", False))
+            feed = PaddedGraphFeed(x, pos, edge_index, edge_capacity, node_capacity, device=dev, who=who,
+                                   min_rows=flatten_readout_rows(model, node_capacity, pooled))
+            logits = lambda mod: graph_logits(mod, feed)
+        if forward is not None:
+            logits = lambda mod: (forward(mod, feed.x, feed.pos, feed.edge_index), None)
+        self._init(model, optimizer, criterion, feed, torch.as_tensor(label).to(dev).clone(), logits, loss_sum, loss_scale,
+                   capture_error_mode)
 
-            def padded_forward(mod, xx, pp, ee):
-                topo = GraphTopology(ee, xx.size(0), device=dev, validate="deferred")  # never the cache: built in every step
-                self._status = topo.status  # the capture's own flags: every replay rewrites them
-                if pooled and mod.graph_net.pooling:  # padded top-K pooling: the first layer erases the slots and the dummies with
-                    # the rows of no graph; the read-out takes the POOLED graph's rows [0, N') through the device graph_ptr'
-                    y, ptr, _ = mod.graph_net.forward_device(xx, pp, topo, graph_ptr=self._graph_ptr, return_pooling=True,
-                                                             compose_kept=False)
-                    return mod.readout_logits(y, ptr)[0]
-                y = mod.graph_net.forward_device(xx, pp, topo)
-                if pooled:  # graph_ptr = [0, valid_nodes]: slots behind the sample's nodes and the dummies get zero gradient
-                    return mod.readout_logits(y, self._graph_ptr)[0]
-                if node_capacity is not None:
-                    return mod.classifier(masked_readout_rows(y, mod.num_nodes, self.valid_nodes).flatten())
-                return mod.classifier(y[:n].flatten())
-            fwd = forward if forward is not None else padded_forward
-        self._capture(model, criterion, fwd, loss_scale, capture_error_mode)
-
-    def _capture(self, model: nn.Module, criterion, fwd, loss_scale: float, capture_error_mode: str) -> None:
-        """The capture itself, over the input buffers ``self.x`` / ``self.pos`` / ``self.edge_index`` / ``self.label`` that the
-        constructor prepared: private leaf aliases, warm-up on a side stream, the recording, and the restore of everything the
-        warm-up and the recording stepped (see the class docstring)."""
-        optimizer = self.optimizer
+    def _init(self, model: nn.Module, optimizer: FusedAdam, criterion, feed, label: torch.Tensor, logits, loss_sum: torch.Tensor,
+              loss_scale: float, capture_error_mode: str) -> None:
+        """The capture itself, over ``feed``'s buffers and the ``label`` buffer: ``logits(mod) -> (logits, status)`` through private
+        leaf aliases, warm-up, the recording, and the restore of everything they stepped (see the class docstring)."""
+        self.feed, self.label, self.optimizer, self.loss_sum = feed, label, optimizer, loss_sum
         fp = optimizer.fp
-        dev = fp.flat.device
-        through = _Through(model, fwd)
-        # private leaves over the parameters' storage (the flat buffer): see the class docstring
+        self.collective_outside = _world(fp.reducer.group) > 1
+        through = _Through(model, logits)
         wanted = dict(zip(fp.names, range(len(fp.names))))
         alias, self._leaves = {}, [None] * len(fp.names)
         for name, p in model.named_parameters():
@@ -298,57 +230,45 @@ class CapturedTrainStep:
             alias["model." + name] = leaf
         if any(l is None for l in self._leaves):
             raise RuntimeError("CapturedTrainStep: the optimizer's FlatParameters were built over another module")
-        leaves = self._leaves
+        leaves, outside = self._leaves, self.collective_outside
 
-        def one_step():
-            logits = torch.func.functional_call(through, alias, (self.x, self.pos, self.edge_index))
-            loss = criterion(logits, self.label)
+        def one_step():  # closes over no ``self``: the object that keeps it (``_record``) must not become a reference cycle
+            out, status = torch.func.functional_call(through, alias, ())
+            loss = criterion(out, label)
             if loss_scale != 1.0:
                 loss = loss * loss_scale
             for leaf in leaves:                                                        # utils/train_model.py:40
                 leaf.grad = None
             loss.backward()                                                            # :41
             grads = [leaf.grad for leaf in leaves]
-            if self.collective_outside:
+            if outside:
                 fp.reducer.pack(grads)
             else:
                 optimizer.step(grads=grads)                                            # :42 (pack + fused Adam)
-            self.loss_sum.add_(loss.detach().double())
+            loss_sum.add_(loss.detach().double())
+            return status
+
+        def warm():
+            one_step()
+            if outside:
+                self._finish()
+            for leaf in leaves:  # the recording starts without gradients
+                leaf.grad = None
 
         snap = optimizer.state_snapshot()
         buffers = [(b, b.clone()) for b in model.buffers()]  # BatchNorm statistics must not absorb the warm-up either
-        keep = self.loss_sum.clone()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):  # kernel attributes, allocator pools, lazily built source-sorted CSR
-                one_step()
-                if self.collective_outside:
-                    self._finish()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for leaf in leaves:
-            leaf.grad = None
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
-            one_step()
+        keep = loss_sum.clone()
+        self._status = self._record(fp.flat.device, one_step, 3, warm, capture_error_mode)
         optimizer.state_restore(snap)
         with torch.no_grad():
             for b, saved in buffers:
                 b.copy_(saved)
-        self.loss_sum.copy_(keep)
+        loss_sum.copy_(keep)
 
     def _finish(self) -> None:
         """Multi-rank tail of a step: the ONE collective over the packed flat buffer, then the fused Adam launch."""
         self.optimizer.fp.reducer.allreduce()
         self.optimizer.step(reduce=False)
-
-    def matches(self, sample) -> bool:
-        x, pos, edge_index = sample
-        if self.edge_capacity is not None:
-            nodes_fit = x.size(0) == self.num_nodes if self.node_capacity is None else x.size(0) <= self.node_capacity
-            return (nodes_fit and x.shape[1:] == self.x.shape[1:] and pos.shape[1:] == self.pos.shape[1:]
-                    and edge_index.dim() == 2 and edge_index.size(1) <= self.edge_capacity)
-        return x.shape == self.x.shape and pos.shape == self.pos.shape and _same_topology(edge_index, self.edge_index_host)
 
     def replay(self) -> None:
         """The step on whatever the captured input buffers hold (``self.x`` / ``self.pos`` / ``self.label``)."""
@@ -357,135 +277,75 @@ class CapturedTrainStep:
             self._finish()
 
     def __call__(self, sample, label) -> None:
-        x, pos, edge_index = sample
-        if self.edge_capacity is None:
-            self.x.copy_(x, non_blocking=True)
-            self.pos.copy_(pos, non_blocking=True)
-        else:
-            n, e = self.num_nodes, int(edge_index.size(1))
-            if self.node_capacity is not None:
-                n = int(x.size(0))
-                if n > self.node_capacity or e > self.edge_capacity:
-                    raise ValueError(f"CapturedTrainStep: sample with {n} nodes / {e} edges does not fit the captured "
-                                     f"{self.node_capacity} nodes / {self.edge_capacity} edges")
-                self.num_nodes = n
-                if n < self._filled:  # a smaller graph after a larger one: its slots become isolated zero nodes again
-                    self.x[n:self._filled].zero_()
-                    self.pos[n:self._filled].zero_()
-                self._filled = n
-                self.valid_nodes.fill_(n)
-            if x.size(0) != n or e > self.edge_capacity:
-                raise ValueError(f"CapturedTrainStep: sample with {x.size(0)} nodes / {e} edges does not fit the captured "
-                                 f"{n} nodes / {self.edge_capacity} edges")
-            # ids in [n, n + dummies) would pass the topology build's range check but are not nodes of THIS graph
-            if e and not edge_index.is_cuda:
-                if int(edge_index.max()) >= n or int(edge_index.min()) < 0:  # host tensor (the loader's): checked here, at once
-                    raise IndexError(f"edge_index has node ids outside [0, {n})")
-            elif e:
-                self._range_flag |= (edge_index >= n).any()  # device tensor: no sync, read by check()
-            self.x[:n].copy_(x, non_blocking=True)
-            self.pos[:n].copy_(pos, non_blocking=True)
-            self.edge_index[:, :e].copy_(edge_index, non_blocking=True)
-            self.edge_index[:, e:].copy_(self._tail[e:])  # the tail: self-loops of the dummy nodes
+        self.feed(*sample)
         self.label.copy_(torch.as_tensor(label), non_blocking=True)
         self.replay()
-
-    def check(self) -> None:
-        """Padded form: read the device flags of the LAST replayed topology build (one host sync) and raise the IndexError the
-        reference's scatter raises for node ids outside the graph (models/GNN.py:18-20)."""
-        status = getattr(self, "_status", None)
-        if status is not None and bool((status.any() | self._range_flag).item()):
-            self._range_flag.zero_()
-            raise IndexError(f"edge_index has node ids outside [0, {self.num_nodes})")
 
 
 class CapturedRaggedBatchStep(CapturedTrainStep):
     """One training step on ANY mini-batch of G graphs with at most ``node_capacity`` nodes and ``edge_capacity`` edges in all
-    (superpixel batches: a new region adjacency and new node counts every batch), captured once and replayed: the
-    ``node_capacity`` form of ``CapturedTrainStep`` extended to G graphs, on the same capture machinery.
-
-    A call is ONE feed launch (``GNN.RaggedBatchFeed``: x, pos, the edge list with its dummy tail, ``graph_ptr`` and the labels
-    go into the captured buffers; the host offsets and labels travel in the kernel arguments) and the replay.  Inside the
-    graph, in order: the topology build over the padded buffers (deferred validation: device flags, no host sync),
-    ``GraphNet.forward_device``, the batched read-out with the DEVICE ``graph_ptr``, mean cross-entropy over the G graphs,
-    backward, the fused Adam, and the add into ``loss_sum``.  Slack rows ``[N, node_capacity)`` belong to no graph and the
-    dummies only talk to dummies, so both contribute exact zeros to the logits and to every gradient.
-
-    G is fixed per capture.  ``matches(batch)``: same G and feature widths, ``N <= node_capacity``, ``E <= edge_capacity``; a
-    call with a batch that does not match raises ValueError.  ``check()`` reads the feed's sticky flag and the last build's
-    status in one sync, clears the flag and raises the reference's IndexError.  BatchNorm layers: NotImplementedError (the dummy
-    rows would enter the batch statistics)."""
+    (superpixel batches: a new region adjacency and new node counts every batch): ``CapturedTrainStep`` over a
+    ``GNN.RaggedBatchFeed``, whose one launch also carries the labels, and ``GNN.ragged_batch_logits`` - mean cross-entropy over the
+    G graphs.  Slack rows ``[N, node_capacity)`` belong to no graph and the dummies only talk to dummies, so both contribute exact
+    zeros to the logits and to every gradient.  G is fixed per capture; a call with a batch that does not ``matches`` raises
+    ValueError.  BatchNorm layers: NotImplementedError (the dummy rows would enter the batch statistics)."""
 
     def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, batch: GraphBatch, labels, loss_sum: torch.Tensor, *,
                  edge_capacity: int, node_capacity: int, loss_scale: float = 1.0, capture_error_mode: str = "global"):
-        from .GNN import CombinedModel, RaggedBatchFeed
-        from .topology import GraphTopology
-        dev = require_gpu_param(next(model.parameters()), "CapturedRaggedBatchStep")
+        who = "CapturedRaggedBatchStep"
+        dev = require_gpu_param(next(model.parameters()), who)
         if not isinstance(model, CombinedModel):
-            raise TypeError("CapturedRaggedBatchStep: a CombinedModel expected")
-        from .GNN import _no_capture_with_pooling
-        _no_capture_with_pooling(model, "CapturedRaggedBatchStep")
-        if any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
-            raise NotImplementedError("CapturedRaggedBatchStep: not with BatchNorm layers (norm_type='BatchNorm1d')")
-        self.optimizer = optimizer
-        self.loss_sum = loss_sum
-        self.collective_outside = _world(optimizer.fp.reducer.group) > 1
-        self.feed = feed = RaggedBatchFeed(batch, edge_capacity, node_capacity, dev, with_labels=True, who="CapturedRaggedBatchStep")
-        self.edge_capacity, self.node_capacity, self.num_graphs = feed.edge_capacity, feed.node_capacity, feed.num_graphs
-        self.x, self.pos, self.edge_index, self.label = feed.x, feed.pos, feed.edge_index, feed.labels
-        self._status = None
+            raise TypeError(f"{who}: a CombinedModel expected")
+        _no_capture_with_pooling(model, who)
+        if _has_batchnorm(model):
+            raise NotImplementedError(f"{who}: not with BatchNorm layers (norm_type='BatchNorm1d')")
+        feed = RaggedBatchFeed(batch, edge_capacity, node_capacity, dev, with_labels=True, who=who)
         feed(batch, labels)
-
-        def forward(mod, xx, pp, ee):
-            topo = GraphTopology(ee, feed.rows, device=dev, validate="deferred")  # never the cache: built in every step
-            self._status = topo.status  # the capture's own flags: every replay rewrites them
-            return mod.forward_batched_device(xx, pp, topo, graph_ptr=feed.graph_ptr)
-        self._capture(model, criterion, forward, loss_scale, capture_error_mode)
-
-    @property
-    def num_nodes(self) -> int:
-        return self.feed.num_nodes
-
-    def matches(self, batch) -> bool:
-        return self.feed.matches(batch)
+        self._init(model, optimizer, criterion, feed, feed.labels, lambda mod: ragged_batch_logits(mod, feed), loss_sum, loss_scale,
+                   capture_error_mode)
 
     def __call__(self, batch, labels) -> None:
         self.feed(batch, labels)
         self.replay()
 
-    def check(self) -> None:
-        self.feed.check(self._status)
+
+class _TensorFeed:
+    """ONE input buffer of the sample's shape and dtype; a call is one copy."""
+
+    edge_capacity = node_capacity = pos = edge_index = None
+
+    def __init__(self, sample: torch.Tensor, device):
+        self.x = sample.to(device).clone()
+
+    def __call__(self, sample: torch.Tensor) -> None:
+        self.x.copy_(sample, non_blocking=True)
+
+    def check(self, status) -> None:
+        pass
 
 
 class CapturedTensorStep(CapturedTrainStep):
     """One training step on a plain tensor batch (the reference's image-MLP path, main.py:21-29: ``mod(x)`` on float32
-    ``[B, 3, R, R]``, mean cross-entropy over the B labels), captured once and replayed, on the capture machinery of
-    ``CapturedTrainStep``: ONE input buffer of the sample's shape and dtype, one label buffer.  Everything runs on a single
-    stream.  ``matches(sample, label)``: same shapes and dtype (a short last batch does not match and runs eagerly)."""
+    ``[B, 3, R, R]``, mean cross-entropy over the B labels): ``CapturedTrainStep`` over a ``_TensorFeed``.  Everything runs on a
+    single stream.  ``matches(sample, label)``: same shapes and dtype (a short last batch does not match and runs eagerly)."""
 
     def __init__(self, model: nn.Module, optimizer: FusedAdam, criterion, sample: torch.Tensor, label, loss_sum: torch.Tensor, *,
                  loss_scale: float = 1.0, capture_error_mode: str = "global"):
         dev = require_gpu_param(next(model.parameters()), "CapturedTensorStep")
-        self.optimizer = optimizer
-        self.loss_sum = loss_sum
-        self.collective_outside = _world(optimizer.fp.reducer.group) > 1
-        self.edge_capacity = self.node_capacity = None
-        self.x = sample.to(dev).clone()
-        self.pos = self.edge_index = None
-        self.label = torch.as_tensor(label).to(dev).clone()
-        self._capture(model, criterion, lambda mod, xx, pp, ee: mod(xx), loss_scale, capture_error_mode)
+        feed = _TensorFeed(sample, dev)
+        self._init(model, optimizer, criterion, feed, torch.as_tensor(label).to(dev).clone(), lambda mod: (mod(feed.x), None),
+                   loss_sum, loss_scale, capture_error_mode)
 
     def matches(self, sample, label=None) -> bool:
         return (isinstance(sample, torch.Tensor) and sample.shape == self.x.shape and sample.dtype == self.x.dtype
                 and (label is None or torch.as_tensor(label).shape == self.label.shape))
 
     def __call__(self, sample, label) -> None:
-        self.x.copy_(sample, non_blocking=True)
+        self.feed(sample)
         self.label.copy_(torch.as_tensor(label), non_blocking=True)
         self.replay()
 
-    def check(self) -> None:
-        pass
+
 
 
 # --------------------------------------------------------------------------- the run's side effects
@@ -576,10 +436,8 @@ class _RaggedBatchCaptures:
     its own.  A batch with another graph count (a short last batch) runs eagerly."""
 
     def __init__(self, model, make, limit: int):
-        from .GNN import CombinedModel
         self.make, self.limit = make, limit  # make(batch, *args, edge_capacity=, node_capacity=) -> the capture object
-        self.allowed = (isinstance(model, CombinedModel)
-                        and not any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()))
+        self.allowed = isinstance(model, CombinedModel) and not _has_batchnorm(model)
         self.current = None
         self.captures = 0
         self.edge_capacity = self.node_capacity = 0
@@ -660,7 +518,7 @@ class _SampleStepper:
             self.padded = None  # more edges (or nodes) than the capacity: capture again with room to spare
         if (self.padded is None and (same_nodes or ragged) and self._padded_captures < self.MAX_PADDED_CAPTURES
                 and hasattr(self.model, "graph_net") and hasattr(self.model, "classifier")
-                and not any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in self.model.modules())):
+                and not _has_batchnorm(self.model)):
             if ragged:  # capacities only grow from one capture to the next
                 self._edge_capacity = padded_capacity(max(int(prev[2].size(1)), int(sample[2].size(1))), self._edge_capacity)
                 self._node_capacity = padded_capacity(max(int(prev[0].size(0)), int(sample[0].size(0))), self._node_capacity, 32)
@@ -796,7 +654,6 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     # record (or, under gloo, host-stage) a collective per sample that nothing here asked for
     # (a model whose top-K pooling reads sizes back in its forward: no capture can record it, every step runs eagerly; padded
     # pooling layers under a pooled read-out are captured like an un-pooled model)
-    from .GNN import pooling_prevents_capture
     stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1 and not pooling_prevents_capture(model))
     stepper.capture_ragged_batches = stepper.capture and capture_ragged_batches
     history = []
@@ -844,7 +701,6 @@ class _BatchScorer:
     ``_logits_of`` as they always did."""
 
     def __init__(self, model, dev, capture: bool):
-        from .GNN import CapturedRaggedBatchForward, pooling_prevents_capture
         # pooling that reads sizes back: eager (no capture)
         self.model, self.dev, self.capture = model, dev, capture and not pooling_prevents_capture(model)
         self.ragged = _RaggedBatchCaptures(

@@ -136,6 +136,30 @@ def test_captured_minibatch_training_equals_eager(tmp_path):
         assert torch.equal(out[True][0][k], out[False][0][k]), k
 
 
+def test_captured_minibatch_training_through_graph_ptr_equals_eager(tmp_path):
+    """The twin of the test above on a model with ``ragged_readout``: its mini-batch step takes the ``graph_ptr`` form of
+    ``forward_batched``, whose device offsets only the ``forward=`` closure of the captured step holds.  Batches of 4, 4, 2 over two
+    epochs: the short batch runs eagerly - and allocates - between the first epoch's replay and the second epoch's two, so
+    offsets that the capture did not keep alive would be somebody else's bytes by then."""
+    from graphnet_classifier_amd.dataset import GraphImageFolder
+    from graphnet_classifier_amd.train import train
+    ds = GraphImageFolder(_folder(tmp_path / "data"), resize_value=8, method="pixel")
+    out = {}
+    for capture in (False, True):
+        m = _model(64, ragged=True)
+        torch.manual_seed(3)  # the same shuffled batches in both runs
+        loader = ds.loader(shuffle=True, batch_size=4)
+        assert len(loader) == 3
+        r = train(m, loader, 2, patience=5, output_path=str(tmp_path / str(capture)), capture=capture)
+        assert r["batched"] and r["captured"] == capture
+        out[capture] = ({k: v.detach().cpu().clone() for k, v in m.state_dict().items()}, r["avg_loss"])
+    print("avg_loss captured", out[True][1], "eager", out[False][1])
+    print("final parameters: worst |captured - eager| =", max(max_abs(out[True][0][k], out[False][0][k]) for k in out[True][0]))
+    assert out[True][1] == out[False][1]
+    for k in out[True][0]:
+        assert torch.equal(out[True][0][k], out[False][0][k]), k
+
+
 def test_batch_size_one_is_the_loader_it_was(tmp_path):
     from graphnet_classifier_amd.dataset import GraphImageFolder
     ds = GraphImageFolder(_folder(tmp_path / "data"), resize_value=16, method="pixel")

@@ -99,6 +99,25 @@ def test_a_bad_edge_list_is_reported_after_a_clean_batch_and_the_capture_lives_o
     cap.check()
 
 
+def test_the_feed_reports_a_negative_id_once():
+    """``RaggedBatchFeed`` alone (the feed launch, no replay): a negative id leaves its graph's node range, so the launch sets the
+    sticky flag; ``check`` raises once, clears it, and a clean batch afterwards checks clean."""
+    from graphnet_classifier_amd.GNN import RaggedBatchFeed
+    clean = _batch(SEEDS[0]).to(DEV)
+    feed = RaggedBatchFeed(clean, C, M, DEV, with_labels=False)
+    feed(clean)
+    feed.check(None)
+    bad = _batch(SEEDS[1]).to(DEV)
+    bad.edge_index = bad.edge_index.clone()
+    bad.edge_index[0, int(bad.edge_ptr[1]) + 1] = -1
+    feed(bad)
+    feed(clean)  # sticky
+    with pytest.raises(IndexError):
+        feed.check(None)
+    feed.check(None)
+    feed.check(torch.zeros(2, dtype=torch.int32, device=DEV))
+
+
 def test_forward_rejects_what_does_not_fit(forward_setup):
     from graphnet_classifier_amd.GNN import CapturedRaggedBatchForward
     m, batches, eager, cap = forward_setup

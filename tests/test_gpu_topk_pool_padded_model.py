@@ -17,6 +17,7 @@ from tests import option_crossing_cases as X
 from tests import topk_pool_cases as K
 from tests import test_gpu_topk_pool_model as M
 from tests._util import max_abs
+from tests.capture_lifetime_cases import replay_between_allocations
 from tests.test_gpu_attention_readout_model import SIX, THREE, _graph
 
 pytestmark = pytest.mark.gpu
@@ -150,24 +151,6 @@ def test_crossings_on_the_batch_of_six(inputs, crossing):
     assert logits.shape == ref.shape and max_abs(logits, ref) <= 1e-5
 
 
-def _replay_between_allocations(capture, sample, want, other_model, other_sample, what):
-    """Four replays of a fixed-topology ``CapturedForward`` with unrelated small device allocations between them - clones of the
-    logits, small int64 tensors, an eager forward of another model, all kept alive - each within the bar of ``want``.  A hipGraph
-    holds the ADDRESSES of its input buffers: one that the capture object does not keep alive (the ``[0, N]`` offsets of the pooling
-    layers and the read-out were such a buffer) goes back to the allocator, the next small allocation lands on it, and from then on
-    a replay reads those bytes.  The first replay straight after construction cannot show that."""
-    held = []
-    for k in range(4):
-        got = capture(sample[0], sample[1])
-        print(f"{what}, fixed topology, replay {k}: |captured - eager sized| = {max_abs(got, want):.3e}")
-        assert max_abs(got, want) <= 1e-5, k
-        held.append(got.clone())
-        held.extend(torch.full((2,), 7 + k + j, dtype=torch.int64, device=DEV) for j in range(8))
-        with torch.no_grad():
-            held.append(other_model(other_sample))
-    assert all(torch.equal(held[0], h) for h in held[10::10])  # the replays among themselves: the same bits
-
-
 @pytest.mark.parametrize("readout", READOUTS)
 def test_unpooled_fixed_topology_replays_survive_later_allocations(readout):
     """The same buffer serves the pooled read-out of a model WITHOUT pooling layers (``readout_logits(y, [0, N])``)."""
@@ -176,7 +159,7 @@ def test_unpooled_fixed_topology_replays_survive_later_allocations(readout):
     sample, other = _dev(_graph(THREE[0][0])), _dev(_graph(THREE[1][0]))
     with torch.no_grad():
         want = m(sample)
-    _replay_between_allocations(CapturedForward(m, *sample), sample, want, m, other, f"un-pooled, {readout}")
+    replay_between_allocations(CapturedForward(m, *sample), sample, want, m, other, f"un-pooled, {readout}")
 
 
 @pytest.mark.parametrize("readout", READOUTS)
@@ -189,7 +172,7 @@ def test_captured_forwards_equal_the_eager_sized_model(readout):
         want = {c: sized(on_dev[c]) for c in on_dev}
     first = THREE[0][0]
     fixed = CapturedForward(m, *on_dev[first])  # one fixed topology
-    _replay_between_allocations(fixed, on_dev[first], want[first], sized, on_dev[THREE[1][0]], f"padded, {readout}")
+    replay_between_allocations(fixed, on_dev[first], want[first], sized, on_dev[THREE[1][0]], f"padded, {readout}")
     any_topology = CapturedForward(m, *on_dev[first], edge_capacity=1024)  # any edge list over the 69 nodes
     assert max_abs(any_topology(*on_dev[first]), want[first]) <= 1e-5
     any_topology.check()

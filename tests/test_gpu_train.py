@@ -296,6 +296,57 @@ def test_captured_step_after_eager_default_stream_training(G):
         assert torch.equal(finals["captured"][0][k], finals["eager"][0][k]), k
 
 
+def test_captured_step_owns_what_its_forward_closes_over(G):
+    """A ``forward=`` closure is the ONLY holder of the device ``graph_ptr`` that the recorded read-out kernels read (what
+    ``train()`` builds for a mini-batch of graphs of any size).  The step object keeps the closure it recorded, so the offsets
+    outlive the constructor: four replays with unrelated allocations in front of and between them - any of which would land on a
+    freed 32-byte buffer - each equal to the same step run eagerly on a twin model.  Three 4 x 4 grid graphs per batch."""
+    from graphnet_classifier_amd import synthetic
+    from graphnet_classifier_amd.train import CapturedTrainStep, FlatParameters, FusedAdam
+    from tests.capture_lifetime_cases import allocate_between_replays
+    batch = synthetic.superpixel_like_graphs(3, seed=11, shapes=((4, 4),))
+    assert batch.graph_ptr.tolist() == [0, 16, 32, 48]
+    xs = [batch.x * (1 + 0.25 * k) for k in range(4)]
+    labels = [torch.tensor(l) for l in ([0, 1, 1], [1, 1, 0], [0, 0, 1], [1, 0, 1])]
+    crit = torch.nn.CrossEntropyLoss()
+
+    def twin():
+        torch.manual_seed(5)
+        m = G.CombinedModel(G.GraphNet(**synthetic.graphnet_kwargs(32, 1)), num_nodes=16, classes=2)
+        return m, FusedAdam(FlatParameters(m)), torch.zeros((), dtype=torch.float64, device=DEV)
+
+    def through(gptr):
+        return lambda mod, x, pos, ei: mod.forward_batched(x, pos, ei, graph_ptr=gptr)
+
+    m, opt, loss_sum = twin()
+    eager, eager_opt, eager_sum = twin()
+    spare = twin()[0].eval()
+    one = batch.slice_graphs(0, 1)
+    spare_sample = (one.x.to(DEV), one.pos.to(DEV), one.edge_index.to(DEV))
+    step = CapturedTrainStep(m, opt, crit, (xs[0], batch.pos, batch.edge_index), labels[0], loss_sum,
+                             forward=through(batch.graph_ptr.to(DEV)))
+    held = []
+    allocate_between_replays(held, -1, spare, spare_sample)
+    for k in range(4):
+        step((xs[k], batch.pos, batch.edge_index), labels[k])
+        logits = eager.forward_batched(xs[k].to(DEV), batch.pos.to(DEV), batch.edge_index, graph_ptr=batch.graph_ptr)
+        loss = crit(logits, labels[k].to(DEV))
+        eager_opt.zero_grad(); loss.backward(); eager_opt.step()
+        eager_sum += loss.detach().double()
+        worst = max(max_abs(a, b) for a, b in zip(m.state_dict().values(), eager.state_dict().values()))
+        print(f"replay {k}: loss_sum captured {float(loss_sum)!r} eager {float(eager_sum)!r}, parameters off by {worst:.3e}")
+        assert float(loss_sum) == float(eager_sum), k
+        for (name, a), b in zip(m.state_dict().items(), eager.state_dict().values()):
+            assert torch.equal(a, b), (k, name)
+        allocate_between_replays(held, k, spare, spare_sample)
+    assert int(opt.step_count.item()) == 4
+    # ... and owning the closure makes no reference cycle: a capture that is replaced frees its graph and its buffers at once
+    import weakref
+    alive = weakref.ref(step)
+    del step
+    assert alive() is None
+
+
 def test_captured_step_restores_batchnorm_buffers(G):
     """Constructing a CapturedTrainStep must not train: the warm-up steps' effect on BatchNorm running statistics is
     undone like their effect on the parameters and the Adam state (advisor finding, round 2)."""

@@ -123,5 +123,5 @@ for tag, runner in (("forward (eager)", None), ("forward/captured, any topology"
 try:
     step.check()
 except IndexError:
-    print("flags:", step._status.tolist(), bool(step._range_flag), "loss_sum", float(loss_sum))
+    print("flags:", step._status.tolist(), bool(step.feed._range_flag), "loss_sum", float(loss_sum))
     raise
