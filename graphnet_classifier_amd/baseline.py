@@ -16,7 +16,9 @@ import torch
 from . import image_to_graph as I2G
 from .MLP import MLP
 from .dataset import ImageTensorFolder
-from .train import train
+from .train import check_optimizer_options, train
+
+TRAINING_CONTROLS = ("optimizer", "lr", "weight_decay", "momentum", "nesterov", "max_grad_norm", "lr_schedule", "skip_nonfinite")
 
 
 def load_data(dataset_path, resize_value=128, batch_size=8):
@@ -25,12 +27,18 @@ def load_data(dataset_path, resize_value=128, batch_size=8):
     return ImageTensorFolder(dataset_path, resize_value).loader(batch_size=batch_size, shuffle=True)
 
 
-def train_MLP(epochs=30, channels=3, resize_value=128, batch_size=8, hidden_layers=2, output_path='weights/MLP', dataset_path='dataset'):
-    """``main.py:21-29`` (``dataset_path`` is the one addition: the reference hard-codes ``'dataset'``).  Returns ``train``'s dict
-    with the model under ``"model"``."""
+def train_MLP(epochs=30, channels=3, resize_value=128, batch_size=8, hidden_layers=2, output_path='weights/MLP', dataset_path='dataset',
+              **training_controls):
+    """``main.py:21-29`` (``dataset_path`` is one addition: the reference hard-codes ``'dataset'``; ``training_controls`` the other:
+    ``train``'s ``optimizer``, ``weight_decay``, ``momentum``, ``nesterov``, ``max_grad_norm``, ``lr_schedule``, ``skip_nonfinite``
+    and ``lr``, checked before the folder is read).  Returns ``train``'s dict with the model under ``"model"``."""
+    unknown = sorted(set(training_controls) - set(TRAINING_CONTROLS))
+    if unknown:
+        raise ValueError(f"train_MLP: unknown training controls {unknown}; {TRAINING_CONTROLS} expected")
+    check_optimizer_options(**{k: v for k, v in training_controls.items() if k != "skip_nonfinite"})
     loader = load_data(dataset_path, resize_value, batch_size)
     model = MLP(in_dim=channels * resize_value * resize_value, out_dim=len(loader.dataset.classes), hidden_layers=hidden_layers)
-    history = train(model, loader, epochs, patience=5, output_path=output_path)
+    history = train(model, loader, epochs, patience=5, output_path=output_path, **training_controls)
     history["model"] = model
     return history
 

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "gnc_common.h"
+#include "optimizer_rules.h"
 
 namespace {
 
@@ -38,19 +39,8 @@ __global__ void adam_tick_kernel(int64_t* __restrict__ step, float* __restrict__
   }
 }
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float step_size, float bc2_sqrt, float omb1,
-                                         float beta2, float omb2, float eps, float wd) {
-  // one rounding per ATen kernel of the foreach path (lerp_, mul_, addcmul_, sqrt, div_, add_, addcdiv_); the
-  // multiply-adds inside one of those kernels are fused there too
-  if (wd != 0.f) g = fmaf(wd, p, g);
-  m = fmaf(omb1, g - m, m);
-  v = fmaf(__fmul_rn(omb2, g), g, __fmul_rn(v, beta2));
-  // sqrtf, not __fsqrt_rn: despite its name that one is the native v_sqrt_f32 (1 ulp) here, sqrtf is correctly rounded as ATen's is
-  const float den = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
-  p = fmaf(-step_size, __fdiv_rn(m, den), p);
-}
+using gnc::adam_one;  // optimizer_rules.h: shared with the controlled rules of optimizer_ctl.hip (K22)
+using gnc::f4;
 
 __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                         float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, int64_t n,

@@ -20,6 +20,11 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 GNC_MAX_SEGMENTS = 4
 GNC_MAX_LINEAR = 8
 ABI_VERSION = 20
+GRAD_NORM_BLOCKS = 256                      # workgroups of the gradient-norm pass: a constant, so the sum's order depends on n alone
+GRAD_NORM_PASS = GRAD_NORM_BLOCKS * 256 * 4  # elements one grid pass of it covers (float4 per thread)
+OPT_SCALARS = 8                             # float32 scalars of a controlled step: step_size, bc2_sqrt, decay, clip_coef, lr, grad_norm
+OPT_RULES = {"adam": 0, "adamw": 1, "sgd": 2}
+LR_SCHEDULES = {"constant": 0, "cosine": 1, "step": 2}
 
 ACTIVATIONS = {  # nn.<Name> accepted by the reference's MLP(activation=...) (models/MLP.py:21)
     "ReLU": 0, "Identity": 1, "Tanh": 2, "Sigmoid": 3, "SiLU": 4, "GELU": 5, "LeakyReLU": 6, "ELU": 7,
@@ -174,6 +179,12 @@ _SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p]),
     "gnc_adam_step_hp64_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_float, c_float,
                                          c_void_p, c_void_p, c_void_p]),
+    "gnc_sizeof_opt_ctl": (c_int32, []),
+    "gnc_grad_norm_pass": (c_int64, []),
+    "gnc_grad_norm_blocks": (c_int32, []),
+    "gnc_grad_sumsq_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "gnc_optimizer_ctl_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -231,6 +242,14 @@ class WideLinearPlan(Structure):
                                               "backward_workspace_floats")]
 
 
+class OptCtl(Structure):
+    """gnc_opt_ctl_t: the hyper-parameters of a controlled optimizer step (``optimizer_ctl_step``), constants of a run."""
+    _fields_ = ([(name, c_int32) for name in ("rule", "schedule", "nesterov", "clip", "check_nonfinite", "reserved")]
+                + [(name, c_int64) for name in ("warmup_steps", "total_steps", "every")]
+                + [(name, c_double) for name in ("lr", "min_lr", "gamma", "max_grad_norm", "beta1", "beta2", "eps", "weight_decay",
+                                                 "momentum")])
+
+
 GNC_XTY_MAX_JOBS = 8
 
 _lib = None
@@ -260,6 +279,12 @@ def load_library() -> ctypes.CDLL:
     if lib.gnc_sizeof_mlp_desc() != ctypes.sizeof(MlpDesc):
         raise RuntimeError(f"{LIB_NAME}: gnc_mlp_desc_t is {lib.gnc_sizeof_mlp_desc()} bytes in C but "
                            f"{ctypes.sizeof(MlpDesc)} in the ctypes binding")
+    if lib.gnc_sizeof_opt_ctl() != ctypes.sizeof(OptCtl):
+        raise RuntimeError(f"{LIB_NAME}: gnc_opt_ctl_t is {lib.gnc_sizeof_opt_ctl()} bytes in C but {ctypes.sizeof(OptCtl)} in the "
+                           f"ctypes binding")
+    if lib.gnc_grad_norm_pass() != GRAD_NORM_PASS or lib.gnc_grad_norm_blocks() != GRAD_NORM_BLOCKS:
+        raise RuntimeError(f"{LIB_NAME}: the gradient-norm grid is {lib.gnc_grad_norm_blocks()} workgroups of "
+                           f"{lib.gnc_grad_norm_pass()} elements per pass in C, not {GRAD_NORM_BLOCKS} / {GRAD_NORM_PASS}")
     _lib = lib
     return lib
 
@@ -2115,3 +2140,72 @@ def adam_step(param: torch.Tensor, grad: torch.Tensor, exp_avg: torch.Tensor, ex
         _check(_launch("adam_flat", param, lambda: lib.gnc_adam_step_hp64_f32(
             param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n, lr, beta1, beta2, eps, weight_decay,
             step.data_ptr(), scratch.data_ptr(), _stream(param)), 28.0 * n), "gnc_adam_step_f32")
+
+
+# --------------------------------------------------------------------------- controlled optimizer step (K22)
+def opt_ctl(rule: str, lr: float, *, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, momentum: float = 0.0,
+            nesterov: bool = False, max_grad_norm: float | None = None, check_nonfinite: bool = False, schedule: str = "constant",
+            warmup_steps: int = 0, total_steps: int = 0, min_lr: float = 0.0, gamma: float = 0.1, every: int = 1) -> OptCtl:
+    """The ``OptCtl`` of a rule ("adam": Adam + L2, "adamw", "sgd") and a schedule ("constant", "cosine", "step").  Unknown names
+    raise ValueError; the ranges are checked by the library on every step."""
+    if rule not in OPT_RULES:
+        raise ValueError(f"optimizer rule {rule!r}: one of {sorted(OPT_RULES)} expected")
+    if schedule not in LR_SCHEDULES:
+        raise ValueError(f"lr schedule {schedule!r}: one of {sorted(LR_SCHEDULES)} expected")
+    c = OptCtl()
+    c.rule, c.schedule, c.nesterov = OPT_RULES[rule], LR_SCHEDULES[schedule], int(bool(nesterov))
+    c.clip, c.check_nonfinite = int(max_grad_norm is not None), int(bool(check_nonfinite) or max_grad_norm is not None)
+    c.warmup_steps, c.total_steps, c.every = int(warmup_steps), int(total_steps), int(every)
+    c.lr, c.min_lr, c.gamma, c.max_grad_norm = float(lr), float(min_lr), float(gamma), float(max_grad_norm or 0.0)
+    c.beta1, c.beta2, c.eps, c.weight_decay, c.momentum = float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(momentum)
+    return c
+
+
+def grad_sumsq(grad: torch.Tensor, partials: torch.Tensor) -> None:
+    """Sum of ``g * g`` over the flat fp32 ``grad`` into ``partials`` (float64 [GRAD_NORM_BLOCKS]): a fixed grid, no atomics, the
+    same bits for the same values at any 16-B aligned address."""
+    lib = load_library()
+    _require_cuda(grad, partials)
+    if grad.dtype != torch.float32 or not grad.is_contiguous() or grad.dim() != 1:
+        raise ValueError("grad_sumsq: a flat contiguous float32 buffer expected")
+    if partials.dtype != torch.float64 or not partials.is_contiguous() or partials.numel() < GRAD_NORM_BLOCKS:
+        raise ValueError(f"grad_sumsq: partials must be float64 [{GRAD_NORM_BLOCKS}]")
+    with torch.cuda.device(grad.device):
+        _check(_launch("grad_sumsq", grad, lambda: lib.gnc_grad_sumsq_f32(grad.data_ptr(), grad.numel(), partials.data_ptr(),
+                                                                          _stream(grad)), 4.0 * grad.numel()), "gnc_grad_sumsq_f32")
+
+
+def optimizer_ctl_step(param: torch.Tensor, grad: torch.Tensor, state1: torch.Tensor | None, state2: torch.Tensor | None,
+                       step: torch.Tensor, scalars: torch.Tensor, skipped: torch.Tensor, partials: torch.Tensor | None,
+                       ctl: OptCtl) -> None:
+    """One controlled update of the flat fp32 buffer ``param`` from ``grad`` (include/gnc_hip.h, csrc/optimizer_ctl.hip): the
+    gradient-norm pass when ``ctl`` clips or checks for non-finite values, the control tick (schedule, clip coefficient, bias
+    corrections, skip flag - all on the device) and the element launch of ``ctl``'s rule.  ``state1`` / ``state2``: Adam's moments,
+    or SGD's momentum buffer (None without momentum) / None.  ``step`` int64 [1], ``scalars`` float32 [OPT_SCALARS], ``skipped`` int64 [2]
+    (count, this step's flag), ``partials`` float64 [GRAD_NORM_BLOCKS] (None when ``ctl`` needs no norm).  ``grad`` is read, never
+    written: the clip is applied to the values as they are read."""
+    lib = load_library()
+    adam = ctl.rule != OPT_RULES["sgd"]
+    use_norm = bool(ctl.clip or ctl.check_nonfinite)
+    if adam and (state1 is None or state2 is None):
+        raise ValueError("optimizer_ctl_step: Adam and AdamW need both moment buffers")
+    if not adam and (state2 is not None or (state1 is None) != (ctl.momentum == 0.0)):
+        raise ValueError("optimizer_ctl_step: SGD takes the momentum buffer as state1 exactly when momentum != 0, and no state2")
+    if use_norm and partials is None:
+        raise ValueError("optimizer_ctl_step: clipping and the non-finite check need the partials buffer")
+    _require_cuda(param, grad, state1, state2, step, scalars, skipped, partials)
+    n = param.numel()
+    for t in (param, grad, state1, state2):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise ValueError("optimizer_ctl_step: flat contiguous float32 buffers of one size expected")
+    if (step.dtype != torch.int64 or step.numel() < 1 or scalars.dtype != torch.float32 or scalars.numel() < OPT_SCALARS
+            or not scalars.is_contiguous() or skipped.dtype != torch.int64 or skipped.numel() < 2 or not skipped.is_contiguous()):
+        raise ValueError(f"optimizer_ctl_step: step must be int64 [1], scalars float32 [{OPT_SCALARS}], skipped int64 [2]")
+    if partials is not None and (partials.dtype != torch.float64 or partials.numel() < GRAD_NORM_BLOCKS or not partials.is_contiguous()):
+        raise ValueError(f"optimizer_ctl_step: partials must be float64 [{GRAD_NORM_BLOCKS}]")
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    state_bytes = 8.0 * ((state1 is not None) + (state2 is not None))
+    with torch.cuda.device(param.device):
+        _check(_launch("optimizer_ctl", param, lambda: lib.gnc_optimizer_ctl_step_f32(
+            param.data_ptr(), grad.data_ptr(), ptr(state1), ptr(state2), n, ctypes.byref(ctl), step.data_ptr(), scalars.data_ptr(),
+            skipped.data_ptr(), ptr(partials), _stream(param)), (12.0 + state_bytes + 4.0 * use_norm) * n), "gnc_optimizer_ctl_step_f32")

@@ -8,6 +8,9 @@ dataset order (:35-45), average training loss per epoch, early stopping on it (:
 
 * parameters and gradients are views of two flat fp32 buffers (``FlatParameters``), the optimizer is ONE fused Adam
   launch over them (``FusedAdam`` -> ``gnc_adam_step_f32``) instead of a walk over 76 tensors;
+* AdamW, SGD, gradient clipping by the global norm, learning-rate schedules (``lr_at``) and a skip on non-finite gradients are
+  keyword options of ``train()`` (``FusedAdam``'s options, ``FusedSGD``): their scalars live on the device, so a captured step
+  replays them (``native.optimizer_ctl_step``, DESIGN K22); the default stays the reference's optimizer;
 * the running loss is accumulated on the device (float64 scalar) and read once per epoch, where the reference
   synchronises on ``loss.item()`` after every sample (:44);
 * when consecutive samples share one topology (pixel / patch graphs: the edge list depends on the image size only,
@@ -27,6 +30,8 @@ are (``utils/inference.py:40-45``) and vice versa.
 """
 from __future__ import annotations
 
+import math
+import numbers
 import os
 import time
 from datetime import datetime
@@ -93,38 +98,199 @@ class _AlignedReducer(FlatGradAllReduce):
         self.collectives = 0
 
 
-class FusedAdam:
-    """torch.optim.Adam(params, lr, betas, eps, weight_decay) semantics (amsgrad off) as one launch over the flat
-    buffers of a ``FlatParameters`` (``gnc_adam_step_f32``).  The step counter is a device tensor, so ``step()`` is
-    the same launch sequence every time (hipGraph-capturable)."""
+LR_SCHEDULE_KEYS = ("kind", "warmup_steps", "total_steps", "min_lr", "gamma", "every")
+OPTIMIZERS = ("adam", "adamw", "sgd")
 
-    def __init__(self, flat_params: FlatParameters, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
-        self.fp = flat_params
-        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-        dev = flat_params.flat.device
-        self.exp_avg = torch.zeros_like(flat_params.flat)
-        self.exp_avg_sq = torch.zeros_like(flat_params.flat)
-        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._scratch = torch.zeros(2, dtype=torch.float32, device=dev)
+
+def lr_at(t: int, lr: float, kind: str = "constant", warmup_steps: int = 0, total_steps: int = 0, min_lr: float = 0.0,
+          gamma: float = 0.1, every: int = 1) -> float:
+    """Learning rate of optimizer step ``t`` (1-based), the closed form the control tick evaluates on the device
+    (csrc/optimizer_ctl.hip, same operations in the same order): ``lr * (t / warmup_steps)`` up to ``warmup_steps`` (reaching ``lr``
+    there), then ``constant``; ``cosine`` from ``lr`` down to ``min_lr`` at ``total_steps`` and held afterwards; or ``step``,
+    ``lr * gamma ** k`` after ``k`` whole periods of ``every`` steps past the warm-up."""
+    t = int(t)
+    if t <= warmup_steps:
+        return lr * (float(t) / float(warmup_steps))  # exactly lr at t == warmup_steps
+    if kind == "cosine":
+        if t >= total_steps:
+            return min_lr
+        progress = float(t - warmup_steps) / float(total_steps - warmup_steps)
+        return min_lr + 0.5 * (lr - min_lr) * (1.0 + math.cos(math.pi * progress))
+    if kind == "step":
+        return lr * gamma ** float((t - warmup_steps) // every)
+    if kind != "constant":
+        raise ValueError(f"lr schedule kind {kind!r}: one of {sorted(native.LR_SCHEDULES)} expected")
+    return lr
+
+
+def check_optimizer_options(optimizer: str = "adam", lr: float = 1e-3, weight_decay: float = 0.0, momentum: float = 0.0,
+                            nesterov: bool = False, max_grad_norm: float | None = None, lr_schedule: dict | None = None) -> dict:
+    """ValueError for an unknown name or values that do not go together; returns the schedule as ``lr_at``'s keywords
+    (``{"kind": "constant"}`` for None).  Touches no device."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer {optimizer!r}: one of {OPTIMIZERS} expected")
+    finite = lambda v: isinstance(v, numbers.Real) and math.isfinite(v)  # noqa: E731  (NumPy scalars included)
+    if not (finite(lr) and lr >= 0):
+        raise ValueError(f"lr {lr!r}: a finite value >= 0 expected")
+    if not (finite(weight_decay) and weight_decay >= 0):
+        raise ValueError(f"weight_decay {weight_decay!r}: a finite value >= 0 expected")
+    if not (finite(momentum) and momentum >= 0):
+        raise ValueError(f"momentum {momentum!r}: a finite value >= 0 expected")
+    if optimizer != "sgd" and (momentum != 0 or nesterov):
+        raise ValueError(f"momentum / nesterov belong to optimizer='sgd', not {optimizer!r} (Adam's momentum is betas[0])")
+    if nesterov and momentum == 0:
+        raise ValueError("nesterov=True needs momentum > 0")
+    if optimizer == "adamw" and lr * weight_decay >= 1:
+        raise ValueError(f"adamw: lr * weight_decay = {lr * weight_decay} must stay below 1 (the decay factor 1 - lr * weight_decay)")
+    if max_grad_norm is not None and not (finite(max_grad_norm) and max_grad_norm > 0):
+        raise ValueError(f"max_grad_norm {max_grad_norm!r}: None or a finite value > 0 expected")
+    sched = {"kind": "constant", "warmup_steps": 0, "total_steps": 0, "min_lr": 0.0, "gamma": 0.1, "every": 1}
+    if lr_schedule is not None:
+        if not isinstance(lr_schedule, dict):
+            raise ValueError("lr_schedule: a dict expected")
+        unknown = sorted(set(lr_schedule) - set(LR_SCHEDULE_KEYS))
+        if unknown:
+            raise ValueError(f"lr_schedule: unknown keys {unknown}; {LR_SCHEDULE_KEYS} expected")
+        sched.update(lr_schedule)
+    kind = sched["kind"]
+    if kind not in native.LR_SCHEDULES:
+        raise ValueError(f"lr schedule kind {kind!r}: one of {sorted(native.LR_SCHEDULES)} expected")
+    for key in ("warmup_steps", "total_steps", "every"):
+        if not isinstance(sched[key], int) or isinstance(sched[key], bool) or sched[key] < 0:
+            raise ValueError(f"lr_schedule[{key!r}] = {sched[key]!r}: a count of optimizer steps (int >= 0) expected")
+    if kind == "cosine":
+        if sched["total_steps"] <= sched["warmup_steps"]:
+            raise ValueError("cosine schedule: total_steps must exceed warmup_steps")
+        if not (finite(sched["min_lr"]) and 0 <= sched["min_lr"] <= lr):
+            raise ValueError(f"cosine schedule: min_lr {sched['min_lr']!r} must lie in [0, lr]")
+    if kind == "step" and not (sched["every"] >= 1 and finite(sched["gamma"]) and sched["gamma"] > 0):
+        raise ValueError("step schedule: every >= 1 and gamma > 0 expected")
+    return sched
+
+
+class _Controls:
+    """Device state of a controlled step (``native.optimizer_ctl_step``, DESIGN K22): the tick's scalars, the skip counter and
+    the partials of the gradient-norm pass, with the ``native.OptCtl`` that holds the run's hyper-parameters."""
+
+    def __init__(self, device, rule: str, lr: float, schedule: dict, max_grad_norm, skip_nonfinite: bool, **hyper):
+        self.schedule = schedule
+        s = dict(schedule)
+        self.ctl = native.opt_ctl(rule, lr, max_grad_norm=max_grad_norm, check_nonfinite=skip_nonfinite, schedule=s.pop("kind"),
+                                  **s, **hyper)
+        # step_size, bc2_sqrt, decay, clip_coef, lr, grad_norm: no norm taken yet (and never, without clipping or the check)
+        first = [0.0, 0.0, 1.0, 1.0, lr_at(1, lr, **schedule), float("nan")]
+        self.scalars = torch.tensor(first + [0.0] * (native.OPT_SCALARS - len(first)), dtype=torch.float32, device=device)
+        self.skipped = torch.zeros(2, dtype=torch.int64, device=device)
+        self.uses_norm = bool(self.ctl.clip or self.ctl.check_nonfinite)
+        self.partials = torch.zeros(native.GRAD_NORM_BLOCKS, dtype=torch.float64, device=device) if self.uses_norm else None
+
+    def step(self, fp: FlatParameters, state1, state2, step_count: torch.Tensor) -> None:
+        native.optimizer_ctl_step(fp.flat, fp.grad, state1, state2, step_count, self.scalars, self.skipped, self.partials, self.ctl)
+
+
+class _FlatOptimizer:
+    """What ``FusedAdam`` and ``FusedSGD`` share: the flat buffers, the device step counter, the three device tensors a run
+    reports (``grad_norm``: the norm before clipping, NaN when no norm pass runs; ``current_lr``; ``skipped_steps``), and a
+    snapshot of every tensor a step writes."""
+
+    def _init_flat(self, flat_params: FlatParameters, controls: _Controls) -> None:
+        self.fp, self._controls = flat_params, controls
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=flat_params.flat.device)
+        self.grad_norm, self.current_lr = controls.scalars[5:6], controls.scalars[4:5]
+        self.skipped_steps = controls.skipped[0:1]
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         self.fp.reducer.zero_grad()
+
+    def _state(self):
+        raise NotImplementedError
+
+    def state_snapshot(self):
+        return [t.clone() for t in self._state()]
+
+    def state_restore(self, snap) -> None:
+        for dst, src in zip(self._state(), snap):
+            dst.copy_(src)
+
+
+class FusedAdam(_FlatOptimizer):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay) semantics (amsgrad off) as one launch over the flat
+    buffers of a ``FlatParameters`` (``gnc_adam_step_f32``).  The step counter is a device tensor, so ``step()`` is
+    the same launch sequence every time (hipGraph-capturable).
+
+    With any of the keyword options the step goes through the controlled path instead (``native.optimizer_ctl_step``, DESIGN K22),
+    which is capturable too - the schedule reads the device counter, so ONE captured step replays a whole schedule and a second
+    capture continues it: ``decoupled_weight_decay`` (torch.optim.AdamW: ``p *= 1 - lr * weight_decay`` in place of the L2 term),
+    ``max_grad_norm`` (the gradient is scaled by ``min(1, max_grad_norm / (norm + 1e-6))`` as it is read - ``fp.grad`` itself is not
+    rewritten - and a step whose gradient holds a NaN or an inf is skipped and counted, where ``clip_grad_norm_`` would poison every
+    parameter), ``lr_schedule`` (``lr_at``'s keywords as a dict) and ``skip_nonfinite`` (the skip without clipping)."""
+
+    def __init__(self, flat_params: FlatParameters, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, *, decoupled_weight_decay: bool = False, max_grad_norm: float | None = None,
+                 lr_schedule: dict | None = None, skip_nonfinite: bool = False):
+        rule = "adamw" if decoupled_weight_decay else "adam"
+        schedule = check_optimizer_options(rule, lr, weight_decay, max_grad_norm=max_grad_norm, lr_schedule=lr_schedule)
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.controlled = bool(decoupled_weight_decay or max_grad_norm is not None or lr_schedule is not None or skip_nonfinite)
+        dev = flat_params.flat.device
+        self._init_flat(flat_params, _Controls(dev, rule, self.lr, schedule, max_grad_norm, skip_nonfinite, betas=self.betas,
+                                               eps=self.eps, weight_decay=self.weight_decay))
+        self.exp_avg = torch.zeros_like(flat_params.flat)
+        self.exp_avg_sq = torch.zeros_like(flat_params.flat)
+        self._scratch = torch.zeros(2, dtype=torch.float32, device=dev)
 
     def step(self, reduce: bool = True, grads=None) -> None:
         """Gradient pack (+ the one all-reduce when a process group with more than one rank is up) and the update.
         ``grads``: see FlatGradAllReduce.pack."""
         if reduce:
             self.fp.reducer(grads)
+        if self.controlled:
+            self._controls.step(self.fp, self.exp_avg, self.exp_avg_sq, self.step_count)
+            return
         native.adam_step(self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self._scratch, self.lr,
                          self.betas[0], self.betas[1], self.eps, self.weight_decay)
 
-    def state_snapshot(self):
-        return [t.clone() for t in (self.fp.flat, self.exp_avg, self.exp_avg_sq, self.step_count)]
+    def _state(self):
+        plain = (self.fp.flat, self.exp_avg, self.exp_avg_sq, self.step_count)
+        return plain + (self._controls.scalars, self._controls.skipped) if self.controlled else plain
 
-    def state_restore(self, snap) -> None:
-        for dst, src in zip((self.fp.flat, self.exp_avg, self.exp_avg_sq, self.step_count), snap):
-            dst.copy_(src)
+
+class FusedSGD(_FlatOptimizer):
+    """torch.optim.SGD(params, lr, momentum, nesterov=, weight_decay=) semantics (dampening 0, maximize off) - with ``momentum=0``
+    the write-up's own rule ``w <- w - lr * dL/dw`` - as one controlled step over the flat buffers (``native.optimizer_ctl_step``,
+    DESIGN K22).  Same interface and keyword options as ``FusedAdam``; the momentum buffer starts at zero, which gives torch's
+    first-step ``buf = g``."""
+
+    def __init__(self, flat_params: FlatParameters, lr: float, momentum: float = 0.0, nesterov: bool = False,
+                 weight_decay: float = 0.0, max_grad_norm: float | None = None, lr_schedule: dict | None = None,
+                 skip_nonfinite: bool = False):
+        schedule = check_optimizer_options("sgd", lr, weight_decay, momentum, nesterov, max_grad_norm, lr_schedule)
+        self.lr, self.momentum, self.nesterov, self.weight_decay = float(lr), float(momentum), bool(nesterov), float(weight_decay)
+        self.controlled = True
+        self._init_flat(flat_params, _Controls(flat_params.flat.device, "sgd", self.lr, schedule, max_grad_norm, skip_nonfinite,
+                                               weight_decay=self.weight_decay, momentum=self.momentum, nesterov=self.nesterov))
+        self.momentum_buffer = torch.zeros_like(flat_params.flat) if self.momentum != 0 else None
+
+    def step(self, reduce: bool = True, grads=None) -> None:
+        """Gradient pack (+ the one all-reduce of a multi-rank group; the norm is taken after it, the same on every rank) and the update."""
+        if reduce:
+            self.fp.reducer(grads)
+        self._controls.step(self.fp, self.momentum_buffer, None, self.step_count)
+
+    def _state(self):
+        buf = (self.momentum_buffer,) if self.momentum_buffer is not None else ()
+        return (self.fp.flat,) + buf + (self.step_count, self._controls.scalars, self._controls.skipped)
+
+
+def make_optimizer(flat_params: FlatParameters, optimizer: str = "adam", lr: float = 1e-3, weight_decay: float = 0.0,
+                   momentum: float = 0.0, nesterov: bool = False, max_grad_norm: float | None = None,
+                   lr_schedule: dict | None = None, skip_nonfinite: bool = False):
+    """The flat optimizer ``train()``'s keywords name: ``FusedAdam`` ("adam": L2 weight decay; "adamw": decoupled) or ``FusedSGD``."""
+    check_optimizer_options(optimizer, lr, weight_decay, momentum, nesterov, max_grad_norm, lr_schedule)
+    if optimizer == "sgd":
+        return FusedSGD(flat_params, lr, momentum, nesterov, weight_decay, max_grad_norm, lr_schedule, skip_nonfinite)
+    return FusedAdam(flat_params, lr, weight_decay=weight_decay, decoupled_weight_decay=optimizer == "adamw",
+                     max_grad_norm=max_grad_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
 
 
 def padded_capacity(needed: int, current: int = 0, quantum: int = 256) -> int:
@@ -624,7 +790,9 @@ class _SampleStepper:
 
 
 def train(model, dataset, epochs, patience=5, output_path='weights', start_weights=None, *, capture: bool = True, lr: float = 1e-3,
-          capture_ragged_batches: bool = False):
+          capture_ragged_batches: bool = False, optimizer: str = "adam", weight_decay: float = 0.0, momentum: float = 0.0,
+          nesterov: bool = False, max_grad_norm: float | None = None, lr_schedule: dict | None = None,
+          skip_nonfinite: bool = False):
     """utils/train_model.py:8-81 (same positional arguments, files and log lines).  Returns a dict with the per-epoch
     average losses (the reference returns None; nothing in it reads the return value).
 
@@ -640,11 +808,22 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     steps of 256, nodes in steps of 32) that only grow, with at most ``MAX_PADDED_CAPTURES`` re-captures, after which a batch
     above the capacities runs eagerly on its own.  This form is used with ``capture_ragged_batches=True`` only: the eager
     ragged-batch step has not been timed against it on an MI355X yet (``tools/latency_ragged_batch.py`` does that), and the
-    default follows the measurement.  A short last batch always runs eagerly.  ``"batched"`` in the returned dict says which form ran."""
+    default follows the measurement.  A short last batch always runs eagerly.  ``"batched"`` in the returned dict says which form ran.
+
+    Training controls (DESIGN K22; all of them run inside a captured step, none reads the device back): ``optimizer`` "adam" (the
+    reference's, ``weight_decay`` as Adam's L2 term), "adamw" (decoupled decay) or "sgd" (``momentum``, ``nesterov``; the write-up's
+    update rule with neither); ``max_grad_norm`` clips the gradient's global norm; ``lr_schedule`` is a dict of ``lr_at``'s keywords
+    (``kind`` "constant" / "cosine" / "step", ``warmup_steps``, ``total_steps``, ``min_lr``, ``gamma``, ``every`` - counts in
+    optimizer steps); ``skip_nonfinite`` (implied by clipping) drops and counts a step whose gradient holds a NaN or an inf.
+    Unknown names and values that do not go together raise ValueError before anything is allocated.  The returned dict holds
+    per-epoch lists ``"lr"`` and ``"grad_norm"`` (of the epoch's last step; the norm before clipping, NaN when none is taken) and
+    the run's ``"skipped_steps"``, read with the epoch's loss."""
+    check_optimizer_options(optimizer, lr, weight_decay, momentum, nesterov, max_grad_norm, lr_schedule)
     if start_weights:
         model.load_state_dict(torch.load(start_weights, map_location="cpu"))           # :14-15
     dev = require_gpu_param(next(model.parameters()), "train")
-    optimizer = FusedAdam(FlatParameters(model), lr=lr)                                # :9
+    optimizer = make_optimizer(FlatParameters(model), optimizer, lr, weight_decay, momentum, nesterov, max_grad_norm, lr_schedule,
+                               skip_nonfinite)                                         # :9
     criterion = nn.CrossEntropyLoss()                                                  # :10
     journal = RunJournal(output_path, epochs, patience)
     shelf = CheckpointShelf(model, output_path)
@@ -656,7 +835,7 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     # pooling layers under a pooled read-out are captured like an un-pooled model)
     stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1 and not pooling_prevents_capture(model))
     stepper.capture_ragged_batches = stepper.capture and capture_ragged_batches
-    history = []
+    history, lr_history, norm_history, skipped_steps = [], [], [], 0
     # Belt and braces: the loop runs on a side stream, so that the eager steps in front of a capture never touch the
     # legacy default stream.  The capture itself no longer depends on it (CapturedTrainStep differentiates private
     # aliases of the parameters, see its docstring for the hipStreamEndCapture crash this used to be the only guard of).
@@ -674,6 +853,9 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
                 avg_loss = float(loss_sum.item()) / max(1, steps)                      # :47 (the epoch's one host sync)
                 stepper.check()  # replayed topology builds: node ids outside the graph raise here (models/GNN.py:18-20)
                 history.append(avg_loss)
+                lr_history.append(float(optimizer.current_lr.item()))                 # of the epoch's last step; the stream is idle
+                norm_history.append(float(optimizer.grad_norm.item()))
+                skipped_steps = int(optimizer.skipped_steps.item())
                 journal.epoch(epoch, avg_loss, time.time() - started)
                 if stopper.observe(avg_loss):                                          # :57-66
                     journal.saved("best", shelf.best(epoch))
@@ -686,6 +868,7 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     finally:
         torch.cuda.current_stream(dev).wait_stream(run_stream)
     return {"avg_loss": history, "best_loss": stopper.best, "log_path": journal.path,
+            "lr": lr_history, "grad_norm": norm_history, "skipped_steps": skipped_steps,
             "captured": stepper.captured is not None or stepper.captured_batch is not None, "batched": stepper.batched,
             "captured_any_topology": stepper.padded is not None,
             "captured_ragged": stepper.padded is not None and stepper.padded.node_capacity is not None,

@@ -907,6 +907,50 @@ int gnc_adam_step_hp64_f32(float* param, const float* grad, float* exp_avg, floa
                            double beta1, double beta2, float eps, float weight_decay, int64_t* step, float* scratch2,
                            void* stream);
 
+/* ---- controlled optimizer step: clipping, AdamW / SGD, learning-rate schedules (K22, csrc/optimizer_ctl.hip) ----
+ * Everything that steers an update lives on the device, so ONE captured step replays a schedule, clips and skips:
+ *   gnc_grad_sumsq_f32   sum of g * g over grad [n] into `partials` (GNC_GRAD_NORM_BLOCKS doubles), one double per workgroup
+ *                        of a FIXED grid (GNC_GRAD_NORM_PASS elements per grid pass): no atomics, the order - and so the bits -
+ *                        depend on n alone.  An fp32 x fp32 product is exact in double.
+ *   gnc_optimizer_ctl_step_f32   [the sum pass, when ctl->clip or ctl->check_nonfinite] + a one-workgroup control tick + one
+ *                        element launch.  The tick sums the partials in fixed order and derives, in double and rounded to fp32
+ *                        once, into `scalars` [GNC_OPT_SCALARS]: [0] step_size (Adam / AdamW: lr(t) / (1 - beta1^t); SGD: lr(t)),
+ *                        [1] sqrt(1 - beta2^t), [2] decay = 1 - lr(t) * weight_decay (AdamW, else 1), [3] clip_coef =
+ *                        min(1, max_grad_norm / (norm + 1e-6)) (1 without clipping), [4] lr(t), [5] the gradient norm BEFORE
+ *                        clipping (NaN when the sum pass did not run); t = *step + 1 is stored back to `step`.
+ *                        lr(t): base lr * (t / warmup_steps) for t <= warmup_steps, then constant, cosine to min_lr at
+ *                        total_steps (held afterwards) or lr * gamma^((t - warmup_steps) / every).
+ *                        A non-finite sum (with clip or check_nonfinite) SKIPS the step: `step`, the parameters and the state
+ *                        stay bit-unchanged, skipped[0] (a running count) is advanced and skipped[1] (this call's flag) set;
+ *                        [5] still reports the norm.  torch.nn.utils.clip_grad_norm_ would scale every gradient by NaN instead.
+ *                        The element launch reads g' = fl(clip_coef * g); `grad` itself is never written.
+ * state1 / state2: exp_avg / exp_avg_sq (Adam, AdamW), or the momentum buffer (zero-initialised; may be null when momentum
+ * == 0) / null (SGD).  param, grad and the state buffers 16-B aligned; `step` int64 [1], `skipped` int64 [2]. */
+enum { GNC_OPT_ADAM = 0, GNC_OPT_ADAMW = 1, GNC_OPT_SGD = 2 };
+enum { GNC_LR_CONSTANT = 0, GNC_LR_COSINE = 1, GNC_LR_STEP = 2 };
+#define GNC_GRAD_NORM_BLOCKS 256
+#define GNC_GRAD_NORM_PASS (GNC_GRAD_NORM_BLOCKS * 256 * 4)
+#define GNC_OPT_SCALARS 8
+
+typedef struct gnc_opt_ctl_t {
+  int32_t rule;            /* GNC_OPT_*                                                              */
+  int32_t schedule;        /* GNC_LR_*                                                               */
+  int32_t nesterov;        /* SGD: d = g + momentum * buf                                            */
+  int32_t clip;            /* scale the gradient to max_grad_norm (implies check_nonfinite)          */
+  int32_t check_nonfinite; /* skip the step when the gradient holds a NaN or an inf                  */
+  int32_t reserved;
+  int64_t warmup_steps, total_steps, every; /* in optimizer steps                                    */
+  double lr, min_lr, gamma, max_grad_norm;
+  double beta1, beta2, eps, weight_decay, momentum;
+} gnc_opt_ctl_t;
+
+int32_t gnc_sizeof_opt_ctl(void);
+int64_t gnc_grad_norm_pass(void);
+int32_t gnc_grad_norm_blocks(void);
+int gnc_grad_sumsq_f32(const float* grad, int64_t n, double* partials, void* stream);
+int gnc_optimizer_ctl_step_f32(float* param, const float* grad, float* state1, float* state2, int64_t n, const gnc_opt_ctl_t* ctl,
+                               int64_t* step, float* scalars, int64_t* skipped, double* partials, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
