@@ -16,9 +16,10 @@ import torch
 from . import image_to_graph as I2G
 from .MLP import MLP
 from .dataset import ImageTensorFolder
-from .train import check_optimizer_options, train
+from .train import check_optimizer_options, make_criterion, train
 
 TRAINING_CONTROLS = ("optimizer", "lr", "weight_decay", "momentum", "nesterov", "max_grad_norm", "lr_schedule", "skip_nonfinite")
+LOSS_CONTROLS = ("loss", "class_weight", "label_smoothing", "pos_weight", "metrics")
 
 
 def load_data(dataset_path, resize_value=128, batch_size=8):
@@ -31,11 +32,13 @@ def train_MLP(epochs=30, channels=3, resize_value=128, batch_size=8, hidden_laye
               **training_controls):
     """``main.py:21-29`` (``dataset_path`` is one addition: the reference hard-codes ``'dataset'``; ``training_controls`` the other:
     ``train``'s ``optimizer``, ``weight_decay``, ``momentum``, ``nesterov``, ``max_grad_norm``, ``lr_schedule``, ``skip_nonfinite``
-    and ``lr``, checked before the folder is read).  Returns ``train``'s dict with the model under ``"model"``."""
-    unknown = sorted(set(training_controls) - set(TRAINING_CONTROLS))
+    and ``lr``, and its loss keywords ``loss``, ``class_weight``, ``label_smoothing``, ``pos_weight`` and ``metrics``, all checked
+    before the folder is read).  Returns ``train``'s dict with the model under ``"model"``."""
+    unknown = sorted(set(training_controls) - set(TRAINING_CONTROLS) - set(LOSS_CONTROLS))
     if unknown:
-        raise ValueError(f"train_MLP: unknown training controls {unknown}; {TRAINING_CONTROLS} expected")
-    check_optimizer_options(**{k: v for k, v in training_controls.items() if k != "skip_nonfinite"})
+        raise ValueError(f"train_MLP: unknown training controls {unknown}; {TRAINING_CONTROLS + LOSS_CONTROLS} expected")
+    check_optimizer_options(**{k: v for k, v in training_controls.items() if k != "skip_nonfinite" and k not in LOSS_CONTROLS})
+    make_criterion(**{k: v for k, v in training_controls.items() if k in LOSS_CONTROLS})  # the check alone: train() makes its own
     loader = load_data(dataset_path, resize_value, batch_size)
     model = MLP(in_dim=channels * resize_value * resize_value, out_dim=len(loader.dataset.classes), hidden_layers=hidden_layers)
     history = train(model, loader, epochs, patience=5, output_path=output_path, **training_controls)

@@ -758,6 +758,49 @@ def readout_batched(y, graph_ptr, num_graphs, num_nodes, w1, b1, w2, b2, w3, b3)
     return _ReadoutBatched.apply(y, graph_ptr, int(num_graphs), int(num_nodes), w1, b1, w2, b2, w3, b3)
 
 
+class _ClassLoss(torch.autograd.Function):
+    """Loss head (csrc/class_loss.hip, K23): the forward launch returns the loss AND d loss / d logits (with the loss accumulator,
+    the confusion counts and the label check on the side); the backward is one multiply by the upstream gradient, on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, options, buffers):
+        need = ctx.needs_input_grad[0]
+        loss, dz = native.class_loss(logits, labels, with_gradient=need, **options, **buffers)
+        if need:
+            ctx.save_for_backward(dz)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        (dz,) = ctx.saved_tensors
+        return dz * grad_loss, None, None, None
+
+
+def class_loss(logits: torch.Tensor, labels: torch.Tensor, *, kind: str = "ce", class_weight: torch.Tensor | None = None,
+               label_smoothing: float = 0.0, pos_weight: float = 1.0, reduction: str = "mean", scale: float = 1.0,
+               status: torch.Tensor | None = None, loss_sum: torch.Tensor | None = None, confusion: torch.Tensor | None = None,
+               workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """0-dim loss of ``logits`` [G, C] float32 on the GPU and ``labels`` int64 [G] - or the reference's single-graph form, ``logits``
+    [C] with a 0-dim label (models/GNN.py:338-341).  ``kind="ce"``: ``F.cross_entropy(logits, labels, weight=class_weight,
+    label_smoothing=..., reduction=...)``; ``kind="bce"``: ``F.binary_cross_entropy_with_logits`` on ONE logit per sample with labels
+    0 / 1 smoothed to ``y (1 - s) + s / 2`` and ``pos_weight``; both times ``scale``.  Differentiable in ``logits`` (scoring only when
+    they need no gradient).  ``status`` (int32 [1]; made here when None) gets bit 0 when a label lies outside the classes - that sample
+    is left out; ``loss_sum`` / ``confusion`` / ``workspace``: see ``native.class_loss``."""
+    labels = torch.as_tensor(labels)
+    if logits.dim() == 1 and labels.dim() == 0:
+        logits, labels = logits.unsqueeze(0), labels.reshape(1)
+    if logits.dim() != 2 or labels.dim() != 1:
+        raise ValueError(f"class_loss: logits [G, C] with labels [G], or logits [C] with a 0-dim label, expected; got "
+                         f"{tuple(logits.shape)} and {tuple(labels.shape)}")
+    labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    options = dict(kind=kind, class_weight=class_weight, label_smoothing=label_smoothing, pos_weight=pos_weight, reduction=reduction,
+                   scale=scale)
+    buffers = dict(status=status, loss_sum=loss_sum, confusion=confusion, workspace=workspace)
+    return _ClassLoss.apply(logits, labels, options, buffers)
+
+
 class _GraphPool(torch.autograd.Function):
     """Global pooling read-out over the graphs of a block-diagonal batch (csrc/pool_readout.hip, K17): one launch (two for a few
     large graphs) forward, one streaming launch backward."""

@@ -25,6 +25,10 @@ GRAD_NORM_PASS = GRAD_NORM_BLOCKS * 256 * 4  # elements one grid pass of it cove
 OPT_SCALARS = 8                             # float32 scalars of a controlled step: step_size, bc2_sqrt, decay, clip_coef, lr, grad_norm
 OPT_RULES = {"adam": 0, "adamw": 1, "sgd": 2}
 LR_SCHEDULES = {"constant": 0, "cosine": 1, "step": 2}
+LOSS_KINDS = {"ce": 0, "bce": 1}            # GNC_LOSS_CE / GNC_LOSS_BCE
+LOSS_REDUCTIONS = {"mean": 0, "sum": 1}     # GNC_LOSS_MEAN / GNC_LOSS_SUM
+CLASS_LOSS_ONE_LAUNCH_ROWS = 64             # GNC_CLASS_LOSS_ONE_LAUNCH_ROWS: up to here the loss head is ONE kernel launch
+CLASS_LOSS_WORKSPACE_DOUBLES = 2 * 256 + 1  # GNC_CLASS_LOSS_WORKSPACE_DOUBLES: the larger batches' partials and the gradient's factor
 
 ACTIVATIONS = {  # nn.<Name> accepted by the reference's MLP(activation=...) (models/MLP.py:21)
     "ReLU": 0, "Identity": 1, "Tanh": 2, "Sigmoid": 3, "SiLU": 4, "GELU": 5, "LeakyReLU": 6, "ELU": 7,
@@ -185,6 +189,10 @@ _SIGNATURES = {
     "gnc_grad_sumsq_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p]),
     "gnc_optimizer_ctl_step_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    "gnc_class_loss_workspace_doubles": (c_int32, []),
+    "gnc_class_loss_launches": (c_int32, [c_int64, c_int32]),
+    "gnc_class_loss_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_double, c_double, c_int32, c_double,
+                                     c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -285,6 +293,9 @@ def load_library() -> ctypes.CDLL:
     if lib.gnc_grad_norm_pass() != GRAD_NORM_PASS or lib.gnc_grad_norm_blocks() != GRAD_NORM_BLOCKS:
         raise RuntimeError(f"{LIB_NAME}: the gradient-norm grid is {lib.gnc_grad_norm_blocks()} workgroups of "
                            f"{lib.gnc_grad_norm_pass()} elements per pass in C, not {GRAD_NORM_BLOCKS} / {GRAD_NORM_PASS}")
+    if lib.gnc_class_loss_workspace_doubles() != CLASS_LOSS_WORKSPACE_DOUBLES or lib.gnc_class_loss_launches(CLASS_LOSS_ONE_LAUNCH_ROWS, 1) != 1:
+        raise RuntimeError(f"{LIB_NAME}: the loss head's workspace is {lib.gnc_class_loss_workspace_doubles()} doubles in C, not "
+                           f"{CLASS_LOSS_WORKSPACE_DOUBLES}, or {CLASS_LOSS_ONE_LAUNCH_ROWS} rows are not one launch")
     _lib = lib
     return lib
 
@@ -2209,3 +2220,59 @@ def optimizer_ctl_step(param: torch.Tensor, grad: torch.Tensor, state1: torch.Te
         _check(_launch("optimizer_ctl", param, lambda: lib.gnc_optimizer_ctl_step_f32(
             param.data_ptr(), grad.data_ptr(), ptr(state1), ptr(state2), n, ctypes.byref(ctl), step.data_ptr(), scalars.data_ptr(),
             skipped.data_ptr(), ptr(partials), _stream(param)), (12.0 + state_bytes + 4.0 * use_norm) * n), "gnc_optimizer_ctl_step_f32")
+
+
+# --------------------------------------------------------------------------- classification loss head (K23)
+def class_loss(logits: torch.Tensor, labels: torch.Tensor, *, status: torch.Tensor, kind: str = "ce", class_weight: torch.Tensor | None = None,
+               label_smoothing: float = 0.0, pos_weight: float = 1.0, reduction: str = "mean", scale: float = 1.0,
+               with_gradient: bool = True, loss_sum: torch.Tensor | None = None, confusion: torch.Tensor | None = None,
+               workspace: torch.Tensor | None = None):
+    """``(loss float32 [1], dlogits float32 [G, C] | None)`` of ``logits`` [G, C] and ``labels`` int64 [G] (include/gnc_hip.h,
+    csrc/class_loss.hip): ``kind`` "ce" (``class_weight`` float32 [C] or None, ``label_smoothing``) or "bce" (C == 1, labels 0 / 1,
+    ``pos_weight``), ``reduction`` "mean" / "sum", the loss and its gradient multiplied by ``scale``.  ``with_gradient=False`` scores
+    only.  ``loss_sum`` (float64, one element) += the returned loss; ``confusion`` (int64 [K, K], K = C or 2 for "bce") += the counts,
+    rows = label, columns = predicted class; ``status`` (int32 [1]) |= 1 when a label lies outside the classes (such a row is left
+    out of everything and its gradient row is zeros).  Up to ``CLASS_LOSS_ONE_LAUNCH_ROWS`` rows all of it is ONE kernel launch;
+    more rows need ``workspace`` (float64 [CLASS_LOSS_WORKSPACE_DOUBLES]; made here when None)."""
+    lib = load_library()
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"class_loss: kind {kind!r}: one of {sorted(LOSS_KINDS)} expected")
+    if reduction not in LOSS_REDUCTIONS:
+        raise ValueError(f"class_loss: reduction {reduction!r}: one of {sorted(LOSS_REDUCTIONS)} expected")
+    _require_cuda(logits, labels, status, class_weight, loss_sum, confusion, workspace)
+    z = _rowmajor(logits.detach())
+    G, C = z.shape
+    K = 2 if kind == "bce" else C
+    if kind == "bce" and C != 1:
+        raise ValueError(f"class_loss: kind 'bce' takes ONE logit per sample, got {C}")
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.numel() != G or not labels.is_contiguous():
+        raise ValueError(f"class_loss: labels must be contiguous int64 [{G}]")
+    if class_weight is not None and (kind == "bce" or class_weight.dtype != torch.float32 or class_weight.shape != (C,)
+                                     or not class_weight.is_contiguous()):
+        raise ValueError(f"class_loss: class_weight must be contiguous float32 [{C}], with kind 'ce'")
+    if status.dtype != torch.int32 or status.numel() < 1:
+        raise ValueError("class_loss: status must be int32 [1]")
+    if loss_sum is not None and (loss_sum.dtype != torch.float64 or loss_sum.numel() != 1):
+        raise ValueError("class_loss: loss_sum must be one float64 element")
+    if confusion is not None and (confusion.dtype != torch.int64 or confusion.shape != (K, K) or not confusion.is_contiguous()):
+        raise ValueError(f"class_loss: confusion must be contiguous int64 [{K}, {K}]")
+    dev = z.device
+    if G > CLASS_LOSS_ONE_LAUNCH_ROWS and workspace is None:
+        workspace = torch.empty(CLASS_LOSS_WORKSPACE_DOUBLES, dtype=torch.float64, device=dev)
+    if workspace is not None and (workspace.dtype != torch.float64 or workspace.numel() < CLASS_LOSS_WORKSPACE_DOUBLES
+                                  or not workspace.is_contiguous()):
+        raise ValueError(f"class_loss: workspace must be float64 [{CLASS_LOSS_WORKSPACE_DOUBLES}]")
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dz = torch.empty(G, C, dtype=torch.float32, device=dev) if with_gradient else None
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _check(_launch("class_loss", z, lambda: lib.gnc_class_loss_f32(
+            z.data_ptr(), _ld(z), labels.data_ptr(), ptr(class_weight), G, C, LOSS_KINDS[kind], float(label_smoothing), float(pos_weight),
+            LOSS_REDUCTIONS[reduction], float(scale), loss.data_ptr(), ptr(dz), C, ptr(loss_sum), ptr(confusion), status.data_ptr(),
+            ptr(workspace), _stream(z)), (8.0 if with_gradient else 4.0) * G * C + 8.0 * G), "gnc_class_loss_f32")
+    return loss, dz
+
+
+def class_loss_launches(num_rows: int, with_gradient: bool = True) -> int:
+    """Kernel launches of one ``class_loss`` call (one ``KernelTimers`` entry either way)."""
+    return int(load_library().gnc_class_loss_launches(int(num_rows), int(bool(with_gradient))))

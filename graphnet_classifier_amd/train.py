@@ -11,6 +11,9 @@ dataset order (:35-45), average training loss per epoch, early stopping on it (:
 * AdamW, SGD, gradient clipping by the global norm, learning-rate schedules (``lr_at``) and a skip on non-finite gradients are
   keyword options of ``train()`` (``FusedAdam``'s options, ``FusedSGD``): their scalars live on the device, so a captured step
   replays them (``native.optimizer_ctl_step``, DESIGN K22); the default stays the reference's optimizer;
+* ``loss="ce"`` / ``"bce"`` replace ``CrossEntropyLoss`` by the device loss head (``loss.ClassificationLoss``, DESIGN K23): class
+  weights, label smoothing or the write-up's binary cross-entropy, with loss, gradient, the loss accumulator, the training
+  confusion counts (``metrics=True``) and a label check in ONE launch of the captured step; the default stays the reference's loss;
 * the running loss is accumulated on the device (float64 scalar) and read once per epoch, where the reference
   synchronises on ``loss.item()`` after every sample (:44);
 * when consecutive samples share one topology (pixel / patch graphs: the edge list depends on the image size only,
@@ -45,6 +48,7 @@ from .GNN import (CapturedRaggedBatchForward, CombinedModel, FixedGraphFeed, Pad
                   _has_batchnorm, _no_capture_with_pooling, _same_topology, flatten_readout_rows, graph_logits,
                   pooling_prevents_capture, ragged_batch_logits)
 from .MLP import require_gpu_param
+from .loss import ClassificationLoss, accuracy_of, check_loss_options
 from .sharding import FlatGradAllReduce
 from .synthetic import GraphBatch
 
@@ -293,6 +297,30 @@ def make_optimizer(flat_params: FlatParameters, optimizer: str = "adam", lr: flo
                      max_grad_norm=max_grad_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
 
 
+def make_criterion(loss=None, class_weight=None, label_smoothing: float = 0.0, pos_weight: float | None = None, metrics: bool = False):
+    """The criterion ``train()``'s keywords name: ``nn.CrossEntropyLoss()`` for ``loss=None`` (no other option may be given then), a
+    ``ClassificationLoss`` for "ce" / "bce", or the ``ClassificationLoss`` instance passed in (the options then live in it;
+    ``metrics`` switches its counting on).  ValueError before anything is allocated."""
+    named = [name for name, given in (("class_weight", class_weight is not None), ("label_smoothing", label_smoothing != 0.0),
+                                      ("pos_weight", pos_weight is not None)) if given]
+    if loss is None:
+        if named or metrics:
+            raise ValueError(f"{named + ['metrics'] if metrics else named}: options of the device loss head; pass loss='ce' or 'bce' "
+                             f"(loss=None is the reference's nn.CrossEntropyLoss())")
+        return nn.CrossEntropyLoss()
+    if isinstance(loss, ClassificationLoss):
+        if named:
+            raise ValueError(f"{named}: set these on the ClassificationLoss instance that was passed")
+        loss.track_metrics = loss.track_metrics or bool(metrics)
+        if loss.track_metrics and loss.num_classes is not None and loss.confusion is None:
+            loss.confusion = torch.zeros(loss.num_classes, loss.num_classes, dtype=torch.int64, device=loss.status.device)
+        return loss
+    if not isinstance(loss, str):
+        raise ValueError(f"loss {loss!r}: None, 'ce', 'bce' or a ClassificationLoss expected")
+    check_loss_options(loss, class_weight, label_smoothing, pos_weight)
+    return ClassificationLoss(loss, class_weight, label_smoothing, pos_weight, track_metrics=metrics)
+
+
 def padded_capacity(needed: int, current: int = 0, quantum: int = 256) -> int:
     """Capacity of a padded capture for ``needed`` edges (or nodes): ``current`` while that still fits, otherwise half as
     much again as needed, rounded up to ``quantum`` - room to spare, so that a data set whose sizes vary around a typical
@@ -306,6 +334,17 @@ def padded_capacity(needed: int, current: int = 0, quantum: int = 256) -> int:
 
 def _world(group=None) -> int:
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+
+
+def _step_loss(criterion, logits, labels, loss_sum: torch.Tensor, loss_scale: float = 1.0):
+    """``(loss, accumulated)`` of one step: a ``ClassificationLoss`` takes the scale into its launch and, bound to ``loss_sum``, adds
+    the loss there itself (``accumulated``); any other callable is called as it always was and the caller accumulates."""
+    if isinstance(criterion, ClassificationLoss):
+        return criterion(logits, labels, scale=loss_scale), criterion.accumulates_into(loss_sum)
+    loss = criterion(logits, labels)
+    if loss_scale != 1.0:
+        loss = loss * loss_scale
+    return loss, False
 
 
 class _Through(nn.Module):
@@ -400,9 +439,7 @@ class CapturedTrainStep(_Captured):
 
         def one_step():  # closes over no ``self``: the object that keeps it (``_record``) must not become a reference cycle
             out, status = torch.func.functional_call(through, alias, ())
-            loss = criterion(out, label)
-            if loss_scale != 1.0:
-                loss = loss * loss_scale
+            loss, accumulated = _step_loss(criterion, out, label, loss_sum, loss_scale)
             for leaf in leaves:                                                        # utils/train_model.py:40
                 leaf.grad = None
             loss.backward()                                                            # :41
@@ -411,7 +448,8 @@ class CapturedTrainStep(_Captured):
                 fp.reducer.pack(grads)
             else:
                 optimizer.step(grads=grads)                                            # :42 (pack + fused Adam)
-            loss_sum.add_(loss.detach().double())
+            if not accumulated:
+                loss_sum.add_(loss.detach().double())
             return status
 
         def warm():
@@ -422,10 +460,14 @@ class CapturedTrainStep(_Captured):
                 leaf.grad = None
 
         snap = optimizer.state_snapshot()
+        tracked = criterion if isinstance(criterion, ClassificationLoss) else None  # its counts and flag must not see the warm-up
+        criterion_snap = tracked.state_snapshot() if tracked is not None else None
         buffers = [(b, b.clone()) for b in model.buffers()]  # BatchNorm statistics must not absorb the warm-up either
         keep = loss_sum.clone()
         self._status = self._record(fp.flat.device, one_step, 3, warm, capture_error_mode)
         optimizer.state_restore(snap)
+        if tracked is not None:
+            tracked.state_restore(criterion_snap)
         with torch.no_grad():
             for b, saved in buffers:
                 b.copy_(saved)
@@ -535,11 +577,13 @@ class RunJournal:
         with open(self.path, mode) as f:
             f.write("".join(line + "\n" for line in lines))
 
-    def epoch(self, number: int, avg_loss: float, seconds: float) -> None:
+    def epoch(self, number: int, avg_loss: float, seconds: float, accuracy: float | None = None) -> None:
+        """``accuracy``: the epoch's training accuracy, added to the loss line when the run tracks metrics (not in the reference)."""
         tag = f"Epoch {number}/{self.epochs}"
-        print(f"{tag}, avg_loss={avg_loss:.4f}")
+        line = f"{tag}, avg_loss={avg_loss:.4f}" + (f", accuracy={accuracy:.4f}" if accuracy is not None else "")
+        print(line)
         print(f"epoch: {number} needed {seconds} time")
-        self._append([f"{tag}, avg_loss={avg_loss:.4f}", f"{tag}, needed {seconds / 60:.2f} minutes"])
+        self._append([line, f"{tag}, needed {seconds / 60:.2f} minutes"])
 
     def saved(self, kind: str, path: str) -> None:
         print(f"Saved {kind} model: {path}")
@@ -760,11 +804,12 @@ class _SampleStepper:
             self._previous_batch = sample + (batch.graph_ptr,)
         x, pos = batch.x.to(dev, non_blocking=True), batch.pos.to(dev, non_blocking=True)
         logits = self._batch_forward(batch)(self.model, x, pos, batch.edge_index)
-        loss = self.criterion(logits, torch.as_tensor(labels).to(dev, non_blocking=True))
+        loss, accumulated = _step_loss(self.criterion, logits, torch.as_tensor(labels).to(dev, non_blocking=True), self.loss_sum)
         self.optimizer.zero_grad()
         loss.backward()
         self.optimizer.step()
-        self.loss_sum += loss.detach().double()
+        if not accumulated:
+            self.loss_sum += loss.detach().double()
 
     def __call__(self, sample, label) -> None:
         dev = self.device
@@ -782,17 +827,19 @@ class _SampleStepper:
         else:
             sample = sample.to(dev, non_blocking=True)
         logits = self.model(sample)                                                            # utils/train_model.py:37
-        loss = self.criterion(logits, torch.as_tensor(label).to(dev, non_blocking=True))      # :38
+        loss, accumulated = _step_loss(self.criterion, logits, torch.as_tensor(label).to(dev, non_blocking=True), self.loss_sum)  # :38
         self.optimizer.zero_grad()                                                             # :40
         loss.backward()                                                                        # :41
         self.optimizer.step()                                                                  # :42
-        self.loss_sum += loss.detach().double()                                                # :44, without the per-sample sync
+        if not accumulated:
+            self.loss_sum += loss.detach().double()                                            # :44, without the per-sample sync
 
 
 def train(model, dataset, epochs, patience=5, output_path='weights', start_weights=None, *, capture: bool = True, lr: float = 1e-3,
           capture_ragged_batches: bool = False, optimizer: str = "adam", weight_decay: float = 0.0, momentum: float = 0.0,
           nesterov: bool = False, max_grad_norm: float | None = None, lr_schedule: dict | None = None,
-          skip_nonfinite: bool = False):
+          skip_nonfinite: bool = False, loss=None, class_weight=None, label_smoothing: float = 0.0, pos_weight: float | None = None,
+          metrics: bool = False):
     """utils/train_model.py:8-81 (same positional arguments, files and log lines).  Returns a dict with the per-epoch
     average losses (the reference returns None; nothing in it reads the return value).
 
@@ -817,18 +864,30 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     optimizer steps); ``skip_nonfinite`` (implied by clipping) drops and counts a step whose gradient holds a NaN or an inf.
     Unknown names and values that do not go together raise ValueError before anything is allocated.  The returned dict holds
     per-epoch lists ``"lr"`` and ``"grad_norm"`` (of the epoch's last step; the norm before clipping, NaN when none is taken) and
-    the run's ``"skipped_steps"``, read with the epoch's loss."""
+    the run's ``"skipped_steps"``, read with the epoch's loss.
+
+    Loss (DESIGN K23): ``loss=None`` is the reference's ``nn.CrossEntropyLoss()`` on PyTorch's own ops, launch for launch as before.
+    ``loss="ce"`` / ``"bce"`` - or a ``loss.ClassificationLoss`` instance - selects the device loss head, ONE launch per step for loss,
+    gradient and the epoch's loss accumulator: ``class_weight`` (one weight per class) and ``label_smoothing`` for "ce";
+    ``pos_weight`` and ``label_smoothing`` for "bce", the write-up's binary cross-entropy on a model with ONE logit
+    (``CombinedModel(classes=1)``), labels 0 / 1.  ``metrics=True`` counts every training sample into a confusion matrix inside that
+    launch: the returned dict gains per-epoch ``"accuracy"`` and ``"confusion"`` (int64 [K, K] tensors, rows = true class), read
+    with the epoch's one host read and reset per epoch, and the log line gains the accuracy.  A label outside the classes raises
+    IndexError at the end of its epoch.  Any of these options with ``loss=None`` is a ValueError."""
     check_optimizer_options(optimizer, lr, weight_decay, momentum, nesterov, max_grad_norm, lr_schedule)
+    criterion = make_criterion(loss, class_weight, label_smoothing, pos_weight, metrics)          # :10
     if start_weights:
         model.load_state_dict(torch.load(start_weights, map_location="cpu"))           # :14-15
     dev = require_gpu_param(next(model.parameters()), "train")
     optimizer = make_optimizer(FlatParameters(model), optimizer, lr, weight_decay, momentum, nesterov, max_grad_norm, lr_schedule,
                                skip_nonfinite)                                         # :9
-    criterion = nn.CrossEntropyLoss()                                                  # :10
     journal = RunJournal(output_path, epochs, patience)
     shelf = CheckpointShelf(model, output_path)
     stopper = PlateauStopper(patience)
     loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+    head = criterion if isinstance(criterion, ClassificationLoss) else None
+    if head is not None:
+        head.bind_loss_sum(loss_sum)
     # this loop steps one rank's model on its own samples: with a multi-rank process group up, a captured step would
     # record (or, under gloo, host-stage) a collective per sample that nothing here asked for
     # (a model whose top-K pooling reads sizes back in its forward: no capture can record it, every step runs eagerly; padded
@@ -836,6 +895,7 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     stepper = _SampleStepper(model, optimizer, criterion, loss_sum, dev, capture and _world() == 1 and not pooling_prevents_capture(model))
     stepper.capture_ragged_batches = stepper.capture and capture_ragged_batches
     history, lr_history, norm_history, skipped_steps = [], [], [], 0
+    accuracy_history, confusion_history = [], []
     # Belt and braces: the loop runs on a side stream, so that the eager steps in front of a capture never touch the
     # legacy default stream.  The capture itself no longer depends on it (CapturedTrainStep differentiates private
     # aliases of the parameters, see its docstring for the hipStreamEndCapture crash this used to be the only guard of).
@@ -846,17 +906,32 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
             for epoch in range(1, epochs + 1):
                 started = time.time()
                 loss_sum.zero_()
+                if head is not None:
+                    head.reset_metrics()
                 steps = 0
                 for sample, label in dataset:                                          # :35
                     stepper(sample, label)
                     steps += 1
-                avg_loss = float(loss_sum.item()) / max(1, steps)                      # :47 (the epoch's one host sync)
+                accuracy = None
+                if head is not None and head.status is not None:  # the loss, the label flag and the counts in ONE host read
+                    parts = [loss_sum.reshape(1), head.status.double()] + ([head.confusion.reshape(-1).double()] if metrics else [])
+                    stats = torch.cat(parts).cpu()
+                    avg_loss = float(stats[0]) / max(1, steps)
+                    if int(stats[1]) & 1:
+                        head.check()  # raises IndexError (and clears the flag)
+                    if metrics:
+                        K = head.num_classes
+                        confusion_history.append(stats[2:].round().to(torch.int64).view(K, K))
+                        accuracy = accuracy_of(confusion_history[-1])
+                        accuracy_history.append(accuracy)
+                else:
+                    avg_loss = float(loss_sum.item()) / max(1, steps)                  # :47 (the epoch's one host sync)
                 stepper.check()  # replayed topology builds: node ids outside the graph raise here (models/GNN.py:18-20)
                 history.append(avg_loss)
                 lr_history.append(float(optimizer.current_lr.item()))                 # of the epoch's last step; the stream is idle
                 norm_history.append(float(optimizer.grad_norm.item()))
                 skipped_steps = int(optimizer.skipped_steps.item())
-                journal.epoch(epoch, avg_loss, time.time() - started)
+                journal.epoch(epoch, avg_loss, time.time() - started, accuracy)
                 if stopper.observe(avg_loss):                                          # :57-66
                     journal.saved("best", shelf.best(epoch))
                 if stopper.exhausted:                                                  # :67-69
@@ -867,7 +942,8 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
             journal.close(stopper.best, final_path)
     finally:
         torch.cuda.current_stream(dev).wait_stream(run_stream)
-    return {"avg_loss": history, "best_loss": stopper.best, "log_path": journal.path,
+    extra = {"accuracy": accuracy_history, "confusion": confusion_history} if metrics else {}
+    return {**extra, "avg_loss": history, "best_loss": stopper.best, "log_path": journal.path,
             "lr": lr_history, "grad_norm": norm_history, "skipped_steps": skipped_steps,
             "captured": stepper.captured is not None or stepper.captured_batch is not None, "batched": stepper.batched,
             "captured_any_topology": stepper.padded is not None,
@@ -921,12 +997,13 @@ def _logits_of(model, sample, dev):
     return logits.unsqueeze(0) if logits.dim() == 1 else logits
 
 
-def predict(model, loader, *, capture: bool = True):
+def predict(model, loader, *, capture: bool = True, binary: bool = False):
     """``(logits [n, C], probabilities [n, C])`` of every sample of ``loader`` in loader order, on the model's device - the pair
     ``utils/inference.py:68-71`` returns per image (softmax over the classes).  ``loader`` yields ``(sample, label)`` with a
     single graph or a ``GraphBatch`` (``GraphImageFolder.loader(shuffle=False, batch_size=...)``); labels are not read.
     ``capture``: ragged mini-batches (superpixel graphs) replay a captured forward (``_BatchScorer``); an edge list that leaves
-    its graph raises IndexError at the end."""
+    its graph raises IndexError at the end.  ``binary``: the model has ONE logit z per sample (trained with ``loss="bce"``) and the
+    probabilities are ``[1 - sigmoid(z), sigmoid(z)]``, shape [n, 2]."""
     dev = require_gpu_param(next(model.parameters()), "predict")
     with torch.no_grad():
         score = _BatchScorer(model, dev, capture)
@@ -935,16 +1012,51 @@ def predict(model, loader, *, capture: bool = True):
             raise ValueError("predict: the loader yielded nothing")
         logits = torch.cat(rows)
         score.check()
+        if binary:
+            if logits.size(1) != 1:
+                raise ValueError(f"predict(binary=True): a model with ONE logit per sample expected, got {logits.size(1)}")
+            return logits, torch.cat([torch.sigmoid(-logits), torch.sigmoid(logits)], dim=1)
         return logits, torch.softmax(logits, dim=-1)
 
 
-def evaluate(model, loader, *, capture: bool = True):
+def _evaluate_with_head(model, loader, capture: bool, criterion: ClassificationLoss, dev):
+    """``evaluate`` on the device loss head: per batch ONE launch in scoring mode adds the batch's summed loss to a float64
+    accumulator and its counts to a confusion matrix; one host read at the end."""
+    head = ClassificationLoss(criterion.kind, criterion._class_weight, criterion.label_smoothing,
+                              criterion.pos_weight if criterion.kind == "bce" else None, reduction="sum", track_metrics=True)
+    loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+    head.bind_loss_sum(loss_sum)
+    count = 0
+    with torch.no_grad():
+        score = _BatchScorer(model, dev, capture)
+        for sample, label in loader:
+            labels = torch.as_tensor(label).to(dev, non_blocking=True).reshape(-1)
+            head(score(sample), labels)
+            count += int(labels.numel())
+        if head.confusion is None:
+            raise ValueError("evaluate: the loader yielded nothing")
+        stats = torch.cat([loss_sum, head.status.double(), head.confusion.reshape(-1).double()]).cpu()  # the one host read
+        score.check()
+    if int(stats[1]) & 1:
+        raise IndexError(f"evaluate: a label lies outside the {head.num_classes} classes [0, {head.num_classes})")
+    confusion = stats[2:].round().to(torch.int64).view(head.num_classes, head.num_classes)
+    return {"loss": float(stats[0]) / count, "accuracy": float(confusion.diagonal().sum()) / count, "confusion": confusion,
+            "count": count}
+
+
+def evaluate(model, loader, *, capture: bool = True, criterion=None):
     """Scores ``model`` on every sample of ``loader`` (either loader form) under ``no_grad``: ``{"loss": mean cross-entropy over
     the samples, "accuracy", "confusion": int64 [C, C] with rows = true class and columns = predicted class, "count"}``.
     Loss and confusion matrix are accumulated on the device (integer scatter-adds, float64 loss) and read ONCE at the end.
     ``capture``: ragged mini-batches (superpixel graphs) replay a captured forward (``_BatchScorer``); an edge list that leaves
-    its graph raises IndexError at the end."""
+    its graph raises IndexError at the end.  ``criterion``: a ``loss.ClassificationLoss`` - loss and counts then come from ONE launch of
+    the device loss head per batch (scoring mode), with ITS definition of the loss (kind, class weights, smoothing, pos_weight), summed
+    over the samples and divided by their number; the criterion's own counts and accumulator are not touched."""
     dev = require_gpu_param(next(model.parameters()), "evaluate")
+    if criterion is not None:
+        if not isinstance(criterion, ClassificationLoss):
+            raise TypeError("evaluate(criterion=...): a ClassificationLoss (or None) expected")
+        return _evaluate_with_head(model, loader, capture, criterion, dev)
     loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
     confusion, count = None, 0
     with torch.no_grad():

@@ -951,6 +951,35 @@ int gnc_grad_sumsq_f32(const float* grad, int64_t n, double* partials, void* str
 int gnc_optimizer_ctl_step_f32(float* param, const float* grad, float* state1, float* state2, int64_t n, const gnc_opt_ctl_t* ctl,
                                int64_t* step, float* scalars, int64_t* skipped, double* partials, void* stream);
 
+/* ---- classification loss head: weighted / smoothed cross-entropy, binary cross-entropy, training metrics (K23, csrc/class_loss.hip) ----
+ * gnc_class_loss_f32: logits fp32 [G, C] (row stride ld_logits), labels int64 [G], class_weight fp32 [C] or null (w = 1).
+ *   GNC_LOSS_CE   torch.nn.CrossEntropyLoss(weight=w, label_smoothing=s):  lp = log_softmax(z_i), W = sum_c w_c,
+ *                 row_i = -(1 - s) w[y_i] lp[y_i] - (s / C) sum_c w_c lp[c];  den = sum_i w[y_i] (MEAN) or 1 (SUM)
+ *   GNC_LOSS_BCE  binary_cross_entropy_with_logits(z, t, pos_weight=pw) on ONE logit per row (C == 1, class_weight null), labels
+ *                 0 or 1, t_i = y_i (1 - s) + s / 2:  row_i = pw t_i softplus(-z_i) + (1 - t_i) softplus(z_i);  den = rows (MEAN)
+ *   loss [1] = scale * sum_i row_i / den;  dlogits [G, C] (row stride ld_dlogits; null: scoring only) = d loss / d logits.
+ *   loss_sum (double [1], or null) += the returned fp32 loss.  confusion (int64 [K, K], or null; K = C, BCE: 2; rows = the label)
+ *   += the counts of (label, predicted class): argmax_c z_ic with the lowest index on ties (BCE: z > 0), inside [0, K) whatever the
+ *   logits hold.  status (int32 [1]) |= 1 when a label lies outside [0, K): that row adds nothing to loss, den, the counts, and its
+ *   dlogits row is zeros; nothing is indexed with the label.  den == 0: loss and dlogits are 0.
+ * Rows in fp32 (accurate exp / log), sums over rows in double in an order that (G, C) alone decide; no floating-point atomics.
+ * With GNC_LOSS_SUM a row's dlogits have the same bits alone and inside any batch.
+ * G <= GNC_CLASS_LOSS_ONE_LAUNCH_ROWS: ONE kernel launch, `workspace` may be null.  Above: rows pass, one-workgroup tick, gradient
+ * pass (gnc_class_loss_launches tells), over `workspace` (GNC_CLASS_LOSS_WORKSPACE_DOUBLES doubles, overwritten).
+ * Nothing is allocated or synchronised. */
+enum { GNC_LOSS_CE = 0, GNC_LOSS_BCE = 1 };
+enum { GNC_LOSS_MEAN = 0, GNC_LOSS_SUM = 1 };
+#define GNC_CLASS_LOSS_ONE_LAUNCH_ROWS 64 /* == GNC_PAD_BATCH_MAX_GRAPHS: every captured mini-batch */
+#define GNC_CLASS_LOSS_BLOCKS 256
+#define GNC_CLASS_LOSS_WORKSPACE_DOUBLES (2 * GNC_CLASS_LOSS_BLOCKS + 1)
+
+int32_t gnc_class_loss_workspace_doubles(void);
+int32_t gnc_class_loss_launches(int64_t G, int32_t with_gradient);
+int gnc_class_loss_f32(const float* logits, int64_t ld_logits, const int64_t* labels, const float* class_weight, int64_t G, int64_t C,
+                       int32_t kind, double label_smoothing, double pos_weight, int32_t reduction, double scale, float* loss,
+                       float* dlogits, int64_t ld_dlogits, double* loss_sum, int64_t* confusion, int32_t* status, double* workspace,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
