@@ -20,6 +20,9 @@ dataset order (:35-45), average training loss per epoch, early stopping on it (:
   utils/image_to_graph/image_to_graph_optimized.py:42-47) the whole step - forward, loss, backward, gradient pack,
   Adam - is captured into a hipGraph once and replayed per sample (``CapturedTrainStep``): one launch per step
   instead of ~150;
+* when every sample brings a NEW topology (superpixel graphs, single or in mini-batches) the step is captured over padded
+  buffers that any sample up to a capacity fits; ONE rule, ``_PaddedCaptures``, says when such a capture is made, grown and
+  checked, for the training loop and for ``evaluate`` / ``predict``;
 * a loader that yields ``(synthetic.GraphBatch, labels [B])`` (``GraphImageFolder.loader(batch_size=B)``) is stepped once per
   mini-batch through ``CombinedModel.forward_batched`` - mean cross-entropy over the batch, captured when consecutive full
   batches share a topology; ``evaluate`` / ``predict`` score a model over either loader form;
@@ -38,6 +41,7 @@ import numbers
 import os
 import time
 from datetime import datetime
+from typing import Callable, NamedTuple
 
 import torch
 import torch.distributed as dist
@@ -554,8 +558,6 @@ class CapturedTensorStep(CapturedTrainStep):
         self.replay()
 
 
-
-
 # --------------------------------------------------------------------------- the run's side effects
 class RunJournal:
     """Everything the reference's train() writes or prints besides checkpoints: the timestamped
@@ -634,49 +636,115 @@ class CheckpointShelf:
         return self._write("final_model.pth")
 
 
-class _RaggedBatchCaptures:
-    """When a ragged mini-batch gets a capture, shared by the training loop and ``evaluate`` / ``predict``: ``get(batch, previous)``
-    returns the capture object that serves ``batch``, or None for a batch that runs eagerly.
+def _batched_forward(model, batch: GraphBatch, dev):
+    """``forward(mod, x, pos, edge_index) -> logits [G, C]`` of a mini-batch, for the eager step, a capture's ``forward=`` and the
+    scorers alike: the ``num_graphs`` form for graphs of exactly ``num_nodes`` nodes on a model without ``ragged_readout`` and
+    without top-K pooling (behind it the flatten read-out needs the offsets), else the ``graph_ptr`` form (a device copy made
+    here, once)."""
+    sizes = batch.graph_ptr[1:] - batch.graph_ptr[:-1]
+    pooling = bool(getattr(getattr(model, "graph_net", None), "pooling", False))
+    if not getattr(model, "ragged_readout", False) and not pooling and bool((sizes == model.num_nodes).all()):
+        G = batch.num_graphs
+        return lambda mod, xx, pp, ee: mod.forward_batched(xx, pp, ee, num_graphs=G)
+    gptr = batch.graph_ptr.to(dev)
+    return lambda mod, xx, pp, ee: mod.forward_batched(xx, pp, ee, graph_ptr=gptr)
 
-    A capture is made for a batch with the graph count and feature widths of the batch before it but ANOTHER topology
-    (superpixel graphs), on a ``CombinedModel`` without BatchNorm layers and with at most ``native.PAD_BATCH_MAX_GRAPHS`` graphs.
-    Capacities come from ``padded_capacity`` (edges in steps of 256, nodes in steps of 32) and only grow.  A batch that outgrows
-    the capture is captured again - the old object's ``check()`` runs first, its flags would be lost with it - at most
-    ``limit`` captures in all; after that the capture stays for every batch that fits and an oversize batch runs eagerly on
-    its own.  A batch with another graph count (a short last batch) runs eagerly."""
 
-    def __init__(self, model, make, limit: int):
-        self.make, self.limit = make, limit  # make(batch, *args, edge_capacity=, node_capacity=) -> the capture object
-        self.allowed = isinstance(model, CombinedModel) and not _has_batchnorm(model)
+def _forward_of(model, sample, dev):
+    """The model's output for one loader item, inputs moved to ``dev``: a ``GraphBatch`` through ``forward_batched``, an
+    ``(x, pos, edge_index)`` graph or a plain tensor through ``model(sample)``."""
+    if isinstance(sample, GraphBatch):
+        x, pos = sample.x.to(dev, non_blocking=True), sample.pos.to(dev, non_blocking=True)
+        return _batched_forward(model, sample, dev)(model, x, pos, sample.edge_index)
+    if isinstance(sample, (tuple, list)) and len(sample) == 3:
+        # edge_index stays where it is: a host tensor is looked up in the topology cache by content, so equal
+        # topologies are sorted once, not once per sample
+        return model((sample[0].to(dev, non_blocking=True), sample[1].to(dev, non_blocking=True), sample[2]))
+    return model(sample.to(dev, non_blocking=True))
+
+
+def _repeats(previous, parts) -> bool:
+    """``parts`` = ``(x, pos, edge_index, graph_ptr or None)`` of a sample with the shapes, the graph offsets and the topology of
+    ``previous``: what ONE fixed-topology capture serves."""
+    return (previous[0].shape == parts[0].shape and previous[1].shape == parts[1].shape
+            and (parts[3] is None or torch.equal(previous[3], parts[3])) and _same_topology(previous[2], parts[2]))
+
+
+def _kind_and_size(parts):
+    """``((graph count, feature widths), nodes, edges)`` of a sample's parts."""
+    x, pos, edge_index, graph_ptr = parts
+    graphs = 1 if graph_ptr is None else graph_ptr.numel() - 1
+    return (graphs, tuple(x.shape[1:]), tuple(pos.shape[1:])), int(x.size(0)), int(edge_index.size(1))
+
+
+class _SampleKind(NamedTuple):
+    """What ``_PaddedCaptures`` is told about the samples it serves."""
+    parts: Callable    # sample -> (x, pos, edge_index, graph_ptr or None): its kind, node count and edge count are read there
+    allowed: bool      # this model's step can run over padded buffers
+    nodes_vary: bool   # a sample may have another node count than the one before it
+    node_form: bool    # ... and the first capture has node slots to spare already (else the edge-only form, until a count differs)
+    repeats: bool      # a sample that repeats the eager one before it is eligible too (else it is a fixed-topology capture's case)
+
+
+def _batches(model) -> _SampleKind:
+    return _SampleKind(lambda b: (b.x, b.pos, b.edge_index, b.graph_ptr), isinstance(model, CombinedModel) and not _has_batchnorm(model),
+                       True, True, False)
+
+
+def _single_graphs(model) -> _SampleKind:  # the stepper tries the fixed-topology capture before it asks
+    return _SampleKind(lambda s: (*s, None), hasattr(model, "graph_net") and hasattr(model, "classifier") and not _has_batchnorm(model),
+                       bool(getattr(model, "ragged_readout", False)), False, True)
+
+
+class _PaddedCaptures:
+    """THE rule for serving a stream of new topologies from one padded capture that only grows - single graphs and mini-batches in
+    the training loop, mini-batches in ``evaluate`` / ``predict``, each with an instance (and so a capture count) of its own:
+    ``get(sample, previous)`` returns the capture object that serves ``sample``, or None for a sample that runs eagerly.
+
+    The capture that matches is returned.  Otherwise a capture is made for an eligible sample only: on an ``allowed`` model, one
+    of the kind (graph count, at most ``native.PAD_BATCH_MAX_GRAPHS``, and feature widths) of the eager sample before it or of
+    the capture it outgrew.  Capacities come from ``padded_capacity`` (edges in steps of 256, nodes in steps of 32): the first
+    capture is sized from the larger of the two samples, a later one from the sample that outgrew the capture, and no capacity
+    ever shrinks.  The capture that is replaced is checked first (``check()``: its flags would be lost with it); at most ``limit``
+    captures are made, after which the capture stays for every sample that fits and an oversize sample runs eagerly on its own,
+    as a sample of another kind does (a short last batch).  In the edge-only form (``node_capacity=None``) another node count is
+    ineligible, or - where ``nodes_vary`` - turns every later capture to the node-capacity form, with room for the node count
+    that the edge-only captures served."""
+
+    def __init__(self, model, make, limit: int, kind=_batches):
+        self.make, self.limit = make, limit  # make(sample, *args, edge_capacity=, node_capacity=) -> the capture object
+        self.parts, self.allowed, self.nodes_vary, self.node_form, self.repeats = kind(model)
         self.current = None
         self.captures = 0
         self.edge_capacity = self.node_capacity = 0
+        self._kind, self._nodes = None, 0  # of the samples the current capture was made for; the largest node count among them
 
-    def get(self, batch, previous, *args):
-        """``previous``: ``(x, pos, edge_index, graph_ptr)`` of the last batch that ran eagerly, or None; ``args`` go to ``make``
-        behind the batch (the labels of a training step)."""
+    def get(self, sample, previous, *args):
+        """``previous``: the parts ``(x, pos, edge_index, graph_ptr or None)`` of the last sample that ran eagerly, or None;
+        ``args`` go to ``make`` behind the sample (the labels of a training step)."""
         cur = self.current
-        if cur is not None and cur.matches(batch):
+        if cur is not None and cur.matches(sample):
             return cur
-        widths = (tuple(batch.x.shape[1:]), tuple(batch.pos.shape[1:]))
-        if cur is not None:  # outgrown: same graph count and widths, above a capacity
-            eligible = batch.num_graphs == cur.num_graphs and widths == cur.feed.feature_shapes
-            need_nodes, need_edges = batch.num_nodes, batch.num_edges
+        if not self.allowed or self.captures >= self.limit:
+            return None
+        parts = self.parts(sample)
+        kind, nodes, edges = _kind_and_size(parts)
+        if cur is not None:  # outgrown, if it is of the capture's kind
+            known, seen_nodes, seen_edges = self._kind, self._nodes, 0
+        elif previous is not None and (self.repeats or not _repeats(previous, parts)):
+            known, seen_nodes, seen_edges = _kind_and_size(previous)
         else:
-            eligible = (previous is not None and previous[3].numel() == batch.graph_ptr.numel()
-                        and (tuple(previous[0].shape[1:]), tuple(previous[1].shape[1:])) == widths
-                        and not (previous[0].shape == batch.x.shape and torch.equal(previous[3], batch.graph_ptr)
-                                 and _same_topology(previous[2], batch.edge_index)))
-            if eligible:
-                need_nodes = max(int(previous[0].size(0)), batch.num_nodes)
-                need_edges = max(int(previous[2].size(1)), batch.num_edges)
-        if not (self.allowed and eligible and batch.num_graphs <= native.PAD_BATCH_MAX_GRAPHS and self.captures < self.limit):
+            return None
+        node_form = self.node_form or (self.nodes_vary and nodes != seen_nodes)
+        if kind != known or kind[0] > native.PAD_BATCH_MAX_GRAPHS or not (node_form or nodes == seen_nodes):
             return None
         if cur is not None:
             cur.check()
-        self.edge_capacity = padded_capacity(need_edges, self.edge_capacity)
-        self.node_capacity = padded_capacity(need_nodes, self.node_capacity, 32)
-        self.current = self.make(batch, *args, edge_capacity=self.edge_capacity, node_capacity=self.node_capacity)
+        self._kind, self._nodes, self.node_form = kind, max(nodes, seen_nodes), node_form
+        self.edge_capacity = padded_capacity(max(edges, seen_edges), self.edge_capacity)
+        if node_form:
+            self.node_capacity = padded_capacity(self._nodes, self.node_capacity, 32)
+        self.current = self.make(sample, *args, edge_capacity=self.edge_capacity, node_capacity=self.node_capacity if node_form else None)
         self.captures += 1
         return self.current
 
@@ -686,66 +754,63 @@ class _RaggedBatchCaptures:
 
 
 class _SampleStepper:
-    """Runs one optimizer step per sample: eagerly, or - once two consecutive samples have shared a topology - as a
-    replay of the captured step."""
+    """Runs one optimizer step per sample: the replay of a captured step where one serves the sample, the eager step otherwise.
+    A sample that repeats the eager one before it gets the ONE capture of its topology (single graph, mini-batch) or shape
+    (tensor batch), replayed while samples match it; every other graph or mini-batch is served under ``_PaddedCaptures``."""
+
+    MAX_PADDED_CAPTURES = 4  # a dataset whose sizes keep outgrowing the capacity runs its oversize samples eagerly
 
     def __init__(self, model, optimizer, criterion, loss_sum, device, capture: bool):
         self.model, self.optimizer, self.criterion, self.loss_sum, self.device = model, optimizer, criterion, loss_sum, device
         self.capture = capture
-        self.captured: CapturedTrainStep | None = None
-        self.padded: CapturedTrainStep | None = None
-        self._padded_captures = 0
-        self._edge_capacity = self._node_capacity = 0  # of the node-capacity captures made so far
-        self._previous = None
-        self.captured_batch: CapturedTrainStep | None = None  # mini-batches (GraphBatch samples)
-        self._previous_batch = None
-        self.captured_tensor: CapturedTensorStep | None = None  # plain tensor samples (the image-MLP baseline)
-        self._previous_tensor = None
-        self.batched = False
         self.capture_ragged_batches = capture  # ragged mini-batches (superpixel graphs): CapturedRaggedBatchStep
-        self.ragged = _RaggedBatchCaptures(
+        self.batched = False
+        # one topology / one shape each: single graphs, mini-batches, plain tensor batches (the image-MLP baseline)
+        self.captured = self.captured_batch = self.captured_tensor = None
+        self._previous = self._previous_batch = self._previous_tensor = None  # of the last sample of the kind that ran eagerly
+        self.padded = _PaddedCaptures(  # single graphs with a new topology each (superpixel graphs)
+            model, lambda sample, label, **capacities: CapturedTrainStep(model, optimizer, criterion, sample, label, loss_sum,
+                                                                         **capacities),
+            self.MAX_PADDED_CAPTURES, _single_graphs)
+        self.ragged = _PaddedCaptures(  # mini-batches of them
             model, lambda batch, labels, **capacities: CapturedRaggedBatchStep(model, optimizer, criterion, batch, labels, loss_sum,
                                                                                **capacities),
-            self.MAX_PADDED_CAPTURES)  # a counter of their own
+            self.MAX_PADDED_CAPTURES)
 
-    MAX_PADDED_CAPTURES = 4  # a dataset whose edge counts keep outgrowing the capacity goes back to eager steps
-
-    def _try_replay(self, sample, label) -> bool:
-        prev = self._previous
-        same_nodes = prev is not None and prev[0].shape == sample[0].shape and prev[1].shape == sample[1].shape
-        if self.captured is None and same_nodes and _same_topology(prev[2], sample[2]):
+    def _replay_graph(self, sample, label) -> bool:
+        """A single graph: the fixed-topology capture first, so topologies that repeat keep their own capture."""
+        parts = (*sample, None)
+        if self.captured is None and self._previous is not None and _repeats(self._previous, parts):
             self.captured = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum)
-        if self.captured is not None and self.captured.matches(sample):
-            self.captured(sample, label)
-            return True
-        # a NEW topology over the same node count (superpixel graphs): the padded form, topology build inside the graph;
-        # with the model's ragged read-out also another node count (SLIC's segment count varies per image): node capacity
-        same_features = prev is not None and prev[0].shape[1:] == sample[0].shape[1:] and prev[1].shape[1:] == sample[1].shape[1:]
-        ragged = bool(getattr(self.model, "ragged_readout", False)) and same_features and (
-            not same_nodes or (self.padded is not None and self.padded.node_capacity is not None) or self._node_capacity > 0)
-        if self.padded is not None and not self.padded.matches(sample) and (
-                ragged or sample[0].size(0) == self.padded.num_nodes):
-            self.padded = None  # more edges (or nodes) than the capacity: capture again with room to spare
-        if (self.padded is None and (same_nodes or ragged) and self._padded_captures < self.MAX_PADDED_CAPTURES
-                and hasattr(self.model, "graph_net") and hasattr(self.model, "classifier")
-                and not _has_batchnorm(self.model)):
-            if ragged:  # capacities only grow from one capture to the next
-                self._edge_capacity = padded_capacity(max(int(prev[2].size(1)), int(sample[2].size(1))), self._edge_capacity)
-                self._node_capacity = padded_capacity(max(int(prev[0].size(0)), int(sample[0].size(0))), self._node_capacity, 32)
-                self.padded = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum,
-                                                edge_capacity=self._edge_capacity, node_capacity=self._node_capacity)
-            else:
-                capacity = padded_capacity(max(int(prev[2].size(1)), int(sample[2].size(1))))
-                self.padded = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, label, self.loss_sum,
-                                                edge_capacity=capacity)
-            self._padded_captures += 1
-        if self.padded is not None and self.padded.matches(sample):
-            self.padded(sample, label)
-            return True
-        self._previous = sample
-        return False
+        fixed = self.captured is not None and self.captured.matches(sample)
+        step = self.captured if fixed else self.padded.get(sample, self._previous, label)
+        if step is None:
+            self._previous = parts
+            return False
+        step(sample, label)
+        return True
 
-    def _try_replay_tensor(self, sample: torch.Tensor, label) -> bool:
+    def _replay_batch(self, batch, labels) -> bool:
+        """A mini-batch (mean cross-entropy over the batch): the fixed-topology capture when it has the topology of the batch
+        before it (pixel / patch graphs of one size: every full batch), else the ragged-batch capture (superpixel graphs)."""
+        sample = (batch.x, batch.pos, batch.edge_index)
+        parts = sample + (batch.graph_ptr,)
+        if self.captured_batch is None and self._previous_batch is not None and _repeats(self._previous_batch, parts):
+            self.captured_batch = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, labels, self.loss_sum,
+                                                    forward=_batched_forward(self.model, batch, self.device))
+            self._captured_graph_ptr = batch.graph_ptr.clone()
+        if (self.captured_batch is not None and torch.equal(self._captured_graph_ptr, batch.graph_ptr)
+                and self.captured_batch.matches(sample)):
+            self.captured_batch(sample, labels)
+            return True
+        step = self.ragged.get(batch, self._previous_batch, labels) if self.capture_ragged_batches else None
+        if step is None:
+            self._previous_batch = parts
+            return False
+        step(batch, labels)
+        return True
+
+    def _replay_tensor(self, sample: torch.Tensor, label) -> bool:
         """A plain tensor sample: captured once two consecutive samples share shape and dtype (and label shape), replayed while
         they keep doing so; anything else (the first sample, a short last batch) is left to the eager step.  Only this package's
         ``MLP`` is captured: its forward is a function of the input buffer and the parameters alone, on the device, which is what
@@ -763,71 +828,22 @@ class _SampleStepper:
         return False
 
     def check(self) -> None:
-        if self.padded is not None:
-            self.padded.check()
+        self.padded.check()
         self.ragged.check()
 
-    def _batch_forward(self, batch):
-        """``forward(model, x, pos, edge_index) -> logits [G, C]`` of a mini-batch: the ``num_graphs`` form for graphs of exactly
-        ``num_nodes`` nodes on a model without ``ragged_readout``, else the ``graph_ptr`` form (a device copy made here, once)."""
-        G = batch.num_graphs
-        sizes = batch.graph_ptr[1:] - batch.graph_ptr[:-1]
-        if not getattr(self.model, "ragged_readout", False) and bool((sizes == self.model.num_nodes).all()):
-            return lambda mod, xx, pp, ee: mod.forward_batched(xx, pp, ee, num_graphs=G)
-        gptr = batch.graph_ptr.to(self.device)
-        return lambda mod, xx, pp, ee: mod.forward_batched(xx, pp, ee, graph_ptr=gptr)
-
-    def _step_batch(self, batch, labels) -> None:
-        """One optimizer step on a mini-batch (``synthetic.GraphBatch``, labels [B]): mean cross-entropy over the batch.  A
-        replay of the captured step when this batch has the topology of the one before it (pixel / patch graphs of one size:
-        every full batch); a replay of the captured ragged-batch step when it has the graph count of the one before it but
-        another topology (superpixel graphs); an eager step otherwise (a short last batch, the first batch of a kind)."""
-        dev = self.device
-        self.batched = True
-        sample = (batch.x, batch.pos, batch.edge_index)
-        if self.capture:
-            prev = self._previous_batch
-            if (self.captured_batch is None and prev is not None and prev[0].shape == sample[0].shape
-                    and prev[1].shape == sample[1].shape and torch.equal(prev[3], batch.graph_ptr) and _same_topology(prev[2], sample[2])):
-                self.captured_batch = CapturedTrainStep(self.model, self.optimizer, self.criterion, sample, labels, self.loss_sum,
-                                                        forward=self._batch_forward(batch))
-                self._captured_graph_ptr = batch.graph_ptr.clone()
-            if (self.captured_batch is not None and torch.equal(self._captured_graph_ptr, batch.graph_ptr)
-                    and self.captured_batch.matches(sample)):
-                self.captured_batch(sample, labels)
-                return
-            if self.capture_ragged_batches:
-                step = self.ragged.get(batch, self._previous_batch, labels)
-                if step is not None:
-                    step(batch, labels)
-                    return
-            self._previous_batch = sample + (batch.graph_ptr,)
-        x, pos = batch.x.to(dev, non_blocking=True), batch.pos.to(dev, non_blocking=True)
-        logits = self._batch_forward(batch)(self.model, x, pos, batch.edge_index)
-        loss, accumulated = _step_loss(self.criterion, logits, torch.as_tensor(labels).to(dev, non_blocking=True), self.loss_sum)
-        self.optimizer.zero_grad()
-        loss.backward()
-        self.optimizer.step()
-        if not accumulated:
-            self.loss_sum += loss.detach().double()
-
     def __call__(self, sample, label) -> None:
-        dev = self.device
         if isinstance(sample, GraphBatch):
-            return self._step_batch(sample, label)
-        is_graph = isinstance(sample, (tuple, list)) and len(sample) == 3
-        if self.capture and is_graph and self._try_replay(sample, label):
-            return
-        if self.capture and isinstance(sample, torch.Tensor) and self._try_replay_tensor(sample, label):
-            return
-        if is_graph:
-            # edge_index stays where it is: a host tensor is looked up in the topology cache by content, so equal
-            # topologies are sorted once, not once per sample
-            sample = (sample[0].to(dev, non_blocking=True), sample[1].to(dev, non_blocking=True), sample[2])
+            self.batched = True
+            replay = self._replay_batch
+        elif isinstance(sample, (tuple, list)) and len(sample) == 3:
+            replay = self._replay_graph
         else:
-            sample = sample.to(dev, non_blocking=True)
-        logits = self.model(sample)                                                            # utils/train_model.py:37
-        loss, accumulated = _step_loss(self.criterion, logits, torch.as_tensor(label).to(dev, non_blocking=True), self.loss_sum)  # :38
+            replay = self._replay_tensor if isinstance(sample, torch.Tensor) else None
+        if self.capture and replay is not None and replay(sample, label):
+            return
+        logits = _forward_of(self.model, sample, self.device)                                  # utils/train_model.py:37
+        loss, accumulated = _step_loss(self.criterion, logits, torch.as_tensor(label).to(self.device, non_blocking=True),
+                                       self.loss_sum)                                          # :38
         self.optimizer.zero_grad()                                                             # :40
         loss.backward()                                                                        # :41
         self.optimizer.step()                                                                  # :42
@@ -844,18 +860,19 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     average losses (the reference returns None; nothing in it reads the return value).
 
     Mini-batches: a ``dataset`` that yields ``(synthetic.GraphBatch, labels [B])`` - ``GraphImageFolder.loader(batch_size=B)`` -
-    takes one optimizer step per batch through ``model.forward_batched`` (the ``num_graphs`` form for equal-size batches on a
-    model without ``ragged_readout``, otherwise ``graph_ptr``); the loss is ``CrossEntropyLoss()``'s mean over the batch
-    (:38 on a batched input, as the reference's image-MLP path with ``batch_size=8``, main.py:13-29) and the epoch average is
-    taken over steps (:47).  When consecutive full batches share one topology (pixel / patch graphs of one size) the step is
-    captured once and replayed (``"captured"`` in the returned dict).  When consecutive batches share only their graph count
-    (superpixel graphs: another region adjacency and other node counts in every batch) the step can be captured over padded buffers
-    (``CapturedRaggedBatchStep``; ``"captured_ragged_batch"``) and every such batch is ONE feed launch and the replay: for a
-    ``CombinedModel`` without BatchNorm layers and at most 64 graphs per batch, at capacities from ``padded_capacity`` (edges in
-    steps of 256, nodes in steps of 32) that only grow, with at most ``MAX_PADDED_CAPTURES`` re-captures, after which a batch
-    above the capacities runs eagerly on its own.  This form is used with ``capture_ragged_batches=True`` only: the eager
-    ragged-batch step has not been timed against it on an MI355X yet (``tools/latency_ragged_batch.py`` does that), and the
-    default follows the measurement.  A short last batch always runs eagerly.  ``"batched"`` in the returned dict says which form ran.
+    takes one optimizer step per batch through ``model.forward_batched`` (``_batched_forward`` picks the form); the loss is
+    ``CrossEntropyLoss()``'s mean over the batch (:38 on a batched input, as the reference's image-MLP path with
+    ``batch_size=8``, main.py:13-29) and the epoch average is taken over steps (:47).  ``"batched"`` in the returned dict says
+    which form ran.
+
+    Captures (``capture=True``): a single graph or a full mini-batch with the topology of the sample before it gets the ONE
+    capture of that topology (``"captured"`` in the returned dict; pixel / patch graphs of one size).  Samples that bring a new
+    topology each (superpixel graphs) are served from a padded capture under ``_PaddedCaptures``' rule, stated there: single
+    graphs (``"captured_any_topology"``; with a node capacity, for a ``ragged_readout`` model whose node counts vary,
+    ``"captured_ragged"``) and, with ``capture_ragged_batches=True`` only, mini-batches of one graph count
+    (``CapturedRaggedBatchStep``: ONE feed launch and the replay per batch; ``"captured_ragged_batch"``) - the eager ragged-batch
+    step has not been timed against it on an MI355X yet (``tools/latency_ragged_batch.py`` does that), and the default follows
+    the measurement.  A short last batch always runs eagerly.
 
     Training controls (DESIGN K22; all of them run inside a captured step, none reads the device back): ``optimizer`` "adam" (the
     reference's, ``weight_decay`` as Adam's L2 term), "adamw" (decoupled decay) or "sgd" (``momentum``, ``nesterov``; the write-up's
@@ -946,8 +963,8 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
     return {**extra, "avg_loss": history, "best_loss": stopper.best, "log_path": journal.path,
             "lr": lr_history, "grad_norm": norm_history, "skipped_steps": skipped_steps,
             "captured": stepper.captured is not None or stepper.captured_batch is not None, "batched": stepper.batched,
-            "captured_any_topology": stepper.padded is not None,
-            "captured_ragged": stepper.padded is not None and stepper.padded.node_capacity is not None,
+            "captured_any_topology": stepper.padded.current is not None,
+            "captured_ragged": stepper.padded.current is not None and stepper.padded.current.node_capacity is not None,
             "captured_ragged_batch": stepper.ragged.current is not None,
             "captured_tensor": stepper.captured_tensor is not None,
             "optimizer": optimizer}
@@ -956,13 +973,12 @@ def train(model, dataset, epochs, patience=5, output_path='weights', start_weigh
 # --------------------------------------------------------------------------- evaluation
 class _BatchScorer:
     """Logits of loader items for ``evaluate`` / ``predict``: ragged mini-batches replay a ``CapturedRaggedBatchForward`` under
-    the rule of the training loop (``_RaggedBatchCaptures``); same-topology batches and single graphs go through
-    ``_logits_of`` as they always did."""
+    the rule of the training loop (``_PaddedCaptures``); same-topology batches and single graphs (one row) run eagerly."""
 
     def __init__(self, model, dev, capture: bool):
         # pooling that reads sizes back: eager (no capture)
         self.model, self.dev, self.capture = model, dev, capture and not pooling_prevents_capture(model)
-        self.ragged = _RaggedBatchCaptures(
+        self.ragged = _PaddedCaptures(
             model, lambda batch, **capacities: CapturedRaggedBatchForward(model, batch, **capacities),
             _SampleStepper.MAX_PADDED_CAPTURES)
         self._previous = None
@@ -973,28 +989,11 @@ class _BatchScorer:
             if forward is not None:
                 return forward(sample).clone()  # the capture's output buffer is rewritten by the next replay
             self._previous = (sample.x, sample.pos, sample.edge_index, sample.graph_ptr)
-        return _logits_of(self.model, sample, self.dev)
+        logits = _forward_of(self.model, sample, self.dev)
+        return logits.unsqueeze(0) if logits.dim() == 1 else logits
 
     def check(self) -> None:
         self.ragged.check()
-
-
-def _logits_of(model, sample, dev):
-    """Logits [B, C] of one loader item: a ``GraphBatch`` through ``forward_batched``, an ``(x, pos, edge_index)`` graph through
-    ``model(sample)`` (one row)."""
-    if isinstance(sample, GraphBatch):
-        x, pos = sample.x.to(dev, non_blocking=True), sample.pos.to(dev, non_blocking=True)
-        sizes = sample.graph_ptr[1:] - sample.graph_ptr[:-1]
-        pooling = bool(getattr(getattr(model, "graph_net", None), "pooling", False))  # the flatten read-out then needs the offsets
-        if not getattr(model, "ragged_readout", False) and not pooling and bool((sizes == model.num_nodes).all()):
-            return model.forward_batched(x, pos, sample.edge_index, num_graphs=sample.num_graphs)
-        return model.forward_batched(x, pos, sample.edge_index, graph_ptr=sample.graph_ptr)
-    if isinstance(sample, (tuple, list)) and len(sample) == 3:
-        sample = (sample[0].to(dev, non_blocking=True), sample[1].to(dev, non_blocking=True), sample[2])
-    else:
-        sample = sample.to(dev, non_blocking=True)
-    logits = model(sample)
-    return logits.unsqueeze(0) if logits.dim() == 1 else logits
 
 
 def predict(model, loader, *, capture: bool = True, binary: bool = False):

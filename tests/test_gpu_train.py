@@ -416,6 +416,25 @@ def test_any_topology_captured_training_matches_eager_training(G, tmp_path):
     assert close >= 0.97 * total, (close, total)
 
 
+@pytest.mark.parametrize("capture", [False, True])
+def test_a_replaced_capture_reports_its_bad_edge_list(G, tmp_path, capture):
+    """A device edge list that names a row outside its graph raises the IndexError of models/GNN.py:18-20 from train() - also
+    when the padded capture that replayed it (and whose feed holds the flag) is outgrown and replaced before the epoch ends."""
+    from graphnet_classifier_amd.train import train
+    g = load_golden("g8_training_run.npz")
+    ds = [(tuple(v.to(DEV) for v in sample), label) for sample, label in _random_graph_dataset(64, 6, seed=11)]
+    x, pos, ei = ds[3][0]
+    bad = ei.clone()
+    bad[1, 5] = 64 + 1  # a dummy row of the 512-slot feed (64 of them behind the 64 nodes): inside its buffers, not a node
+    ds[3] = ((x, pos, bad), ds[3][1])
+    x, pos, _ = ds[4][0]
+    ds[4] = ((x, pos, torch.randint(0, 64, (2, 600), device=DEV)), ds[4][1])  # outgrows the capture
+    m = G.CombinedModel(G.GraphNet(**_kwargs(g)), num_nodes=64, classes=2)
+    m.load_state_dict(sub_state_dict(g, "before/"), strict=True)
+    with pytest.raises(IndexError):
+        train(m, ds, 1, patience=5, output_path=str(tmp_path), capture=capture)
+
+
 def test_any_topology_captured_step_limits_and_flags(G):
     from graphnet_classifier_amd.train import CapturedTrainStep, FlatParameters, FusedAdam
     g = load_golden("g8_training_run.npz")
