@@ -4,7 +4,9 @@ over ``torchvision.datasets.ImageFolder``) on the device path.
 ``GraphImageFolder(dataset_path, resize_value, diagonals, method, n_segments, patch_size, use_cache)`` finds images
 by torchvision's ``ImageFolder`` rules and yields ``((x, pos, edge_index), label)`` as the reference's
 ``__getitem__`` does, with the tensors already on the GPU.  It is a ``torch.utils.data.Dataset``, so ``main.py``'s
-``DataLoader(ds, batch_size=1, shuffle=True, collate_fn=lambda b: b[0])`` works unchanged.
+``DataLoader(ds, batch_size=1, shuffle=True, collate_fn=lambda b: b[0])`` works unchanged.  Behind the reference's own
+parameters, ``edges="knn"`` (with ``knn_k`` and ``knn_pos_weight``) swaps a method's edge list for the k nearest neighbours of
+every node in (colour, position), ``image_to_graph.graphs_from_images``' option (DESIGN K24); ``edges=None`` is the reference.
 
 ``GraphImageFolder.loader()`` is the fast way through an epoch: the same samples in the same order as that
 ``DataLoader`` (and the same draws from the global RNG), with decoding on a host thread pool and the resize and the
@@ -86,9 +88,10 @@ class GraphImageFolder(Dataset):
     out as ``torchvision.datasets.ImageFolder`` expects (``root/<class>/.../<image>``)."""
 
     def __init__(self, dataset_path='dataset', resize_value=128, diagonals=False, method='pixel', n_segments=100,
-                 patch_size=8, use_cache=True):
+                 patch_size=8, use_cache=True, edges=None, knn_k=8, knn_pos_weight=1.0):
         if method not in I2G.METHODS:
             raise ValueError(f"Unknown method: {method}")
+        I2G.check_edges(edges, knn_k)
         self.dataset_path = dataset_path
         self.classes, self.class_to_idx = find_classes(dataset_path)
         self.samples = make_dataset(dataset_path, self.class_to_idx)
@@ -99,6 +102,9 @@ class GraphImageFolder(Dataset):
         self.n_segments = n_segments
         self.patch_size = patch_size
         self.use_cache = use_cache
+        self.edges = edges  # None: the method's own edges; "knn": k nearest neighbours in (colour, position) (K24)
+        self.knn_k = knn_k
+        self.knn_pos_weight = knn_pos_weight
 
     def __len__(self):
         return len(self.samples)
@@ -106,7 +112,8 @@ class GraphImageFolder(Dataset):
     def _graphs(self, images):
         return I2G.graphs_from_images(images, self.method, resize_value=self.resize_value, diagonals=self.diagonals,
                                       use_cache=self.use_cache, n_segments=self.n_segments,
-                                      patch_size=self.patch_size)
+                                      patch_size=self.patch_size, edges=self.edges, knn_k=self.knn_k,
+                                      knn_pos_weight=self.knn_pos_weight)
 
     def __getitem__(self, idx):
         path, label = self.samples[idx]

@@ -939,6 +939,46 @@ def topk_pool(x: torch.Tensor, scores: torch.Tensor, topo, graph_ptr: torch.Tens
     return x_out, e_rows, topo_out, gp_out, kept
 
 
+def knn_graph(feat: torch.Tensor, k: int, graph_ptr=None, loop: bool = False, return_dist: bool = False, return_status: bool = False):
+    """k-nearest-neighbour edges (K24): ``edge_index`` int64 [2, k N] in which slot ``v k + j`` holds the ``j``-th nearest row of
+    ``v`` inside ``v``'s own graph as the sender and ``v`` as the receiver - receiver-major, in-degree exactly ``k``.  The distance is
+    the squared Euclidean one over the columns of ``feat`` [N, D] (device float32, D <= 16, a strided row is read where it lies),
+    summed in fp32 with ascending columns and no fused multiply-add; equal distances go to the smaller node id; ``loop`` admits the
+    node itself.  The result is a pure function of the features' bits: the same alone, inside any batch and twice.
+
+    ``graph_ptr``: int64 [G + 1] on the host (tensor, list) or the device; None is one graph.  On the host a graph with fewer than
+    ``k`` candidates raises ``ValueError`` before anything is launched.  On the device nothing is read back: such a graph leaves -1
+    in its unfillable slots and sets ``native.KNN_FEW_CANDIDATES`` in the status word, a NaN distance sets
+    ``native.KNN_NAN_DISTANCE``; ``return_status=True`` appends that int32 [1] device tensor to the result.  One launch, no host
+    synchronisation, capturable.  Not differentiable: indices come back, ``feat.requires_grad`` is ignored.
+
+    Returns ``edge_index``, or a tuple ``(edge_index[, dist][, status])`` with ``dist`` float32 [k N] when asked."""
+    if not isinstance(feat, torch.Tensor) or feat.dim() != 2:
+        raise ValueError("knn_graph: feat must be a [N, D] tensor")
+    feat = feat.detach()
+    native._knn_feat(feat, k, "knn_graph")
+    N = feat.size(0)
+    if graph_ptr is None:
+        graph_ptr = [0, N]
+    if not isinstance(graph_ptr, torch.Tensor) or not graph_ptr.is_cuda:
+        host = torch.as_tensor(graph_ptr, dtype=torch.int64).reshape(-1)
+        if host.numel() < 2 or int(host[0]) != 0 or int(host[-1]) != N or bool((host[1:] < host[:-1]).any()):
+            raise ValueError(f"knn_graph: graph_ptr must ascend from 0 to the {N} rows of feat")
+        sizes = host[1:] - host[:-1]
+        need = k if loop else k + 1
+        small = torch.nonzero((sizes < need) & (sizes > 0)).reshape(-1)
+        if small.numel():
+            g = int(small[0])
+            raise ValueError(f"knn_graph: graph {g} has {int(sizes[g])} nodes, fewer than the {need} that k = {k} needs"
+                             f"{'' if loop else ' without self-loops'}")
+        graph_ptr = host.to(feat.device)
+    elif graph_ptr.dtype != torch.int64:
+        raise ValueError(f"knn_graph: graph_ptr must be int64, got {graph_ptr.dtype}")
+    edge_index, dist, status = native.knn_graph(feat, graph_ptr, k, loop=loop, return_dist=return_dist)
+    out = (edge_index,) + ((dist,) if return_dist else ()) + ((status,) if return_status else ())
+    return out[0] if len(out) == 1 else out
+
+
 def edge_features(pos: torch.Tensor, src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """[pos[dst]-pos[src], L1 norm] per edge (models/GNN.py:299-302).  ``pos`` is input data
     (utils/dataloader.py:50); gradients with respect to it are not provided."""

@@ -20,6 +20,7 @@ import functools
 import numpy as np
 import torch
 
+from . import functional as F
 from . import native
 from .MLP import default_device
 
@@ -66,8 +67,8 @@ def pixel_graph_from_array(img_u8: np.ndarray, diagonals: bool = False, use_cach
     return _pixel_graph(_to_device_u8(img_u8), diagonals, use_cache)
 
 
-def _pixel_graph(img: torch.Tensor, diagonals: bool, use_cache: bool):
-    """pixel graph of a device uint8 [H, W, C] image"""
+def _pixel_graph(img: torch.Tensor, diagonals: bool, use_cache: bool, with_edges: bool = True):
+    """pixel graph of a device uint8 [H, W, C] image (``with_edges=False``: the nodes alone, ``edge_index`` is None)"""
     lib = native.load_library()
     H, W, C = img.shape
     x = torch.empty(H * W, C, dtype=torch.float32, device=img.device)
@@ -75,6 +76,8 @@ def _pixel_graph(img: torch.Tensor, diagonals: bool, use_cache: bool):
     with torch.cuda.device(img.device):
         native._check(lib.gnc_pixel_nodes_f32(img.data_ptr(), H, W, C, x.data_ptr(), pos.data_ptr(),
                                               torch.cuda.current_stream(img.device).cuda_stream), "gnc_pixel_nodes_f32")
+    if not with_edges:
+        return x, pos, None
     ei = get_cached_edge_index(H, bool(diagonals)) if (use_cache and H == W) else create_grid_edges_optimized(H, W, diagonals)
     return x, pos, ei
 
@@ -88,8 +91,8 @@ def patch_graph_from_array(img_u8: np.ndarray, patch_size: int = 8):
     return _patch_graph(_to_device_u8(img_u8), patch_size)
 
 
-def _patch_graph(img: torch.Tensor, patch_size: int):
-    """patch graph of a device uint8 [H, W, C] image"""
+def _patch_graph(img: torch.Tensor, patch_size: int, with_edges: bool = True):
+    """patch graph of a device uint8 [H, W, C] image (``with_edges=False``: the nodes alone, ``edge_index`` is None)"""
     lib = native.load_library()
     H, W, C = img.shape
     nh, nw = H // patch_size, W // patch_size
@@ -98,7 +101,7 @@ def _patch_graph(img: torch.Tensor, patch_size: int):
     with torch.cuda.device(img.device):
         native._check(lib.gnc_patch_nodes_f32(img.data_ptr(), H, W, C, patch_size, x.data_ptr(), pos.data_ptr(),
                                               torch.cuda.current_stream(img.device).cuda_stream), "gnc_patch_nodes_f32")
-    return x, pos, create_grid_edges_optimized(nh, nw, False)
+    return x, pos, (create_grid_edges_optimized(nh, nw, False) if with_edges else None)
 
 
 def image_to_graph_patch(image_or_path, resize_value: int = 128, patch_size: int = 8):
@@ -234,19 +237,32 @@ def superpixel_graphs_batched(images_u8, labels=None, *, n_segments: int = 100, 
     return SuperpixelGraphBatch(x, pos, ei, counts)
 
 
-def _superpixel_graphs_from_device_batch(imgs: torch.Tensor, labels: torch.Tensor, node_capacity: int, edge_capacity: int):
+def _superpixel_graphs_from_device_batch(imgs: torch.Tensor, labels: torch.Tensor, node_capacity: int, edge_capacity: int, knn=None):
     """The loader's list of ``(x, pos, edge_index)`` for a device batch: one batched build, ONE host read of the sizes;
-    an image that does not fit the capacities (or a batch outside the kernel's supported set) takes the per-image path."""
+    an image that does not fit the capacities (or a batch outside the kernel's supported set) takes the per-image path.
+    ``knn = (k, pos_weight)``: the edges are the k nearest neighbours instead (K24), one more launch over the padded batch, off
+    its device node counts and in front of the same single host read."""
     B, H, W, _ = imgs.shape
+
+    def per_image(im, lab):
+        x, pos, ei = _superpixel_graph_from_device_labels(im, lab)
+        return (x, pos, ei) if knn is None else (x, pos, _knn_edges_of_graph(x, pos, "superpixel", H, *knn))
+
     if native.load_library().gnc_rag_batched_workspace_bytes(B, H, W, node_capacity, edge_capacity) == 0:
-        return [_superpixel_graph_from_device_labels(im, lab) for im, lab in zip(imgs, labels)]
+        return [per_image(im, lab) for im, lab in zip(imgs, labels)]
     batch = superpixel_graphs_batched(imgs, labels, node_capacity=node_capacity, edge_capacity=edge_capacity)
+    if knn is not None:
+        k = knn[0]
+        knn_ei, _, _ = native.knn_graph_padded(knn_features(batch.x, batch.pos, "superpixel", H, knn[1]), batch.counts, k)
     graphs = []
     for b, (s, e, bad, overflow) in enumerate(batch.counts.tolist()):  # the chunk's one host sync
         if bad:
             raise ValueError("label image has values outside [0, H*W)")
         if overflow:
-            graphs.append(_superpixel_graph_from_device_labels(imgs[b], labels[b]))
+            graphs.append(per_image(imgs[b], labels[b]))
+        elif knn is not None:
+            _check_knn_nodes(s, k)
+            graphs.append((batch.x[b, :s].contiguous(), batch.pos[b, :s].contiguous(), knn_ei[b, :, :k * s].contiguous()))
         else:  # contiguous copies: the topology cache and the capture's copies see what the per-image path hands them
             graphs.append((batch.x[b, :s].contiguous(), batch.pos[b, :s].contiguous(), batch.edge_index[b, :, :e].contiguous()))
     return graphs
@@ -406,7 +422,8 @@ METHODS = ("pixel", "patch", "superpixel")
 
 def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128, diagonals: bool = False,
                        use_cache: bool = True, n_segments: int = 100, patch_size: int = 8, compactness: float = 10, *,
-                       node_capacity: int | None = None, edge_capacity: int | None = None):
+                       node_capacity: int | None = None, edge_capacity: int | None = None, edges=None, knn_k: int = 8,
+                       knn_pos_weight: float = 1.0):
     """Graphs of a batch of decoded uint8 RGB images ``[H_i, W_i, 3]`` (any sizes): a list of ``(x, pos, edge_index)``
     equal to ``image_to_graph_pixel_optimized`` / ``image_to_graph_patch`` / ``image_to_graph_superpixel`` of each
     image, with arguments named as ``utils/dataloader.py``'s ``OptimizedDatasetLoader``.  The resize of the whole
@@ -414,17 +431,73 @@ def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128
     (``superpixel_graphs_batched`` at capacities derived from ``n_segments``) with ONE host synchronisation per call for
     the graphs' sizes, which depend on the data; pixel and patch nodes are one launch per image.  A superpixel image
     that does not fit the capacities is built by the per-image path (one more synchronisation each);
-    ``node_capacity`` / ``edge_capacity`` override the derived capacities (the result does not depend on them)."""
+    ``node_capacity`` / ``edge_capacity`` override the derived capacities (the result does not depend on them).
+
+    ``edges="knn"`` (K24) keeps every method's nodes (``x``, ``pos`` bit for bit) and replaces its edge list by the ``knn_k``
+    nearest neighbours of each node in ``knn_features`` (colour next to ``knn_pos_weight`` x position): ``knn_k n`` edges,
+    receiver-major.  One more launch per chunk and no further host synchronisation: superpixel chunks run the padded kNN entry
+    off the batch's device counts in front of the one host read, pixel and patch chunks one call over the collated nodes.  A
+    graph with ``n <= knn_k`` nodes raises ``ValueError``.  ``edges=None`` is the method's own edge list."""
     if method not in METHODS:
         raise ValueError(f"Unknown method: {method}")
+    check_edges(edges, knn_k)
     if len(images_u8) == 0:
         return []
     imgs = resize(list(images_u8), (resize_value, resize_value))
-    if method == "pixel":
-        return [_pixel_graph(im, diagonals, use_cache) for im in imgs]
-    if method == "patch":
-        return [_patch_graph(im, patch_size) for im in imgs]
+    if method in ("pixel", "patch"):
+        grid = edges is None  # under "knn" the grid's edge list is not built at all
+        graphs = [_pixel_graph(im, diagonals, use_cache, grid) if method == "pixel" else _patch_graph(im, patch_size, grid) for im in imgs]
+        if grid:
+            return graphs
+        # one kNN launch over the chunk's collated nodes (same-sized images: the sizes are host values), then split per image
+        n = graphs[0][0].size(0)
+        _check_knn_nodes(n, knn_k)
+        feat = knn_features(torch.cat([g[0] for g in graphs]), torch.cat([g[1] for g in graphs]), method, resize_value, knn_pos_weight)
+        ei = F.knn_graph(feat, knn_k, graph_ptr=torch.arange(len(graphs) + 1, dtype=torch.int64) * n)
+        ei = (ei.view(2, len(graphs), knn_k * n) - (torch.arange(len(graphs), device=ei.device) * n).view(1, -1, 1))
+        return [(x, pos, ei[:, b].contiguous()) for b, (x, pos, _) in enumerate(graphs)]
     labels = slic(imgs, n_segments=n_segments, compactness=compactness, start_label=0)
-    nodes, edges = superpixel_capacities(n_segments)
+    nodes, cap_edges = superpixel_capacities(n_segments)
     return _superpixel_graphs_from_device_batch(imgs, labels, nodes if node_capacity is None else int(node_capacity),
-                                                edges if edge_capacity is None else int(edge_capacity))
+                                                cap_edges if edge_capacity is None else int(edge_capacity),
+                                                knn=None if edges is None else (knn_k, knn_pos_weight))
+
+
+EDGES = (None, "knn")
+
+
+def check_edges(edges, knn_k) -> None:
+    """The ``edges`` / ``knn_k`` keywords of ``graphs_from_images`` and ``GraphImageFolder``."""
+    if edges not in EDGES:
+        raise ValueError(f"Unknown edges: {edges!r} (None: the method's own edges; 'knn': k nearest neighbours)")
+    if edges == "knn" and (isinstance(knn_k, bool) or not isinstance(knn_k, int) or not 1 <= knn_k <= native.KNN_MAX_K):
+        raise ValueError(f"knn_k must be an integer in [1, {native.KNN_MAX_K}], got {knn_k!r}")
+
+
+def _check_knn_nodes(n: int, k: int) -> None:
+    if n <= k:
+        raise ValueError(f"a graph of {n} nodes has fewer than knn_k = {k} other nodes to choose neighbours from; lower knn_k")
+
+
+def knn_features(x: torch.Tensor, pos: torch.Tensor, method: str, resize_value: int, pos_weight: float = 1.0) -> torch.Tensor:
+    """The joint (colour, position) space in which ``edges="knn"`` looks for neighbours: ``[..., 5]`` float32 = the node colours
+    scaled to [0, 1] (pixel and patch ``x`` is 0 .. 255 and is divided by 255; superpixel ``x`` already is a mean of ``img / 255``)
+    next to ``pos / resize_value * pos_weight``.  ``pos_weight`` is the one knob: 0 gives pure colour neighbours, a large value
+    pure spatial ones.  Element-wise, so a batch ``[B, n, .]`` gives each image the bits it gets alone."""
+    if method not in METHODS:
+        raise ValueError(f"Unknown method: {method}")
+    colour = x if method == "superpixel" else x / 255.0
+    return torch.cat([colour, pos / float(resize_value) * float(pos_weight)], dim=-1)
+
+
+def _knn_edges_of_graph(x, pos, method, resize_value, k, pos_weight):
+    _check_knn_nodes(x.size(0), k)
+    return F.knn_graph(knn_features(x, pos, method, resize_value, pos_weight), k)
+
+
+def knn_edges(x: torch.Tensor, pos: torch.Tensor, k: int = 8, method: str = "superpixel", resize_value: int = 128,
+              pos_weight: float = 1.0) -> torch.Tensor:
+    """``edge_index`` int64 [2, k n] of ONE image graph's nodes: every node receives from its ``k`` nearest nodes in
+    ``knn_features`` (``functional.knn_graph``: receiver-major, ties by the smaller node id, no self-loops)."""
+    check_edges("knn", k)
+    return _knn_edges_of_graph(x, pos, method, resize_value, k, pos_weight)

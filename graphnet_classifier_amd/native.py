@@ -193,6 +193,11 @@ _SIGNATURES = {
     "gnc_class_loss_launches": (c_int32, [c_int64, c_int32]),
     "gnc_class_loss_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_double, c_double, c_int32, c_double,
                                      c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gnc_knn_graph_f32": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p, c_int64, c_void_p,
+                                    c_void_p, c_void_p]),
+    "gnc_knn_graph_padded_f32": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "gnc_knn_graph_constants": (None, [c_void_p, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -1508,6 +1513,87 @@ def wide_linear_backward(grad_a0: torch.Tensor, az: torch.Tensor, x: torch.Tenso
                            float(act_param), dw.data_ptr(), db.data_ptr(), ws.data_ptr() if ws is not None else None, n_ws,
                            _stream(x)), 2.0 * rows * K * H), "gnc_wide_linear_backward_f32")
     return dw, db
+
+
+# --------------------------------------------------------------------------- K24: k-nearest-neighbour edges
+KNN_MAX_K = 16
+KNN_MAX_DIM = 16
+KNN_FEW_CANDIDATES = 1  # GNC_KNN_FEW_CANDIDATES: a graph had fewer candidates than k (its unfillable slots hold -1)
+KNN_NAN_DISTANCE = 2    # GNC_KNN_NAN_DISTANCE
+
+
+def knn_graph_constants() -> tuple[int, int]:
+    """``(query rows of a workgroup, unroll of the candidate loop)`` of the kNN kernel: the sizes at which it changes path (it
+    stages nothing in LDS)."""
+    q, t = c_int32(0), c_int32(0)
+    load_library().gnc_knn_graph_constants(ctypes.byref(q), ctypes.byref(t))
+    return int(q.value), int(t.value)
+
+
+def _knn_feat(feat: torch.Tensor, k, who: str) -> torch.Tensor:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"{who}: k must be an integer in [1, {KNN_MAX_K}], got {k!r}")
+    if feat.dtype != torch.float32:
+        raise NotImplementedError(f"{who}: features must be float32, got {feat.dtype}")
+    if not 1 <= feat.size(-1) <= KNN_MAX_DIM:
+        raise NotImplementedError(f"{who}: {feat.size(-1)} feature columns; the bit-exact kernel serves 1 .. {KNN_MAX_DIM}")
+    return feat
+
+
+def knn_graph(feat: torch.Tensor, graph_ptr: torch.Tensor, k: int, loop: bool = False, return_dist: bool = False):
+    """``gnc_knn_graph_f32``: the ``k`` nearest rows of ``feat`` [N, D] (float32, unit column stride, any row stride - never copied
+    then) inside each graph of ``graph_ptr`` (DEVICE int64 [G + 1], never read on the host).  Returns ``(edge_index, dist, status)``:
+    ``edge_index`` int64 [2, k N] (slot ``v k + j``: sender = the j-th nearest of ``v``, receiver = ``v``; global ids), ``dist``
+    float32 [k N] or None, ``status`` int32 [1] on the device (``KNN_FEW_CANDIDATES`` / ``KNN_NAN_DISTANCE`` bits).  One launch, no
+    host synchronisation."""
+    lib = load_library()
+    if feat.dim() != 2:
+        raise ValueError(f"knn_graph: feat must be [N, D], got {tuple(feat.shape)}")
+    feat = _rowmajor(_knn_feat(feat, k, "knn_graph"))
+    _require_cuda(feat, graph_ptr)
+    dev, N, D = feat.device, feat.size(0), feat.size(1)
+    gp = _pool_graph_ptr(graph_ptr, dev)
+    G = gp.numel() - 1
+    edge_index = torch.empty(2, k * N, dtype=torch.int64, device=dev)
+    dist = torch.empty(k * N, dtype=torch.float32, device=dev) if return_dist else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("knn_graph", feat,
+                       lambda: lib.gnc_knn_graph_f32(feat.data_ptr(), _ld(feat), D, gp.data_ptr(), G, N, k, int(bool(loop)),
+                                                     edge_index.data_ptr(), k * N, dist.data_ptr() if return_dist else None,
+                                                     status.data_ptr(), _stream(feat)),
+                       3.0 * D * N * N / max(G, 1)), "gnc_knn_graph_f32")
+    return edge_index, dist, status
+
+
+def knn_graph_padded(feat: torch.Tensor, counts: torch.Tensor, k: int, loop: bool = False, return_dist: bool = False):
+    """``gnc_knn_graph_padded_f32`` over the layout of ``rag_build_batched``: ``feat`` [B, node_capacity, D] (float32, contiguous
+    rows), the node count of image ``b`` read on the device from ``counts[b, 0]`` (int32 [B] or [B, S]).  Returns ``(edge_index,
+    dist, status)``: ``edge_index`` int64 [B, 2, k node_capacity] with ids local to each image and -1 behind ``k n_b``, ``dist``
+    float32 [B, k node_capacity] (+inf there) or None, ``status`` as ``knn_graph``'s.  One launch, no host synchronisation."""
+    lib = load_library()
+    if feat.dim() != 3:
+        raise ValueError(f"knn_graph_padded: feat must be [B, node_capacity, D], got {tuple(feat.shape)}")
+    feat = _knn_feat(feat, k, "knn_graph_padded").contiguous()
+    _require_cuda(feat, counts)
+    dev = feat.device
+    B, cap, D = feat.shape
+    if counts.dtype != torch.int32 or counts.device != dev or counts.dim() not in (1, 2) or counts.size(0) != B:
+        raise ValueError(f"knn_graph_padded: counts must be int32 [{B}] or [{B}, S] on the device of feat")
+    counts = counts.contiguous()
+    stride = counts.size(1) if counts.dim() == 2 else 1
+    if cap < 1 or stride < 1:
+        raise ValueError("knn_graph_padded: empty capacity")
+    edge_index = torch.empty(B, 2, k * cap, dtype=torch.int64, device=dev)
+    dist = torch.empty(B, k * cap, dtype=torch.float32, device=dev) if return_dist else None
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(_launch("knn_graph_padded", feat,
+                       lambda: lib.gnc_knn_graph_padded_f32(feat.data_ptr(), D, D, counts.data_ptr(), stride, B, cap, k, int(bool(loop)),
+                                                            edge_index.data_ptr(), dist.data_ptr() if return_dist else None,
+                                                            status.data_ptr(), _stream(feat)),
+                       3.0 * D * B * cap * cap), "gnc_knn_graph_padded_f32")
+    return edge_index, dist, status
 
 
 def u8_hwc_to_f32_chw(img: torch.Tensor) -> torch.Tensor:

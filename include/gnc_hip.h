@@ -718,6 +718,38 @@ int gnc_topk_pool_filter_edges_padded(const int32_t* src_sorted, const int32_t* 
                                       int32_t* dst_out, int32_t* kept_edges, int32_t* edge_new_id, int32_t* rowptr_out,
                                       int32_t* workspace, int64_t workspace_ints, void* stream);
 
+/* ---- K24: k-nearest-neighbour edges inside every graph (csrc/knn_graph.hip) ------------
+ * Node v scans every candidate u of its OWN graph (u == v only when loop != 0).  d(v, u) = sum_c (f_v[c] - f_u[c])^2 in fp32,
+ * c ascending, from +0.0, subtract / multiply / add each rounded once (no fused multiply-add).  Candidates are ordered by the
+ * 64-bit key (bits of d) << 32 | local index of u: smaller distance first, equal distances by the smaller node; a NaN distance
+ * takes the distance field 0xffffffff and sets GNC_KNN_NAN_DISTANCE.  Edge slot v k + j holds the j-th smallest key of v: the
+ * sender u in edge_index[0], the receiver v in edge_index[1], and in `dist` (may be NULL) the key's distance field as fp32.  A
+ * graph with fewer candidates than k sets GNC_KNN_FEW_CANDIDATES; its unfillable slots hold -1 / -1 / +inf.  A pure function of
+ * the features' bits: the same for a graph alone, inside any batch and twice.
+ *
+ *   gnc_knn_graph_f32         graph g owns rows [graph_ptr[g], graph_ptr[g+1]) (DEVICE int64 [num_graphs + 1], ascending, clamped
+ *                             into [0, num_nodes]); ids are global; edge_index int64 [2, ld_edges], ld_edges >= k num_nodes; dist
+ *                             fp32 [k num_nodes].  Rows of no graph are not written.
+ *   gnc_knn_graph_padded_f32  the layout of gnc_rag_build_batched: feat [B, node_capacity, ld_feat], n_b = counts[b counts_stride]
+ *                             read on the device (clamped into [0, node_capacity]); edge_index int64 [B, 2, k node_capacity] with
+ *                             ids local to the image, dist fp32 [B, k node_capacity]; slots behind k n_b hold -1 / -1 / +inf, rows
+ *                             behind n_b are never read.
+ *
+ * `status` (DEVICE int32 [1]) is zeroed by the call (a memset node ahead of the one kernel) and OR-ed into with an integer atomic,
+ * the only atomic.  Stream-ordered, no host synchronisation, capturable; one launch sized from host values alone
+ * (num_nodes / 64 + num_graphs, or B ceil(node_capacity / 64) workgroups).  Supported: 1 <= k <= 16, 1 <= dim <= 16,
+ * ld_feat >= dim; GNC_ERR_UNSUPPORTED otherwise, decided before the first HIP call.  gnc_knn_graph_constants reports the query
+ * rows of a workgroup and the unroll of its candidate loop (the sizes at which the kernel changes path).  Added without an
+ * ABI bump: a library without these symbols fails the symbol lookup of the binding. */
+enum { GNC_KNN_FEW_CANDIDATES = 1, GNC_KNN_NAN_DISTANCE = 2 };
+int gnc_knn_graph_f32(const float* feat, int64_t ld_feat, int32_t dim, const int64_t* graph_ptr, int64_t num_graphs,
+                      int64_t num_nodes, int32_t k, int32_t loop, int64_t* edge_index, int64_t ld_edges, float* dist,
+                      int32_t* status, void* stream);
+int gnc_knn_graph_padded_f32(const float* feat, int64_t ld_feat, int32_t dim, const int32_t* counts, int64_t counts_stride,
+                             int32_t B, int32_t node_capacity, int32_t k, int32_t loop, int64_t* edge_index, float* dist,
+                             int32_t* status, void* stream);
+void gnc_knn_graph_constants(int32_t* query_block, int32_t* candidate_unroll);
+
 /* ---- K18: mean / max neighbourhood aggregation (csrc/segment_reduce.hip) --------------
  * The node model's aggregation with another reducer than K1's sum, over the same destination-sorted CSR and with K1's argument
  * conventions: out[v, :] reduces src[row(k), :] over the sorted positions k in [rowptr[v], rowptr[v+1]), row(k) = perm[k] or k
