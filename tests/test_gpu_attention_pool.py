@@ -224,6 +224,36 @@ def test_backward(Fn, batch, C, kind):
     assert none is None and torch.equal(ds_only, ds)
 
 
+@pytest.mark.parametrize("C", (1, 64))
+def test_backward_and_weights_beyond_two_passes_of_the_capped_grid(Fn, C):
+    """attn_backward_kernel runs at most 8 workgroups per CU, 256 / lanes rows each per trip (C = 1: one lane per row, 256 rows;
+    C = 64: 16 lanes, 16 rows); attn_weights_kernel 8 x 256 rows per CU.  Two full passes and 1027 rows more, 300 graphs of
+    random sizes and 40 slack rows, against the same float64 reference and bounds as ``test_backward`` / ``test_return_weights``.
+    At C = 1 the row count is also two passes and 1027 rows of the weights kernel."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lanes = {1: 1, 64: 16}[C]
+    rows = 2 * 8 * cus * (256 // lanes) + 1027
+    assert rows > 2 * 8 * cus * (256 // lanes) and (C != 1 or rows > 2 * 8 * cus * 256)
+    gen = torch.Generator().manual_seed(40 + C)
+    inside = rows - SLACK
+    cuts = torch.randperm(inside - 1, generator=gen)[:299].sort().values + 1
+    gp = torch.cat([torch.zeros(1, dtype=torch.int64), cuts, torch.tensor([inside])])
+    y, s, dout = torch.randn(rows, C, generator=gen), 4 * torch.randn(rows, generator=gen), torch.randn(300, C, generator=gen)
+    ref = _reference(y, s, dout, gp)
+    out, dy, ds = _grads(Fn, y, s, gp, dout)
+    assert _plus_zero(dy[inside:]) and _plus_zero(ds[inside:])
+    err_dy, bound_dy, err_ds, bound_ds = _backward_errors_and_bounds(ref, dy, ds, inside)
+    print(f"C = {C}, {rows} rows: worst dy err / bound = {float((err_dy / bound_dy).max()):.4f}, "
+          f"ds err / bound = {float((err_ds / bound_ds).max()):.4f}")
+    assert bool((err_dy <= bound_dy).all()) and bool((err_ds <= bound_ds).all())
+    _, alpha = Fn.graph_attention_pool(y.to(DEV), s.to(DEV), gp.to(DEV), return_weights=True)
+    alpha = alpha.cpu()
+    assert _plus_zero(alpha[inside:])
+    n, D = ref["n"][ref["graph_of"][:inside]], ref["D"][ref["graph_of"][:inside]]
+    err = (alpha[:inside].double() - ref["alpha"][:inside]).abs()
+    assert bool((err <= (n + 2 * D + 8) * U * ref["alpha"][:inside] + 2.0 ** -126).all())
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_return_weights(Fn, batch, kind):
     C = 3

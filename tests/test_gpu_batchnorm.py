@@ -124,6 +124,26 @@ def test_forward_backward_and_running_statistics(native, width):
         assert all(torch.equal(a, b) for a, b in zip(again, (dz, dgamma, dbeta)))
 
 
+@pytest.mark.parametrize("width", [130, 256])
+def test_apply_and_backward_beyond_two_passes_of_their_capped_grid(native, width):
+    """gnc_bn_apply_f32 and gnc_bn_backward_dz_f32 run at most 8 workgroups per CU; a workgroup of 256 / lanes row slots takes
+    the rows r, r + s, r + 2 s, r + 3 s (s = the grid's slots) per trip.  The largest row count of ``_rows`` (the reducing
+    kernels' cap) stays inside ONE such trip.  Here: two full trips and 83 rows on a third (a ragged last workgroup), at 64
+    lanes per row with vector (256) and scalar (130) rows, against the same float64 references and bound."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows_per_trip = 4 * (256 // 64)  # of one workgroup
+    rows = 2 * 8 * cus * rows_per_trip + 5 * rows_per_trip + 3
+    assert rows > 2 * 8 * cus * rows_per_trip and max(_rows(width)) <= 8 * cus * rows_per_trip
+    w = B.well_conditioned.__wrapped__(rows, width)  # (not kept in the case cache: 67 MB a tensor)
+    z, res, g = w["z"].to(DEV), w["residual"].to(DEV), w["grad_out"].to(DEV)
+    out, mean, invstd = native.bn_forward(z, w["gamma"].to(DEV), w["beta"].to(DEV), res, eps=B.EPS)
+    dz, dgamma, dbeta = native.bn_backward(g, z, mean, invstd, w["gamma"].to(DEV))
+    for got, name in ((out, "out"), (dz, "dz"), (dgamma, "dgamma"), (dbeta, "dbeta")):
+        err = max_abs(got.cpu(), w[name])
+        print(f"rows {rows} width {width} {name}: {err:.2e} (bound {B.bound(w[name]):.2e})")
+        assert err <= B.bound(w[name]), name
+
+
 def test_one_row_is_refused_like_pytorch_and_batches_are_counted(native):
     from graphnet_classifier_amd.MLP import MLP
     m = MLP(12, 20, hidden_dim=32, norm_type="BatchNorm1d").train()

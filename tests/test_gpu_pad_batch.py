@@ -172,6 +172,23 @@ def test_an_edge_that_leaves_its_graph_sets_the_sticky_flag(name):
     assert int(buf.flag.item()) == 0
 
 
+def test_a_feed_of_more_than_two_passes_of_the_capped_grid():
+    """The launch is capped at 4 workgroups per CU (1024 x CUs threads, one 16-byte chunk each per trip): 64 graphs large enough
+    that x, pos AND the edge rows each reach into a later trip of the grid-stride loop, with an odd edge capacity and slack."""
+    from graphnet_classifier_amd import synthetic
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    side = int((5 * cus) ** 0.5) + 2
+    b = synthetic.superpixel_like_graphs(64, 101, shapes=((side, side), (side, side + 1)))
+    M, C = b.num_nodes + 37, b.num_edges + 1027
+    chunks_x, chunks_pos, chunks_row = -(-M * 3 // 4), -(-M * 2 // 4), -(-C // 2)
+    total = chunks_x + chunks_pos + 2 * chunks_row + 2 * 64 + 1
+    assert total > 2 * 1024 * cus, "the capped grid must make a third trip"
+    assert chunks_x + chunks_pos < 1024 * cus < chunks_x + chunks_pos + chunks_row  # the first pass ends inside edge row 0
+    buf = _Buffers(64, M, C)
+    _feed_and_check(buf, b, list(range(64)))
+    assert int(buf.flag.item()) == 0
+
+
 def test_sixty_five_graphs_raise_on_the_host_and_nothing_is_launched():
     from graphnet_classifier_amd import native
     b = _batch(65, 91)

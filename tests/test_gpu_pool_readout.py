@@ -206,6 +206,41 @@ def test_backward(N, Fn, batch, C):
     assert bool(((dhyb - total).abs() <= bound).all())
 
 
+@pytest.mark.parametrize("C", (3, 64))
+def test_backward_beyond_two_passes_of_the_capped_grid(N, Fn, C):
+    """pool_backward_kernel runs at most 8 workgroups of 256 threads per CU, one item (4 columns of a row at C % 4 == 0, else one)
+    per thread and trip: two full passes and 1027 items more, over 300 graphs of random sizes and 40 slack rows.  sum: bit for
+    bit; mean: one division, 2^-23 relative; max: exact, at the reference's (tie-free) argmax."""
+    from tests import grid_pass_cases as G
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    per_row = C // 4 if C % 4 == 0 else C
+    items = 2 * 8 * cus * 256 + 1027
+    rows = -(-items // per_row)
+    assert rows * per_row > 2 * 8 * cus * 256
+    gen = torch.Generator().manual_seed(5 + C)
+    inside = rows - SLACK
+    cuts = torch.randperm(inside - 1, generator=gen)[:299].sort().values + 1
+    gp = torch.cat([torch.zeros(1, dtype=torch.int64), cuts, torch.tensor([inside])])
+    sizes = (gp[1:] - gp[:-1])
+    graph_of = torch.repeat_interleave(torch.arange(300), sizes)
+    y = torch.randn(rows, C, generator=gen)
+    grad = {name: torch.randn(300, C, generator=gen) for name in ("mean", "max", "sum")}
+    _, ref_arg = G.max_first_row_wins(y[:inside], graph_of, 300)
+
+    def run(mode):
+        yd = y.to(DEV).requires_grad_(True)
+        Fn.graph_pool(yd, gp.to(DEV), mode).backward(grad[mode].to(DEV))
+        dy = yd.grad.cpu()
+        assert dy.shape == (rows, C) and not dy[inside:].any() and not torch.signbit(dy[inside:]).any()
+        return dy[:inside]
+
+    assert torch.equal(run("sum"), grad["sum"][graph_of])
+    hit = ref_arg[graph_of] == torch.arange(inside)[:, None]
+    assert torch.equal(run("max"), torch.where(hit, grad["max"][graph_of], torch.zeros(())))
+    want = grad["mean"].double()[graph_of] / sizes.double()[graph_of][:, None]
+    assert bool(((run("mean").double() - want).abs() <= 2.0 ** -23 * want.abs()).all())
+
+
 def test_graphs_that_do_not_start_at_row_zero_and_rows_in_front_get_zero_gradient(N, Fn):
     """``graph_ptr[0] > 0``: the rows in front of the first graph belong to no graph, like the slack rows behind the last."""
     y = torch.randn(50, 8, generator=torch.Generator().manual_seed(3))

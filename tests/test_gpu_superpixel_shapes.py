@@ -82,6 +82,26 @@ def test_batch_equals_per_image_at_partial_tiles(I2G, shape, connectivity):
     assert int(counts[S.BATCH_ORACLE_IMAGE]) == info["n_labels"]
 
 
+@pytest.mark.parametrize("per_pixel_centres", [False, True], ids=["n100", "one_centre_per_pixel"])
+def test_batch_beyond_two_passes_of_the_capped_grid_equals_per_image(I2G, per_pixel_centres):
+    """The per-pixel launches (Lab conversion, plain labels) and the per-centre seeding run at most 8 workgroups of 256 threads
+    per CU.  Five images that each fit in ONE pass, as a batch of more than two passes: the batch must give each image's own
+    labels.  With one centre per pixel (unit steps) the seeding of the batch's centres takes its later trips too."""
+    cap = 8 * 256 * torch.cuda.get_device_properties(0).multi_processor_count
+    side = int((2 * cap / 5) ** 0.5) + 2
+    assert side * side <= cap and 5 * side * side > 2 * cap
+    rng = np.random.default_rng(side)
+    batch = rng.integers(0, 256, size=(5, side, side, 3), dtype=np.uint8)
+    kw = dict(n_segments=side * side if per_pixel_centres else 100, enforce_connectivity=False, max_iter=2)
+    alone = [I2G.slic(batch[i], **kw, return_counts=True) for i in range(5)]
+    centres = int(alone[0][1][0])  # without the connectivity pass: K, the number of centres
+    assert not per_pixel_centres or (centres <= cap and 5 * centres > 2 * cap)
+    labels, counts = I2G.slic(batch, **kw, return_counts=True)
+    for i in range(5):
+        assert torch.equal(labels[i], alone[i][0]) and int(counts[i]) == int(alone[i][1][0]) == centres
+    assert int(labels.min()) >= 0 and int(labels.max()) < centres
+
+
 def test_repeated_calls_give_the_same_labels(I2G):
     """the box atomics of slic_assign and a workspace that an earlier call of another shape has used"""
     first = {}

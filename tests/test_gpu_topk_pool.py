@@ -188,6 +188,47 @@ def test_rows_forward_and_backward(C, padded):
     assert worst <= 1.0
 
 
+@pytest.mark.parametrize("C", (1, 64))
+def test_row_launches_beyond_two_passes_of_the_capped_grid(C):
+    """The three capped launches - rows_forward over the N' kept rows and rows_backward over all rows (8 workgroups per CU,
+    256 / lanes rows each per trip) and, at C = 1, the CSR-offset kernel of the edge filter (8 x 256 rows per CU) - at two full
+    passes and 1027 rows more for the SMALLEST of them (N' at ratio 0.5): graphs of up to 4,097 rows, checked as everywhere here."""
+    from graphnet_classifier_amd import native
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lanes = {1: 1, 64: 16}[C]
+    first_pass = 8 * cus * (256 // lanes)
+    rows = 2 * (2 * first_pass + 1027)
+    rng = np.random.default_rng(17 + C)
+    sizes = []
+    while sum(sizes) < rows - 9:
+        sizes.append(min(int(rng.integers(2000, 4098)), rows - 9 - sum(sizes)))
+    gp = _batch_ptr(sizes, front=5)
+    assert int(gp[-1]) == rows - 4
+    scores = (2.0 * rng.standard_normal(rows)).astype(np.float32)
+    new_id, kept, _, counts, n_out = _select(scores, gp, 0.5)
+    assert n_out > 2 * first_pass and rows + 1 > 2 * first_pass and (C != 1 or rows + 1 > 2 * 8 * cus * 256)
+    if C == 1:  # the edge filter's rowptr launch over rows + 1 entries
+        src, dst, rowptr = K.sorted_edges(rng, rows, rows, hub=True)
+        assert _filter(src, dst, rowptr, new_id, kept, counts, K.ref_select(scores, gp, 0.5)[0]) > 0
+    kept = kept[:n_out]
+    x =torch.from_numpy(rng.standard_normal((rows, C)).astype(np.float32)).to(DEV)
+    grad = torch.from_numpy(rng.standard_normal((n_out, C)).astype(np.float32)).to(DEV)
+    s = _dev(scores)
+    ref_out, ref_dx, ref_ds = K.ref_rows(x.cpu(), scores, kept.cpu().numpy(), grad.cpu())
+    out = native.topk_pool_rows_forward(x, kept, s, out=torch.full((n_out, C), float("nan"), device=DEV))
+    dx, ds = native.topk_pool_rows_backward(grad, new_id, x, s, dx=torch.full((rows, C), float("nan"), device=DEV),
+                                            ds=torch.full((rows,), float("nan"), device=DEV))
+    dropped = new_id < 0
+    assert bool(dropped.any()) and not bool(dx[dropped].ne(0).any()) and not bool(ds[dropped].ne(0).any())
+    worst = max(_bar(out, ref_out), _bar(dx, ref_dx), _bar(ds, ref_ds))
+    print(f"C = {C}, {rows} rows, {n_out} kept: worst error {worst:.3f} bars")
+    assert worst <= 1.0
+    plain = native.topk_pool_rows_forward(x, kept, None)
+    assert torch.equal(plain, x[kept.long()])  # no gate: the bits of x
+    dx_plain, _ = native.topk_pool_rows_backward(grad, new_id, None, None)
+    assert torch.equal(dx_plain[~dropped], grad[new_id[~dropped].long()]) and not bool(dx_plain[dropped].ne(0).any())
+
+
 def test_functional_topk_pool_on_a_grid_and_its_gradients():
     """``Fn.topk_pool`` end to end on the 128 x 128 grid's edges (16,384 nodes, 32,512 edges, ONE graph of the largest size): the
     pooled topology is the reference's and serves the aggregation kernels; autograd reaches x, the scores and the edge rows."""
