@@ -15,6 +15,9 @@ graph builds of a chunk of images run as batched launches (``image_to_graph.grap
 ``ImageTensorFolder(dataset_path, resize_value)`` is the image side of the reference's MLP baseline (``main.py:13-18``:
 ``ImageFolder`` + ``Resize`` + ``ToTensor``): ``(float32 [3, R, R], label)`` per image, and ``.loader(batch_size=8)`` yields the
 mini-batches of ``DataLoader(ds, batch_size=8, shuffle=True)`` as ``(float32 [B, 3, R, R] on the device, labels [B])``.
+
+Both folders take ``augment=augment.Augmentation(...)`` (K25): their loaders then crop, flip and colour-jitter every image anew in
+every epoch, on the device and with Pillow's pixels, from parameters keyed by ``(seed, epoch, sample index)``.
 """
 from __future__ import annotations
 
@@ -74,6 +77,13 @@ def load_rgb(path: str) -> np.ndarray:
         return np.array(img.convert("RGB"))
 
 
+def _check_augment(augment):
+    from .augment import Augmentation
+    if augment is not None and not isinstance(augment, Augmentation):
+        raise TypeError(f"augment must be an augment.Augmentation or None, got {type(augment).__name__}")
+    return augment
+
+
 def default_workers() -> int:
     """``OMP_NUM_THREADS`` capped at 16 (never the machine's CPU count: a job is given a share of it)."""
     try:
@@ -88,7 +98,7 @@ class GraphImageFolder(Dataset):
     out as ``torchvision.datasets.ImageFolder`` expects (``root/<class>/.../<image>``)."""
 
     def __init__(self, dataset_path='dataset', resize_value=128, diagonals=False, method='pixel', n_segments=100,
-                 patch_size=8, use_cache=True, edges=None, knn_k=8, knn_pos_weight=1.0):
+                 patch_size=8, use_cache=True, edges=None, knn_k=8, knn_pos_weight=1.0, augment=None):
         if method not in I2G.METHODS:
             raise ValueError(f"Unknown method: {method}")
         I2G.check_edges(edges, knn_k)
@@ -105,30 +115,39 @@ class GraphImageFolder(Dataset):
         self.edges = edges  # None: the method's own edges; "knn": k nearest neighbours in (colour, position) (K24)
         self.knn_k = knn_k
         self.knn_pos_weight = knn_pos_weight
+        self.augment = _check_augment(augment)  # an augment.Augmentation for the loaders (K25); None: the plain images
 
     def __len__(self):
         return len(self.samples)
 
-    def _graphs(self, images):
+    def _graphs(self, images, augmentation=None):
         return I2G.graphs_from_images(images, self.method, resize_value=self.resize_value, diagonals=self.diagonals,
                                       use_cache=self.use_cache, n_segments=self.n_segments,
                                       patch_size=self.patch_size, edges=self.edges, knn_k=self.knn_k,
-                                      knn_pos_weight=self.knn_pos_weight)
+                                      knn_pos_weight=self.knn_pos_weight, augmentation=augmentation)
+
+    _build = _graphs  # what a loader calls per chunk
 
     def __getitem__(self, idx):
+        """The plain, un-augmented graph of image ``idx`` whatever ``augment`` is: augmentation belongs to an epoch, and only the
+        loaders know which one is running."""
         path, label = self.samples[idx]
         return self._graphs([load_rgb(path)])[0], torch.tensor(label, dtype=torch.long)
 
     def loader(self, shuffle: bool = True, chunk: int = 64, workers: int | None = None, batch_size: int = 1,
-               drop_last: bool = False):
+               drop_last: bool = False, augment: bool = True):
         """Iterable for ``train(model, ds.loader(), epochs, ...)``; every iteration is one epoch.
 
         ``batch_size=1``: ``((x, pos, edge_index), label)`` per image, in the order ``DataLoader(self, batch_size=1,
         shuffle=shuffle)`` would give under the same global RNG state.  ``batch_size=B > 1``: ``(GraphBatch, labels [B])``
         per mini-batch (``image_to_graph.collate_graphs``), the batches being those of ``DataLoader(self, batch_size=B,
         shuffle=shuffle, drop_last=drop_last)`` under the same global RNG state; without ``drop_last`` the last batch
-        may be shorter."""
-        return GraphFolderLoader(self, shuffle, chunk, workers, batch_size, drop_last)
+        may be shorter.
+
+        ``augment=True`` applies the dataset's ``Augmentation`` (if it has one): every ``__iter__`` is one epoch with its own
+        crops, flips and jitter, and advances the loader's epoch counter (``set_epoch(e)`` sets it).  ``augment=False`` gives the
+        plain images of the same folder, for ``evaluate`` / ``predict``.  The order of the samples is the same either way."""
+        return GraphFolderLoader(self, shuffle, chunk, workers, batch_size, drop_last, augment)
 
 
 class GraphFolderLoader:
@@ -136,7 +155,7 @@ class GraphFolderLoader:
     current chunk is consumed), then resize and graph builds per chunk in batched launches."""
 
     def __init__(self, dataset: GraphImageFolder, shuffle: bool = True, chunk: int = 64, workers: int | None = None,
-                 batch_size: int = 1, drop_last: bool = False):
+                 batch_size: int = 1, drop_last: bool = False, augment: bool = True):
         if chunk < 1:
             raise ValueError("chunk must be at least 1")
         if batch_size < 1:
@@ -147,6 +166,24 @@ class GraphFolderLoader:
         self.batch_size = int(batch_size)
         self.drop_last = bool(drop_last)
         self.workers = default_workers() if workers is None else max(1, min(int(workers), MAX_WORKERS))
+        self.augment = getattr(dataset, "augment", None) if augment else None
+        self.epoch = 0  # the epoch the next __iter__ runs; part of the key of every augmentation draw
+
+    def set_epoch(self, epoch: int) -> None:
+        """The epoch number of the next ``__iter__`` (each ``__iter__`` then counts on from it)."""
+        self.epoch = int(epoch)
+
+    def _next_epoch(self) -> int:
+        epoch = self.epoch
+        self.epoch = epoch + 1
+        return epoch
+
+    def _build(self, images, idx, epoch):
+        """graphs (or tensors) of one decoded chunk, augmented with the parameters of samples ``idx`` in ``epoch``"""
+        if self.augment is None:
+            return self.dataset._build(images)
+        params = self.augment.sample([im.shape[:2] for im in images], epoch, idx)
+        return self.dataset._build(images, augmentation=params)
 
     def __len__(self):
         n, b = len(self.dataset), self.batch_size
@@ -176,6 +213,7 @@ class GraphFolderLoader:
 
     def __iter__(self):
         samples = self.dataset.samples
+        epoch = self._next_epoch()
         if self.batch_size == 1:
             batches = None
             order = self.order()
@@ -193,7 +231,7 @@ class GraphFolderLoader:
             for c, idx in enumerate(chunks):
                 images = [f.result() for f in pending]
                 pending = decode(chunks[c + 1]) if c + 1 < len(chunks) else []
-                graphs = self.dataset._graphs(images)
+                graphs = self._build(images, idx, epoch)
                 del images
                 if batches is None:
                     for i, g in zip(idx, graphs):
@@ -211,25 +249,32 @@ class ImageTensorFolder(Dataset):
     torchvision: the same classes, samples and order, the same pixel values (Pillow's BILINEAR resize and the division by 255
     run on the device, ``image_to_graph.tensors_from_images``)."""
 
-    def __init__(self, dataset_path='dataset', resize_value=128):
+    def __init__(self, dataset_path='dataset', resize_value=128, augment=None):
         self.dataset_path = dataset_path
         self.classes, self.class_to_idx = find_classes(dataset_path)
         self.samples = make_dataset(dataset_path, self.class_to_idx)
         self.targets = [t for _, t in self.samples]
         self.resize_value = resize_value
+        self.augment = _check_augment(augment)  # an augment.Augmentation for the loader (K25); None: the plain images
 
     def __len__(self):
         return len(self.samples)
 
+    def _build(self, images, augmentation=None):
+        return I2G.tensors_from_images(images, self.resize_value, augmentation=augmentation)
+
     def __getitem__(self, idx):
+        """The plain, un-augmented tensor of image ``idx`` whatever ``augment`` is (see ``GraphImageFolder.__getitem__``)."""
         path, label = self.samples[idx]
         return I2G.tensors_from_images([load_rgb(path)], self.resize_value)[0], label
 
-    def loader(self, batch_size: int = 8, shuffle: bool = True, drop_last: bool = False, chunk: int = 64, workers: int | None = None):
+    def loader(self, batch_size: int = 8, shuffle: bool = True, drop_last: bool = False, chunk: int = 64, workers: int | None = None,
+               augment: bool = True):
         """Iterable for ``train(mlp, ds.loader(), epochs)``; every iteration is one epoch of ``(images float32 [B, 3, R, R] on the
         device, labels int64 [B])``, the batches being those of ``DataLoader(self, batch_size=batch_size, shuffle=shuffle,
-        drop_last=drop_last)`` under the same global RNG state; without ``drop_last`` the last batch may be shorter."""
-        return TensorFolderLoader(self, shuffle, chunk, workers, batch_size, drop_last)
+        drop_last=drop_last)`` under the same global RNG state; without ``drop_last`` the last batch may be shorter.  ``augment`` as in
+        ``GraphImageFolder.loader``: True applies the dataset's ``Augmentation``, anew in every epoch; False gives the plain images."""
+        return TensorFolderLoader(self, shuffle, chunk, workers, batch_size, drop_last, augment)
 
 
 class TensorFolderLoader(GraphFolderLoader):
@@ -238,6 +283,7 @@ class TensorFolderLoader(GraphFolderLoader):
 
     def __iter__(self):
         samples = self.dataset.samples
+        epoch = self._next_epoch()
         batches = self.index_batches()
         per = max(1, self.chunk // self.batch_size)
         groups = [batches[i:i + per] for i in range(0, len(batches), per)]
@@ -249,7 +295,7 @@ class TensorFolderLoader(GraphFolderLoader):
             for c, group in enumerate(groups):
                 images = [f.result() for f in pending]
                 pending = decode(groups[c + 1]) if c + 1 < len(groups) else []
-                tensors = I2G.tensors_from_images(images, self.dataset.resize_value)
+                tensors = self._build(images, [i for b in group for i in b], epoch)
                 del images
                 at = 0
                 for b in group:

@@ -10,7 +10,9 @@ int64, already on the GPU, in the reference's node and edge order.
 
 ``resize`` is Pillow's ``Image.resize`` on the device (csrc/resize.hip) for a batch of decoded images of any sizes, and
 ``graphs_from_images`` builds the graphs of such a batch from it: the same tensors as the single-image builders, with
-the resize and SLIC run as batched launches.
+the resize and SLIC run as batched launches.  ``crop_resize`` and ``color_jitter`` (csrc/augment.hip, K25) are Pillow's
+``crop().resize()`` / ``FLIP_LEFT_RIGHT`` and ``ImageEnhance`` chains on the device, byte for byte; with the parameters an
+``augment.Augmentation`` samples they take the place of the resize (``augmentation=`` of the batch builders).
 """
 from __future__ import annotations
 
@@ -305,10 +307,10 @@ def _resample_code(resample) -> int:
     raise ValueError(f"resize: unknown resample {resample!r}")
 
 
-def _as_u8_tensor(img) -> torch.Tensor:
+def _as_u8_tensor(img, who: str = "resize") -> torch.Tensor:
     t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
     if t.dtype != torch.uint8:
-        raise TypeError(f"resize: expected uint8 images, got {t.dtype}")
+        raise TypeError(f"{who}: expected uint8 images, got {t.dtype}")
     return t
 
 
@@ -317,6 +319,44 @@ def _upload(t: torch.Tensor, dev: torch.device) -> torch.Tensor:
     if t.is_cuda:
         return t.to(dev)
     return t.contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def _gather_images(images, dev: torch.device, who: str):
+    """The images of ``resize`` / ``crop_resize`` on the device: ``(src, rows, single)``.  ``rows`` is None for a dense
+    ``[B, H, W, 3]`` ``src``; for a list of images of different sizes ``src`` is their bytes back to back and ``rows`` the host
+    list of ``[byte offset, h, w]`` per image (the kernels' size table)."""
+    if isinstance(images, (list, tuple)):
+        if not images:
+            raise ValueError(f"{who}: empty list of images")
+        imgs = [_as_u8_tensor(im, who) for im in images]
+        for im in imgs:
+            if im.dim() != 3 or im.shape[-1] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError(f"{who}: expected RGB images [H, W, 3], got {tuple(im.shape)}")
+        if all(im.shape == imgs[0].shape for im in imgs):
+            src = torch.stack([_upload(im, dev) for im in imgs]) if imgs[0].is_cuda else _upload(torch.stack(imgs), dev)
+            return src, None, False
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+        offs = np.cumsum([0] + [h * w * 3 for h, w in sizes])
+        if all(im.is_cuda for im in imgs):
+            src = torch.cat([im.to(dev).reshape(-1) for im in imgs])
+        else:
+            src = _upload(torch.cat([im.cpu().reshape(-1) for im in imgs]), dev)
+        return src, [[int(o), h, w] for o, (h, w) in zip(offs[:-1], sizes)], False
+    t = _as_u8_tensor(images, who)
+    if t.dim() not in (3, 4) or t.shape[-1] != 3:
+        raise ValueError(f"{who}: expected an RGB image [H, W, 3] or batch [B, H, W, 3], got {tuple(t.shape)}")
+    single = t.dim() == 3
+    src = _upload(t.unsqueeze(0) if single else t, dev).contiguous()
+    if src.shape[0] == 0 or src.shape[1] == 0 or src.shape[2] == 0:
+        raise ValueError(f"{who}: empty image or batch")
+    return src, None, single
+
+
+def _batch_extent(src: torch.Tensor, rows):
+    """``(B, in_h, in_w)`` of a gathered batch: the largest image sides of a mixed-size one"""
+    if rows is None:
+        return int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
+    return len(rows), max(r[1] for r in rows), max(r[2] for r in rows)
 
 
 def resize(images, size, resample="bicubic", box=None, reducing_gap=None) -> torch.Tensor:
@@ -340,38 +380,9 @@ def resize(images, size, resample="bicubic", box=None, reducing_gap=None) -> tor
         raise ValueError(f"resize: output size must be positive, got {tuple(size)}")
     dev = _device()
     lib = native.load_library()
-    single = False
-    table = None
-    if isinstance(images, (list, tuple)):
-        if not images:
-            raise ValueError("resize: empty list of images")
-        imgs = [_as_u8_tensor(im) for im in images]
-        for im in imgs:
-            if im.dim() != 3 or im.shape[-1] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
-                raise ValueError(f"resize: expected RGB images [H, W, 3], got {tuple(im.shape)}")
-        if all(im.shape == imgs[0].shape for im in imgs):
-            src = torch.stack([_upload(im, dev) for im in imgs]) if imgs[0].is_cuda else _upload(torch.stack(imgs), dev)
-        else:
-            sizes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
-            offs = np.cumsum([0] + [h * w * 3 for h, w in sizes])
-            tab = torch.tensor([[int(o), h, w] for o, (h, w) in zip(offs[:-1], sizes)], dtype=torch.int64)
-            if all(im.is_cuda for im in imgs):
-                src = torch.cat([im.to(dev).reshape(-1) for im in imgs])
-            else:
-                src = _upload(torch.cat([im.cpu().reshape(-1) for im in imgs]), dev)
-            table = _upload(tab, dev)
-            in_h, in_w = max(h for h, _ in sizes), max(w for _, w in sizes)
-            B = len(imgs)
-    else:
-        t = _as_u8_tensor(images)
-        if t.dim() not in (3, 4) or t.shape[-1] != 3:
-            raise ValueError(f"resize: expected an RGB image [H, W, 3] or batch [B, H, W, 3], got {tuple(t.shape)}")
-        single = t.dim() == 3
-        src = _upload(t.unsqueeze(0) if single else t, dev).contiguous()
-    if table is None:
-        B, in_h, in_w = int(src.shape[0]), int(src.shape[1]), int(src.shape[2])
-    if B == 0 or in_h == 0 or in_w == 0:
-        raise ValueError("resize: empty image or batch")
+    src, rows, single = _gather_images(images, dev, "resize")
+    table = None if rows is None else _upload(torch.tensor(rows, dtype=torch.int64), dev)
+    B, in_h, in_w = _batch_extent(src, rows)
     out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         nbytes = lib.gnc_resize_workspace_bytes(B, in_h, in_w, out_h, out_w, code)
@@ -383,6 +394,141 @@ def resize(images, size, resample="bicubic", box=None, reducing_gap=None) -> tor
                                             in_w, out_h, out_w, code, out.data_ptr(), ws.data_ptr(), nbytes,
                                             torch.cuda.current_stream(dev).cuda_stream), "gnc_resize_rgb_u8")
     return out[0] if single else out
+
+
+def crop_resize(images, boxes, size, resample="bicubic", flip=None) -> torch.Tensor:
+    """``Image.fromarray(img_b).crop(box_b).resize(size, resample)`` and, where ``flip[b]`` is set,
+    ``.transpose(Image.Transpose.FLIP_LEFT_RIGHT)``, on the GPU, byte for byte (csrc/augment.hip, K25).
+
+    ``images`` and ``size`` as in ``resize``.  ``boxes``: a host integer array ``[B, 4]`` of ``(left, top, right, bottom)`` per image
+    (``[4]`` for a single image), ``flip``: a host bool array ``[B]`` or None.  An empty box, a box that leaves its image or a length
+    that does not match the batch raises ``ValueError``.  This is *crop, then resize*: filter windows are clamped at the box, where
+    ``Image.resize(box=...)`` reads the pixels around it.  Boxes and flags travel with the size table in one pinned upload; the
+    launches are those of ``resize`` (the flip is part of the last store), stream-ordered without a host synchronisation.  For a
+    replay under ``torch.cuda.graph`` pass ``boxes`` (int64 ``[B, 4]``) and ``flip`` as DEVICE tensors beside a dense device batch:
+    they are then not checked on the host, and a row the kernel finds outside its image leaves its output as it was."""
+    code = _resample_code(resample)
+    out_w, out_h = (int(v) for v in size)
+    if out_w < 1 or out_h < 1:
+        raise ValueError(f"crop_resize: output size must be positive, got {tuple(size)}")
+    dev = _device()
+    lib = native.load_library()
+    src, rows, single = _gather_images(images, dev, "crop_resize")
+    B, in_h, in_w = _batch_extent(src, rows)
+    if isinstance(boxes, torch.Tensor) and boxes.is_cuda:
+        if boxes.dtype != torch.int64 or tuple(boxes.shape) != (B, 4):
+            raise ValueError(f"crop_resize: device boxes must be int64 [{B}, 4], got {boxes.dtype} {tuple(boxes.shape)}")
+        if flip is None:
+            flip = torch.zeros(B, dtype=torch.int64, device=dev)
+        if not (isinstance(flip, torch.Tensor) and flip.is_cuda and tuple(flip.shape) == (B,)):
+            raise ValueError(f"crop_resize: with device boxes, flip must be a device tensor [{B}]")
+        table = None if rows is None else _upload(torch.tensor(rows, dtype=torch.int64), dev)
+        box_table = torch.cat([boxes.to(dev), flip.to(dev, torch.int64).view(B, 1)], dim=1).contiguous()
+    else:
+        bx = np.asarray(boxes)
+        if bx.dtype.kind not in "iu":
+            raise ValueError(f"crop_resize: boxes must be integers, got {bx.dtype}")
+        bx = bx.astype(np.int64).reshape(1, -1) if single and bx.ndim == 1 else bx.astype(np.int64)
+        if bx.shape != (B, 4):
+            raise ValueError(f"crop_resize: {B} images need boxes [{B}, 4], got {tuple(bx.shape)}")
+        fl = np.zeros(B, np.int64) if flip is None else np.asarray(flip).astype(bool).astype(np.int64).reshape(-1)
+        if fl.shape != (B,):
+            raise ValueError(f"crop_resize: {B} images need {B} flip flags, got {tuple(fl.shape)}")
+        hw = np.array([[r[1], r[2]] for r in rows], np.int64) if rows is not None else np.array([[in_h, in_w]] * B, np.int64)
+        bad = ~((bx[:, 0] >= 0) & (bx[:, 1] >= 0) & (bx[:, 0] < bx[:, 2]) & (bx[:, 1] < bx[:, 3]) & (bx[:, 2] <= hw[:, 1])
+                & (bx[:, 3] <= hw[:, 0]))
+        if bad.any():
+            b = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"crop_resize: box {tuple(int(v) for v in bx[b])} of image {b} is empty or leaves its "
+                             f"{int(hw[b, 0])} x {int(hw[b, 1])} image")
+        # one upload: the size table (mixed sizes only), then the (left, top, right, bottom, flip) rows
+        host = np.concatenate([np.asarray(rows if rows is not None else [], np.int64).reshape(-1),
+                               np.concatenate([bx, fl[:, None]], axis=1).reshape(-1)])
+        both = _upload(torch.from_numpy(host), dev)
+        table = None if rows is None else both[:3 * B]
+        box_table = both[both.numel() - 5 * B:]
+    out = torch.empty(B, out_h, out_w, 3, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = lib.gnc_crop_resize_workspace_bytes(B, in_h, in_w, out_h, out_w, code)
+        if nbytes == 0:
+            raise NotImplementedError(f"crop_resize: {B} images of up to {in_h} x {in_w} -> {out_h} x {out_w} is outside "
+                                      "the supported set (batch and sides up to 65535)")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        native._check(lib.gnc_crop_resize_rgb_u8(src.data_ptr(), table.data_ptr() if table is not None else None,
+                                                 box_table.data_ptr(), B, in_h, in_w, out_h, out_w, code, out.data_ptr(),
+                                                 ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
+                      "gnc_crop_resize_rgb_u8")
+    return out[0] if single else out
+
+
+JITTER_OPS = ("brightness", "contrast", "saturation")  # the operation codes 0, 1, 2 of ``order``
+
+
+def _jitter_factors(value, B: int, name: str) -> np.ndarray:
+    f = np.asarray(value, dtype=np.float32)
+    if f.ndim == 0:
+        f = np.full(B, f, np.float32)
+    if f.shape != (B,):
+        raise ValueError(f"color_jitter: {name} must be a scalar or [{B}], got {tuple(f.shape)}")
+    if not np.all(np.isfinite(f)) or (f < 0).any():
+        raise ValueError(f"color_jitter: {name} factors must be finite and >= 0")
+    return f
+
+
+def color_jitter(batch_u8, brightness=None, contrast=None, saturation=None, order=None) -> torch.Tensor:
+    """Pillow's ``ImageEnhance.Brightness`` / ``.Contrast`` / ``.Color`` on the GPU, byte for byte, for a dense uint8 batch
+    ``[B, H, W, 3]`` (or one ``[H, W, 3]`` image): every image gets its own float32 factors (``[B]`` or a scalar; None leaves the
+    operation out) in its own order.  ``order``: host ``[B, 3]`` (or ``[3]``), per image a permutation of ``(0, 1, 2)`` =
+    ``(brightness, contrast, saturation)``, first to last; the default is that order.  Returns a new tensor: one copy and ONE
+    launch in place on it (csrc/augment.hip), no host synchronisation.  Contrast's grey level is the rounded mean L of the image
+    as the operations in front of it left it, as in a chain of ``enhance`` calls.  With no operation the copy is returned as it is."""
+    t = _as_u8_tensor(batch_u8, "color_jitter")
+    if t.dim() not in (3, 4) or t.shape[-1] != 3:
+        raise ValueError(f"color_jitter: expected an RGB image [H, W, 3] or batch [B, H, W, 3], got {tuple(t.shape)}")
+    single = t.dim() == 3
+    dev = _device()
+    if t.is_cuda:
+        out = (t.unsqueeze(0) if single else t).to(dev).contiguous().clone()
+    else:
+        out = _upload(t.unsqueeze(0) if single else t, dev)
+    B, H, W = int(out.shape[0]), int(out.shape[1]), int(out.shape[2])
+    if B == 0 or H == 0 or W == 0:
+        raise ValueError("color_jitter: empty image or batch")
+    given = (brightness, contrast, saturation)
+    factors = np.ones((B, 3), np.float32)
+    for op, (value, name) in enumerate(zip(given, JITTER_OPS)):
+        if value is not None:
+            factors[:, op] = _jitter_factors(value, B, name)
+    if order is None:
+        perm = np.tile(np.arange(3, dtype=np.int32), (B, 1))
+    else:
+        perm = np.asarray(order)
+        if perm.dtype.kind not in "iu":
+            raise ValueError(f"color_jitter: order must be integers, got {perm.dtype}")
+        perm = np.tile(perm.astype(np.int32), (B, 1)) if perm.ndim == 1 else perm.astype(np.int32)
+        if perm.shape != (B, 3) or (np.sort(perm, axis=1) != np.arange(3)).any():
+            raise ValueError(f"color_jitter: order must hold a permutation of (0, 1, 2) per image, [{B}, 3]")
+    perm = np.where(np.array([v is not None for v in given])[perm], perm, -1).astype(np.int32)  # left-out operations
+    if (perm < 0).all():
+        return out[0] if single else out
+    lib = native.load_library()
+    host = np.concatenate([perm.reshape(-1), factors.reshape(-1).view(np.int32)])  # one upload: order, then the factors' bits
+    both = _upload(torch.from_numpy(host), dev)
+    with torch.cuda.device(dev):
+        native._check(lib.gnc_color_jitter_rgb_u8(out.data_ptr(), B, H, W, both.data_ptr(), both[3 * B:].data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream), "gnc_color_jitter_rgb_u8")
+    return out[0] if single else out
+
+
+def _augmented(images_u8, resize_value: int, resample: str, augmentation) -> torch.Tensor:
+    """The chunk's ``resize`` with sampled augmentation parameters (``augment.AugmentParams``): ``crop_resize`` and, if any factor
+    was drawn, ``color_jitter``."""
+    if len(augmentation.boxes) != len(images_u8):
+        raise ValueError(f"augmentation holds parameters of {len(augmentation.boxes)} images, the batch has {len(images_u8)}")
+    imgs = crop_resize(list(images_u8), augmentation.boxes, (resize_value, resize_value), resample, augmentation.flips)
+    if augmentation.brightness is None and augmentation.contrast is None and augmentation.saturation is None:
+        return imgs
+    return color_jitter(imgs, augmentation.brightness, augmentation.contrast, augmentation.saturation, augmentation.order)
 
 
 def collate_graphs(graphs):
@@ -407,13 +553,18 @@ def collate_graphs(graphs):
     return GraphBatch(x, pos, edge_index + shift, graph_ptr, edge_ptr)
 
 
-def tensors_from_images(images_u8, resize_value: int = 128) -> torch.Tensor:
+def tensors_from_images(images_u8, resize_value: int = 128, *, augmentation=None) -> torch.Tensor:
     """torchvision's ``Compose([Resize((R, R)), ToTensor()])`` (main.py:13-16 of the reference) for a batch of decoded uint8 RGB
     images ``[H_i, W_i, 3]`` of any sizes: float32 ``[B, 3, R, R]`` on the device, values in [0, 1].  ``Resize`` on a PIL image is
     Pillow's BILINEAR ``Image.resize`` (``resize`` here, byte for byte), ``ToTensor`` is ``permute(2, 0, 1).float().div(255)``
-    (``native.u8_hwc_to_f32_chw``, bit for bit): two batched enqueues, no host synchronisation."""
+    (``native.u8_hwc_to_f32_chw``, bit for bit): two batched enqueues, no host synchronisation.
+
+    ``augmentation`` (K25): the parameters ``augment.Augmentation.sample`` drew for these images; the resize then is ``crop_resize``
+    (BILINEAR) followed by ``color_jitter``, as Pillow would produce them, and ``ToTensor`` is unchanged."""
     if len(images_u8) == 0:
         raise ValueError("tensors_from_images: empty list of images")
+    if augmentation is not None:
+        return native.u8_hwc_to_f32_chw(_augmented(images_u8, resize_value, "bilinear", augmentation))
     return native.u8_hwc_to_f32_chw(resize(list(images_u8), (resize_value, resize_value), "bilinear"))
 
 
@@ -423,7 +574,7 @@ METHODS = ("pixel", "patch", "superpixel")
 def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128, diagonals: bool = False,
                        use_cache: bool = True, n_segments: int = 100, patch_size: int = 8, compactness: float = 10, *,
                        node_capacity: int | None = None, edge_capacity: int | None = None, edges=None, knn_k: int = 8,
-                       knn_pos_weight: float = 1.0):
+                       knn_pos_weight: float = 1.0, augmentation=None):
     """Graphs of a batch of decoded uint8 RGB images ``[H_i, W_i, 3]`` (any sizes): a list of ``(x, pos, edge_index)``
     equal to ``image_to_graph_pixel_optimized`` / ``image_to_graph_patch`` / ``image_to_graph_superpixel`` of each
     image, with arguments named as ``utils/dataloader.py``'s ``OptimizedDatasetLoader``.  The resize of the whole
@@ -437,13 +588,20 @@ def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128
     nearest neighbours of each node in ``knn_features`` (colour next to ``knn_pos_weight`` x position): ``knn_k n`` edges,
     receiver-major.  One more launch per chunk and no further host synchronisation: superpixel chunks run the padded kNN entry
     off the batch's device counts in front of the one host read, pixel and patch chunks one call over the collated nodes.  A
-    graph with ``n <= knn_k`` nodes raises ``ValueError``.  ``edges=None`` is the method's own edge list."""
+    graph with ``n <= knn_k`` nodes raises ``ValueError``.  ``edges=None`` is the method's own edge list.
+
+    ``augmentation`` (K25): the parameters ``augment.Augmentation.sample`` drew for these images.  The one ``resize`` call then is
+    ``crop_resize`` (random resized crop and horizontal flip) followed by ``color_jitter``: the graphs are those of the images
+    Pillow produces with the same parameters, and everything behind the resize is unchanged.  None: no new launch."""
     if method not in METHODS:
         raise ValueError(f"Unknown method: {method}")
     check_edges(edges, knn_k)
     if len(images_u8) == 0:
         return []
-    imgs = resize(list(images_u8), (resize_value, resize_value))
+    if augmentation is not None:
+        imgs = _augmented(images_u8, resize_value, "bicubic", augmentation)
+    else:
+        imgs = resize(list(images_u8), (resize_value, resize_value))
     if method in ("pixel", "patch"):
         grid = edges is None  # under "knn" the grid's edge list is not built at all
         graphs = [_pixel_graph(im, diagonals, use_cache, grid) if method == "pixel" else _patch_graph(im, patch_size, grid) for im in imgs]

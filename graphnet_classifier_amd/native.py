@@ -116,6 +116,11 @@ _SIGNATURES = {
     "gnc_resize_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "gnc_resize_rgb_u8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    "gnc_crop_resize_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "gnc_crop_resize_rgb_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
+    "gnc_color_jitter_resident_pixels": (c_int64, []),
+    "gnc_color_jitter_rgb_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "gnc_u8_hwc_to_f32_chw": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "gnc_wide_linear_supported": (c_int32, [c_void_p, c_void_p]),
     "gnc_wide_linear_workspace_floats": (c_int64, [c_int64, c_int64, c_int32, c_int32]),

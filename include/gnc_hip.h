@@ -878,6 +878,32 @@ size_t gnc_resize_workspace_bytes(int32_t B, int32_t in_h, int32_t in_w, int32_t
 int gnc_resize_rgb_u8(const uint8_t* src, const int64_t* table, int32_t B, int32_t in_h, int32_t in_w, int32_t out_h,
                       int32_t out_w, int32_t filter, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K25: train-time image augmentation, pinned to Pillow (csrc/augment.hip) ---------------------
+ * gnc_crop_resize_rgb_u8   `Image.fromarray(img_b).crop(box_b).resize((out_w, out_h), filter)`, then FLIP_LEFT_RIGHT where the
+ *                      image's flag is set, byte for byte.  The arguments of gnc_resize_rgb_u8 and `boxes`: DEVICE int64 [B, 5] =
+ *                      (left, top, right, bottom, flip) with 0 <= left < right <= w_b and 0 <= top < bottom <= h_b; a row outside
+ *                      that is skipped (its output left as it was), never read out of bounds.  Crop, then resize: filter windows
+ *                      clamp at the box (this is not `Image.resize(box=...)`, which reads outside the box).  The same three
+ *                      launches as the resize; the flip is part of the last store.  Workspace of
+ *                      gnc_crop_resize_workspace_bytes(B, in_h, in_w, out_h, out_w, filter) bytes, in_h / in_w being the largest
+ *                      IMAGE sides (0 = not supported).  Stream-ordered, no host synchronisation, safe under stream capture.
+ * gnc_color_jitter_rgb_u8  Pillow's ImageEnhance.Brightness / .Contrast / .Color chains, byte for byte, IN PLACE on a dense uint8
+ *                      [B, H, W, 3] batch.  `order` DEVICE int32 [B, 3]: the operations of image b in the order they run
+ *                      (0 brightness, 1 contrast, 2 color; any other value, or a repeated one, is no operation); `factor` DEVICE
+ *                      float32 [B, 3] indexed by operation.  A factor of 1 is the identity and costs nothing.  One launch, one
+ *                      workgroup per image, no workspace, no atomics; images of up to gnc_color_jitter_resident_pixels() pixels
+ *                      wait in the LDS across the contrast's reduction, larger ones are read twice.  Sides <= 65535.
+ *                      Stream-ordered, a kernel node under stream capture.
+ * Added without an ABI bump: a library without these symbols fails the symbol lookup of the binding.
+ */
+size_t gnc_crop_resize_workspace_bytes(int32_t B, int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, int32_t filter);
+int gnc_crop_resize_rgb_u8(const uint8_t* src, const int64_t* table, const int64_t* boxes, int32_t B, int32_t in_h, int32_t in_w,
+                           int32_t out_h, int32_t out_w, int32_t filter, uint8_t* out, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int64_t gnc_color_jitter_resident_pixels(void);
+int gnc_color_jitter_rgb_u8(uint8_t* img, int32_t B, int32_t H, int32_t W, const int32_t* order, const float* factor,
+                            void* stream);
+
 /* gnc_u8_hwc_to_f32_chw  torchvision's ToTensor for B uint8 images [B, H, W, C] on the device: out [B, C, H, W] float32 with
  *                      out[b, c, y, x] = float(img[b, y, x, c]) / 255 (a correctly rounded division: bit for bit what
  *                      `t.permute(2, 0, 1).float().div(255)` gives).  B, C <= 65535.  Stream-ordered, a kernel node under stream
