@@ -155,23 +155,19 @@ class EdgeProcessor(nn.Module):
         caller then runs K1).  ``need_edges=False`` (with ``aggregate``, autograd off): ``e'`` may come back as None
         when the launch can form ``agg`` without storing it."""
         mlp = self.edge_processor
-        norm = mlp.model[-1] if mlp.norm_type is not None else None
-        lin = mlp._linears()
+        weights, biases, ln = mlp._kernel_params()
         # (with autograd on, only for ReLU: its backward is the fused K8 launch over the split form; another activation
         # trains through the concat form, whose backward runs layer by layer - functional._layerwise_mlp_backward_hip)
         trainable_split = mlp.activation_name == "ReLU" or not torch.is_grad_enabled()
-        if (WSPLIT and trainable_split and not isinstance(norm, nn.BatchNorm1d) and mlp.activation_name in native.ACTIVATIONS
-                and lin[0].in_features == 2 * x.size(1) + edge_attr.size(1) and x.size(1) % 4 == 0):
+        if (WSPLIT and trainable_split and mlp.norm_type != "BatchNorm1d" and mlp.activation_name in native.ACTIVATIONS
+                and weights[0].size(1) == 2 * x.size(1) + edge_attr.size(1) and x.size(1) % 4 == 0):
             # W-split of the first Linear: node-side products once per node, gathered and added per edge
-            ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
             if aggregate and not torch.is_grad_enabled():
-                return Fn.edge_processor_wsplit_aggregated(x, edge_attr, topo, [m.weight for m in lin], [m.bias for m in lin],
-                                                           ln, mlp.activation_name, mlp._act_param(), store_edges=need_edges)
-            if aggregate:  # training: same launch, both outputs differentiable
-                return Fn.edge_processor_wsplit(x, edge_attr, topo, [m.weight for m in lin], [m.bias for m in lin], ln,
-                                                mlp.activation_name, mlp._act_param(), with_agg=True)
-            return Fn.edge_processor_wsplit(x, edge_attr, topo, [m.weight for m in lin],
-                                            [m.bias for m in lin], ln, mlp.activation_name, mlp._act_param())
+                return Fn.edge_processor_wsplit_aggregated(x, edge_attr, topo, weights, biases, ln, mlp.activation_name,
+                                                           mlp._act_param(), store_edges=need_edges)
+            # (with aggregate, training: the same launch, both outputs differentiable)
+            return Fn.edge_processor_wsplit(x, edge_attr, topo, weights, biases, ln, mlp.activation_name, mlp._act_param(),
+                                            with_agg=aggregate)
         out = mlp.forward_segments(
             [(x, topo.src_sorted), (x, topo.dst_sorted), (edge_attr, None)], residual=edge_attr, rows=topo.num_edges)
         return (out, None) if aggregate else out
@@ -276,10 +272,7 @@ class MetaLayer(nn.Module):
             else:
                 edge_attr = self.edge_model.forward_sorted(x, topo, edge_attr)
         if self.node_model is not None:
-            if agg is not None:
-                x = self.node_model.forward_sorted(x, topo, edge_attr, agg)
-            else:
-                x = self.node_model.forward_sorted(x, topo, edge_attr)
+            x = self.node_model.forward_sorted(x, topo, edge_attr, agg)
         return x, edge_attr
 
 

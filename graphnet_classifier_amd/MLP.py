@@ -73,6 +73,13 @@ class MLP(nn.Module):
     def _linears(self):
         return [m for m in self.model if isinstance(m, nn.Linear)]
 
+    def _kernel_params(self):
+        """``(weights, biases, ln)`` as the kernels take them: one entry per Linear, ``ln = (gamma, beta, eps)`` behind a
+        LayerNorm and None otherwise."""
+        lin, norm = self._linears(), self.model[-1]
+        ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
+        return [m.weight for m in lin], [m.bias for m in lin], ln
+
     def _act_param(self) -> float:
         a = self.activation
         return float(getattr(a, "negative_slope", getattr(a, "alpha", 0.0)))
@@ -83,12 +90,12 @@ class MLP(nn.Module):
         return bool(norm.affine and norm.track_running_stats and norm.momentum == 0.1 and norm.running_mean is not None
                     and norm.weight.is_cuda and norm.weight.dtype == torch.float32 and norm.num_features <= native.BN_MAX_WIDTH)
 
-    def _folded_batchnorm(self, lin, norm):
+    def _folded_batchnorm(self, weights, biases, norm):
         """(weights, biases) of the Linear chain with the eval-mode BatchNorm folded into the last Linear (K14 fold kernel).
         Formed from the live parameters and running statistics on every call: nothing is cached, so in-place edits,
         ``load_state_dict`` and a graph replay always see the current values."""
-        w, b = native.bn_fold(lin[-1].weight, lin[-1].bias, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps)
-        return [m.weight.detach() for m in lin[:-1]] + [w], [m.bias.detach() if m.bias is not None else None for m in lin[:-1]] + [b]
+        w, b = native.bn_fold(weights[-1], biases[-1], norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps)
+        return [p.detach() for p in weights[:-1]] + [w], [p.detach() if p is not None else None for p in biases[:-1]] + [b]
 
     def forward_segments(self, segments, residual: Tensor | None = None, rows: int | None = None) -> Tensor:
         """Run the MLP on the virtual concat of ``segments`` = [(table, int32 index | None)]
@@ -96,19 +103,17 @@ class MLP(nn.Module):
         LayerNorm and residual are one kernel launch.  With ``norm_type='BatchNorm1d'``: in training mode the Linear chain is
         that launch and the batch statistics, the normalisation (+ residual) and their backward run on the K14 kernels; in eval
         mode without a wanted gradient the normalisation is folded into the last Linear and everything is the one launch again."""
-        lin = self._linears()
-        require_gpu_param(lin[0].weight, "MLP")
+        weights, biases, ln = self._kernel_params()
+        require_gpu_param(weights[0], "MLP")
         if self.activation_name not in native.ACTIVATIONS:
             raise NotImplementedError(f"activation nn.{self.activation_name} has no HIP kernel "
                                       f"(available: {sorted(native.ACTIVATIONS)})")
-        norm = self.model[-1] if self.norm_type is not None else None
-        if isinstance(norm, nn.BatchNorm1d):
-            return self._forward_batchnorm(lin, norm, segments, residual, rows)
-        ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
-        return Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=ln,
+        if self.norm_type == "BatchNorm1d":
+            return self._forward_batchnorm(weights, biases, self.model[-1], segments, residual, rows)
+        return Fn.fused_mlp(segments, weights, biases, ln=ln,
                             activation=self.activation_name, act_param=self._act_param(), residual=residual, rows=rows)
 
-    def _forward_batchnorm(self, lin, norm, segments, residual, rows):
+    def _forward_batchnorm(self, weights, biases, norm, segments, residual, rows):
         t0, i0 = segments[0]
         n_rows = int(rows) if rows is not None else int(i0.numel() if i0 is not None else t0.size(0))
         wants_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
@@ -120,16 +125,15 @@ class MLP(nn.Module):
                 if n_rows == 1:  # torch.nn.functional.batch_norm's check, before any launch
                     raise ValueError(f"Expected more than 1 value per channel when training, got input size "
                                      f"{torch.Size([1, norm.num_features])}")
-                z = Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=None, residual=None, **kw)
+                z = Fn.fused_mlp(segments, weights, biases, ln=None, residual=None, **kw)
                 y = Fn.batch_norm_rows(z, norm.weight, norm.bias, residual, norm.running_mean, norm.running_var, norm.momentum,
                                        norm.eps, True, inplace=True)  # z is this call's own table
                 norm.num_batches_tracked.add_(1)  # a device op: no host value enters a captured step
                 return y
             if not wants_grad:
-                weights, biases = self._folded_batchnorm(lin, norm)
-                return Fn.fused_mlp(segments, weights, biases, ln=None, residual=residual, **kw)
+                return Fn.fused_mlp(segments, *self._folded_batchnorm(weights, biases, norm), ln=None, residual=residual, **kw)
         # every other case (eval mode with a wanted gradient, no rows, a non-default BatchNorm1d): the PyTorch-ROCm module
-        y = Fn.fused_mlp(segments, [m.weight for m in lin], [m.bias for m in lin], ln=None, residual=None, **kw)
+        y = Fn.fused_mlp(segments, weights, biases, ln=None, residual=None, **kw)
         y = norm(y)
         if residual is not None:
             y = y + residual
@@ -139,19 +143,17 @@ class MLP(nn.Module):
         """This MLP on the edge features of models/GNN.py:299-302 WITHOUT storing them (K6 as the launch's prologue); None
         when that form is not available (training, a BatchNorm the fold does not serve, a shape / batch size no kernel serves
         this way)."""
-        lin = self._linears()
         if self.activation_name != "ReLU":
             return None
         if torch.is_grad_enabled() and (pos.requires_grad or any(p.requires_grad for p in self.parameters())):
             return None  # the backward needs the feature rows (dW_0)
-        norm = self.model[-1] if self.norm_type is not None else None
-        if isinstance(norm, nn.BatchNorm1d):  # eval mode: folded into the last Linear; training mode needs the batch statistics
-            if norm.training or not self._batchnorm_in_library(norm) or not lin[0].weight.is_cuda:
+        weights, biases, ln = self._kernel_params()
+        if self.norm_type == "BatchNorm1d":  # eval mode: folded into the last Linear; training mode needs the batch statistics
+            norm = self.model[-1]
+            if norm.training or not self._batchnorm_in_library(norm) or not weights[0].is_cuda:
                 return None
-            weights, biases = self._folded_batchnorm(lin, norm)
-            return native.mlp_forward_edge_features(pos, src, dst, weights, biases, ln=None)
-        ln = (norm.weight, norm.bias, norm.eps) if isinstance(norm, nn.LayerNorm) else None
-        return native.mlp_forward_edge_features(pos, src, dst, [m.weight for m in lin], [m.bias for m in lin], ln=ln)
+            weights, biases = self._folded_batchnorm(weights, biases, norm)
+        return native.mlp_forward_edge_features(pos, src, dst, weights, biases, ln=ln)
 
     def forward(self, x: Tensor):
         """models/MLP.py:45-47: flatten to (rows, -1), cast to float32, run the Sequential."""

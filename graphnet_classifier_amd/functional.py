@@ -9,12 +9,18 @@ reference's only caller that needs gradients is ``utils/train_model.py:41``
   forward of the widths <= 64 kernels keeps the hidden layers' post-activations for it, the wider ones
   recompute the forward of each tile from the inputs (``GNC_TORCH_BACKWARD=1`` switches to a PyTorch-ROCm
   recompute for A/B runs; nothing here ever runs on the CPU);
+* the three Functions around that kernel pair - ``_FusedMLP``, ``_WideFirstMLP``, ``_EdgeProcessorWSplit`` - share one record of a
+  call (``_MlpCall``: the non-tensor facts and the flat order of the tensor arguments, their saved copies and their gradients),
+  one assembly of the parameter gradients (``_parameter_grads``), one gradient of a gathered table and one PyTorch recompute
+  chain;
 * an MLP over ONE wide table (the image-MLP baseline: 49152 inputs, 8 rows) runs its first Linear on the split-K kernels K16 and
   the rest of its chain as an ordinary fused-MLP call, tied together by ``_WideFirstMLP`` (``GNC_NO_WIDE_LINEAR=1`` keeps the
   row-tiled kernels everywhere, for A/B runs);
 * batch normalisation over table rows (``norm_type='BatchNorm1d'``) runs on the K14 kernels both ways.
 """
 from __future__ import annotations
+
+import collections
 
 import torch
 import torch.nn.functional as F
@@ -184,262 +190,281 @@ def _torch_activation(name: str, param: float):
             "GELU": F.gelu}[name]
 
 
-class _MlpMeta:
-    """Non-tensor arguments of one fused-MLP call."""
-    __slots__ = ("indices", "num_linear", "activation", "act_param", "ln_eps", "has_ln", "has_residual", "rows", "training")
+_MlpArgs = collections.namedtuple("_MlpArgs", "tables weights biases ln residual")
 
-    def __init__(self, indices, num_linear, activation, act_param, ln_eps, has_ln, has_residual, rows):
-        self.indices, self.num_linear, self.activation, self.act_param = indices, num_linear, activation, act_param
-        self.ln_eps, self.has_ln, self.has_residual, self.rows = ln_eps, has_ln, has_residual, rows
+
+class _MlpCall:
+    """One fused-MLP call: its non-tensor facts, and the flat layout of its tensor arguments - tables, weights, biases,
+    (gamma, beta behind a LayerNorm), (residual if any).  That order is the one of the arguments behind the record in
+    ``Function.apply``, of ``needs_input_grad`` and the saved tensors, and of the gradients a backward returns; nothing else
+    knows it.  There are as many tables as ``indices``: one (or None) per segment - for the W-split edge processor the tables
+    (x, e) and the two gathers (src, dst) of x."""
+    __slots__ = ("indices", "num_tables", "num_linear", "activation", "act_param", "ln_eps", "has_ln", "has_residual", "rows",
+                 "with_agg", "training")
+
+    def __init__(self, indices, num_linear, activation, act_param, ln, residual, rows, with_agg=False):
+        self.indices, self.num_tables = tuple(indices), len(indices)
+        self.num_linear, self.activation, self.act_param = num_linear, activation, float(act_param)
+        self.has_ln, self.ln_eps = ln is not None, float(ln[2]) if ln is not None else 0.0
+        self.has_residual, self.rows, self.with_agg = residual is not None, int(rows), bool(with_agg)
         # the caller's grad mode (inside Function.forward it is always off): a backward can only follow when it was on
         self.training = torch.is_grad_enabled()
 
+    def pack(self, tables, weights, biases, ln=None, residual=None) -> tuple:
+        """The flat tuple of the named groups; of ``ln`` its first two entries (gamma, beta) go in."""
+        return (*tables, *weights, *biases, *(ln[:2] if self.has_ln else ()), *((residual,) if self.has_residual else ()))
 
-class _FusedMLP(torch.autograd.Function):
-    """args = tables[S] + weights[L] + biases[L] + (gamma, beta if LN) + (residual if any)."""
+    def unpack(self, flat) -> _MlpArgs:
+        """The named groups of a flat tuple - arguments, ``needs_input_grad`` flags or gradients; ``ln`` is (gamma, beta, eps) as
+        the kernels take it, or None."""
+        s = self.num_tables
+        w = s + self.num_linear
+        b = w + self.num_linear
+        ln = (flat[b], flat[b + 1], self.ln_eps) if self.has_ln else None
+        return _MlpArgs(list(flat[:s]), list(flat[s:w]), list(flat[w:b]), ln, flat[-1] if self.has_residual else None)
 
-    @staticmethod
-    def forward(ctx, meta: _MlpMeta, *args):
-        s, l = len(meta.indices), meta.num_linear
-        tables, weights, biases = args[:s], args[s:s + l], args[s + l:s + 2 * l]
-        rest = list(args[s + 2 * l:])
-        ln = (rest.pop(0), rest.pop(0), meta.ln_eps) if meta.has_ln else None
-        residual = rest.pop(0) if meta.has_residual else None
-        # training forward: the kernel also leaves the hidden layers' post-activations (what autograd would keep) for K8
-        acts = [] if (meta.training and any(ctx.needs_input_grad) and HIP_BACKWARD) else None
-        out = native.mlp_forward(list(zip(tables, meta.indices)), list(weights), list(biases), ln=ln,
-                                 activation=meta.activation, act_param=meta.act_param, residual=residual, rows=meta.rows,
-                                 save_act=acts, save_need_dx=any(ctx.needs_input_grad[1:1 + s]))
-        ctx.meta = meta
-        # the saved post-activations go through save_for_backward like the inputs: autograd then frees them as soon as this
-        # node's backward has run (held as plain attributes they lived until the whole graph died: +30 GB at c5)
-        ctx.n_acts = len(acts) if acts else 0
-        ctx.save_for_backward(*args, *(acts or []))
-        return out
+    def tables(self, flat):
+        """The tables' entries of a flat tuple alone (what a forward asks of ``needs_input_grad``)."""
+        return flat[:self.num_tables]
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        meta, saved = ctx.meta, ctx.saved_tensors
-        args = saved[:len(saved) - ctx.n_acts]
-        acts = list(saved[len(saved) - ctx.n_acts:]) if ctx.n_acts else None
-        s, l = len(meta.indices), meta.num_linear
-        need = ctx.needs_input_grad[1:]
-        if meta.rows == 0:  # no rows: every gradient is a zero of its argument's shape (an edge-less graph, superpixel.py:70-71)
-            return (None,) + tuple(torch.zeros_like(a) if n else None for a, n in zip(args, need))
-        if HIP_BACKWARD:
-            hip = _fused_mlp_backward_hip(meta, args, need, grad_out, acts)
-            if hip is None:  # an activation other than ReLU (or a shape outside K8): layer by layer, still on this library
-                hip = _layerwise_mlp_backward_hip(meta, args, need, grad_out)
-            return (None,) + hip
-        # GNC_TORCH_BACKWARD=1 (A/B and parity runs only): PyTorch-ROCm recompute backward of the same ops on the GPU
-        leaves = [a.detach().requires_grad_(bool(n)) for a, n in zip(args, need)]
-        tables, weights, biases = leaves[:s], leaves[s:s + l], leaves[s + l:s + 2 * l]
-        rest = leaves[s + 2 * l:]
-        act = _torch_activation(meta.activation, meta.act_param)
-        with torch.enable_grad():
-            h = torch.cat([t if i is None else t[i.long()] for t, i in zip(tables, meta.indices)], dim=-1)
-            for k in range(l):
-                h = F.linear(h, weights[k], biases[k])
-                if k + 1 < l:
-                    h = act(h)
-            if meta.has_ln:
-                h = F.layer_norm(h, (h.size(-1),), rest[0], rest[1], meta.ln_eps)
-            if meta.has_residual:
-                h = h + rest[-1]
-            wanted = [x for x, n in zip(leaves, need) if n]
-            grads = iter(torch.autograd.grad(h, wanted, grad_out.contiguous(), allow_unused=True))
-        return (None,) + tuple(next(grads) if n else None for n in need)
+    def split_saved(self, saved):
+        """(the flat arguments, whatever the forward saved behind them) of a node's ``saved_tensors``."""
+        n = self.num_tables + 2 * self.num_linear + 2 * self.has_ln + self.has_residual
+        return saved[:n], list(saved[n:])
+
+    def grads(self, need, tables=None, weights=None, biases=None, gamma=None, beta=None, residual=None) -> tuple:
+        """The gradient tuple a backward returns behind the non-tensor arguments: gradients given by name, table k / weight l /
+        bias l as the k-th / l-th entry of their lists; None for a group left out and wherever ``need`` says no."""
+        flat = self.pack(tables or [None] * self.num_tables, weights or [None] * self.num_linear,
+                         biases or [None] * self.num_linear, (gamma, beta), residual)
+        return tuple([g if n else None for g, n in zip(flat, need)])
 
 
-def _fused_mlp_backward_hip(meta: _MlpMeta, args, need, grad_out, saved_act=None):
-    """Backward of one fused-MLP call on the HIP kernels (K8): data path + one skinny GEMM per Linear.
-    Returns the gradient tuple in argument order, or None when the shape is outside the kernels."""
-    s, l = len(meta.indices), meta.num_linear
-    tables, weights, biases = list(args[:s]), list(args[s:s + l]), list(args[s + l:s + 2 * l])
-    rest = list(args[s + 2 * l:])
-    ln = (rest[0], rest[1], meta.ln_eps) if meta.has_ln else None
-    residual = rest[-1] if meta.has_residual else None
-    segments = list(zip(tables, meta.indices))
-    if (meta.activation != "ReLU" or l < 2 or not grad_out.is_cuda
-            or not native.mlp_backward_supported(segments, weights, biases, ln, meta.activation, residual, meta.rows,
-                                                 saved_act=saved_act)):
-        return None
-    grad_out = grad_out.contiguous()
-    need_tables = any(need[:s])
-    r = native.mlp_backward(segments, weights, biases, ln, grad_out, rows=meta.rows, need_dx=need_tables, saved_act=saved_act,
-                            defer_ln_sums=True)
-    grads = [None] * len(args)
-    # inputs: dx is in concat (= weight column) order
-    off = 0
-    layer0_inputs = []
-    for k, (t, idx) in enumerate(segments):
-        w = t.size(1)
-        rows_k = t if idx is None else native.gather_rows(t, idx)
-        layer0_inputs.append(rows_k)
-        if need[k]:
-            gk = r["dx"][:, off:off + w]
-            if idx is None:
-                grads[k] = gk
-            else:  # rows gathered by index (operator-level API only): sum the row gradients per table row with K1 through
-                # the index's own destination CSR - stable order, no float atomics, bitwise reproducible
-                from .topology import get_destination_csr
-                csr = get_destination_csr(idx, t.size(0), t.device)
-                grads[k] = native.scatter_sum_csr(gk, csr.rowptr, csr.perm, t.size(0))
-        off += w
-    # weights and biases: dW_l = dz_l^T (input of Linear l), db_l = column sums of dz_l - every product of this MLP (and
-    # the row sums of its LayerNorm partials) in one xty_multi call: one launch for a small batch
-    products, slots = [], []
-    for k in range(l):
-        if not (need[s + k] or need[s + l + k]):
-            continue
-        if "dw" in r:  # fused kernel: weight gradients came out of the data kernel (single row-ordered segment)
-            grads[s + k] = r["dw"][k] if need[s + k] else None
-            grads[s + l + k] = r["db"][k] if need[s + l + k] else None
-            continue
-        dz = r["dz"][k]
-        if k == 0:
-            dw = torch.empty(weights[0].size(0), sum(t.size(1) for t in layer0_inputs), dtype=torch.float32, device=dz.device)
-            off = 0
-            for rows_k in layer0_inputs:  # column blocks of dW_0, in concat order
-                products.append((dz, rows_k, dw[:, off:off + rows_k.size(1)]))
-                slots.append((k, off == 0))
-                off += rows_k.size(1)
-            grads[s + k] = dw if need[s + k] else None
+def _torch_recompute_backward(call: _MlpCall, flat, need, grad_out, first_input, residual=lambda a: a.residual):
+    """GNC_TORCH_BACKWARD=1 (A/B and parity runs only): PyTorch-ROCm recompute backward of the same ops on the GPU.
+    ``first_input(tables)`` is the first Linear's input, ``residual(args)`` what is added behind the norm (or None)."""
+    leaves = [a.detach().requires_grad_(bool(n)) for a, n in zip(flat, need)]
+    a = call.unpack(leaves)
+    act = _torch_activation(call.activation, call.act_param)
+    with torch.enable_grad():
+        h = first_input(a.tables)
+        for k, (w, b) in enumerate(zip(a.weights, a.biases)):
+            h = F.linear(h, w, b)
+            if k + 1 < call.num_linear:
+                h = act(h)
+        if a.ln is not None:
+            h = F.layer_norm(h, (h.size(-1),), *a.ln)
+        if residual(a) is not None:
+            h = h + residual(a)
+        wanted = [x for x, n in zip(leaves, need) if n]
+        grads = iter(torch.autograd.grad(h, wanted, grad_out.contiguous(), allow_unused=True))
+    return tuple(next(grads) if n else None for n in need)
+
+
+def _gathered_table_grad(row_grads, table, idx):
+    """Gradient of ``table`` from the gradients of the rows a segment read from it.  Rows gathered by index (operator-level
+    API only): summed per table row with K1 through the index's own destination CSR - stable order, no float atomics,
+    bitwise reproducible."""
+    if idx is None:
+        return row_grads
+    from .topology import get_destination_csr
+    csr = get_destination_csr(idx, table.size(0), table.device)
+    return native.scatter_sum_csr(row_grads, csr.rowptr, csr.perm, table.size(0))
+
+
+def _parameter_grads(r, blocks, need_w, need_b, need_ln, grad_out):
+    """``([dW_l], [db_l], dgamma, dbeta)`` of one MLP backward from ``r``, the result of ``native.mlp_backward``; None where the
+    flags ``need_w[l]`` / ``need_b[l]`` / ``need_ln`` ((gamma, beta), or None without a LayerNorm) do not ask.  dW_l = dz_l^T (input
+    of Linear l), db_l = column sums of dz_l.  ``blocks``: the column blocks of dW_0 in concat order as (left, right) operands,
+    dW_0[:, block] = left^T right; a block whose left operand is dz_0 itself is the data kernel's own first Linear: the first of
+    them gives db_0, and the fused kernel hands them - like every later layer - out itself (``r["dw"]`` / ``r["db"]``).  Every
+    other product of the layers asked for, and the row sums of the LayerNorm partials, are ONE xty_multi call (one launch for
+    a small batch), the blocks of dW_0 written in place."""
+    fused, dz0, num_linear = "dw" in r, r["dz"][0], len(need_w)
+    dw, db = [None] * num_linear, [None] * num_linear
+    products, slots = [], []  # slots[i]: the layer that takes (dW, db) of product i - of dW_0's blocks only db - or None
+    if need_w[0] or need_b[0]:
+        own = [left is dz0 for left, _ in blocks]
+        if fused:
+            db[0] = r["db"][0]
+        if fused and all(own):
+            dw[0] = r["dw"][0]
         else:
-            products.append((dz, r["act"][k - 1], None))
-            slots.append((k, True))
+            dw[0] = torch.empty(blocks[0][0].size(1), sum(right.size(1) for _, right in blocks), dtype=torch.float32,
+                                device=blocks[0][1].device)
+            off = 0
+            for (left, right), mine in zip(blocks, own):
+                out = dw[0][:, off:off + right.size(1)]
+                off += right.size(1)
+                if fused and mine:
+                    out.copy_(r["dw"][0])
+                else:
+                    products.append((left, right, out))
+                    slots.append(0 if mine and 0 not in slots else None)
+    for k in range(1, num_linear):
+        if not (need_w[k] or need_b[k]):
+            continue
+        if fused:
+            dw[k], db[k] = r["dw"][k], r["db"][k]
+        else:
+            products.append((r["dz"][k], r["act"][k - 1], None))
+            slots.append(k)
     ln_part = r.get("ln_part")
     res, sums = native.xty_multi(products, [ln_part] if ln_part is not None else []) if (products or ln_part is not None) else ([], [])
-    for (k, first), (c, cs) in zip(slots, res):
-        if k > 0:
-            grads[s + k] = c if need[s + k] else None
-        if first:
-            grads[s + l + k] = cs if need[s + l + k] else None
-    pos = s + 2 * l
-    if meta.has_ln:
+    for k, (c, cs) in zip(slots, res):
+        if k is not None:
+            dw[k], db[k] = (c if k > 0 else dw[0]), cs
+    dgamma = dbeta = None
+    if need_ln is not None:
         if ln_part is not None:
             od = ln_part.size(1) // 2
             dbeta, dgamma = sums[0][:od], sums[0][od:]
         else:
             dbeta, dgamma = r["ln_sums"] if r["ln_sums"] is not None else native.colsum_pair(grad_out, r["yhat"])
-        grads[pos] = dgamma if need[pos] else None
-        grads[pos + 1] = dbeta if need[pos + 1] else None
-        pos += 2
-    if meta.has_residual and need[pos]:
-        grads[pos] = grad_out
-    return tuple(grads)
+        dgamma, dbeta = dgamma if need_ln[0] else None, dbeta if need_ln[1] else None
+    return [g if n else None for g, n in zip(dw, need_w)], [g if n else None for g, n in zip(db, need_b)], dgamma, dbeta
 
 
-def _layerwise_mlp_backward_hip(meta: _MlpMeta, args, need, grad_out):
+class _FusedMLP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, call: _MlpCall, *flat):
+        a = call.unpack(flat)
+        # training forward: the kernel also leaves the hidden layers' post-activations (what autograd would keep) for K8
+        acts = [] if (call.training and any(ctx.needs_input_grad) and HIP_BACKWARD) else None
+        out = native.mlp_forward(list(zip(a.tables, call.indices)), a.weights, a.biases, ln=a.ln,
+                                 activation=call.activation, act_param=call.act_param, residual=a.residual, rows=call.rows,
+                                 save_act=acts, save_need_dx=any(call.tables(ctx.needs_input_grad[1:])))
+        ctx.call = call
+        # the saved post-activations go through save_for_backward like the inputs: autograd then frees them as soon as this
+        # node's backward has run (held as plain attributes they lived until the whole graph died: +30 GB at c5)
+        ctx.save_for_backward(*flat, *(acts or []))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        call, need = ctx.call, ctx.needs_input_grad[1:]
+        flat, acts = call.split_saved(ctx.saved_tensors)
+        if call.rows == 0:  # no rows: every gradient is a zero of its argument's shape (an edge-less graph, superpixel.py:70-71)
+            return (None,) + tuple(torch.zeros_like(a) if n else None for a, n in zip(flat, need))
+        if HIP_BACKWARD:
+            hip = _fused_mlp_backward_hip(call, flat, need, grad_out, acts or None)
+            if hip is None:  # an activation other than ReLU (or a shape outside K8): layer by layer, still on this library
+                hip = _layerwise_mlp_backward_hip(call, flat, need, grad_out)
+            return (None,) + hip
+        return (None,) + _torch_recompute_backward(call, flat, need, grad_out, lambda tables: torch.cat(
+            [t if i is None else t[i.long()] for t, i in zip(tables, call.indices)], dim=-1))
+
+
+def _fused_mlp_backward_hip(call: _MlpCall, flat, need, grad_out, saved_act=None):
+    """Backward of one fused-MLP call on the HIP kernels (K8): data path + one skinny GEMM per Linear.
+    Returns the gradient tuple in argument order, or None when the shape is outside the kernels."""
+    a, n = call.unpack(flat), call.unpack(need)
+    segments = list(zip(a.tables, call.indices))
+    if (call.activation != "ReLU" or call.num_linear < 2 or not grad_out.is_cuda
+            or not native.mlp_backward_supported(segments, a.weights, a.biases, a.ln, call.activation, a.residual, call.rows,
+                                                 saved_act=saved_act)):
+        return None
+    grad_out = grad_out.contiguous()
+    r = native.mlp_backward(segments, a.weights, a.biases, a.ln, grad_out, rows=call.rows, need_dx=any(n.tables),
+                            saved_act=saved_act, defer_ln_sums=True)
+    # inputs: dx is in concat (= weight column) order, and so are the column blocks of dW_0 = dz_0^T [rows of every segment]
+    off, dtables, blocks = 0, [], []
+    for (t, idx), wanted in zip(segments, n.tables):
+        w = t.size(1)
+        blocks.append((r["dz"][0], t if idx is None else native.gather_rows(t, idx)))
+        dtables.append(_gathered_table_grad(r["dx"][:, off:off + w], t, idx) if wanted else None)
+        off += w
+    dw, db, dgamma, dbeta = _parameter_grads(r, blocks, n.weights, n.biases, n.ln, grad_out)
+    return call.grads(need, dtables, dw, db, dgamma, dbeta, grad_out)
+
+
+def _layerwise_mlp_backward_hip(call: _MlpCall, flat, need, grad_out):
     """Backward of one fused-MLP call for the shapes the K8 kernels do not take - an activation other than ReLU
     (models/MLP.py:21 accepts any nn.<Name>) - layer by layer on the library's own kernels: the pre-activations are
     recomputed with single-Linear K4 launches, act / act' / the LayerNorm backward are row-wise kernels
     (csrc/elementwise.hip), da = dz W is a single-Linear launch on the transposed weight, dW = dz^T a and db come from
     gnc_xty_f32, gathered segments get their gradient through K1.  Nothing here is on the path of a ReLU model."""
-    s, l = len(meta.indices), meta.num_linear
-    tables, weights, biases = list(args[:s]), list(args[s:s + l]), list(args[s + l:s + 2 * l])
-    rest = list(args[s + 2 * l:])
-    act, ap = meta.activation, meta.act_param
+    p, n = call.unpack(flat), call.unpack(need)
+    l, weights, biases = call.num_linear, p.weights, p.biases
+    act, ap = call.activation, call.act_param
     if act not in native.ACTIVATIONS or not grad_out.is_cuda:
         raise NotImplementedError(f"backward of an MLP with activation nn.{act} has no HIP kernel")
-    segments = list(zip(tables, meta.indices))
+    segments = list(zip(p.tables, call.indices))
     grad_out = grad_out.contiguous()
     # forward recompute: z_k (pre-activations) and a_k = act(z_k)
     zs, acts = [], []
-    z = native.mlp_forward(segments, [weights[0]], [biases[0]], activation="Identity", rows=meta.rows)
+    z = native.mlp_forward(segments, [weights[0]], [biases[0]], activation="Identity", rows=call.rows)
     for k in range(l):
         zs.append(z)
         if k + 1 < l:
             a = native.activation(z, act, ap)
             acts.append(a)
             z = native.mlp_forward([(a, None)], [weights[k + 1]], [biases[k + 1]], activation="Identity")
-    grads = [None] * len(args)
-    pos = s + 2 * l
-    if meta.has_ln:
-        dz, yhat = native.layer_norm_backward(zs[-1], rest[0], grad_out, meta.ln_eps)
-        if need[pos] or need[pos + 1]:
+    dtables, dw, db = [], [None] * l, [None] * l
+    dz, dgamma, dbeta = grad_out, None, None
+    if p.ln is not None:
+        dz, yhat = native.layer_norm_backward(zs[-1], p.ln[0], grad_out, call.ln_eps)
+        if n.ln[0] or n.ln[1]:
             dbeta, dgamma = native.colsum_pair(grad_out, yhat)
-            grads[pos] = dgamma if need[pos] else None
-            grads[pos + 1] = dbeta if need[pos + 1] else None
-        pos += 2
-    else:
-        dz = grad_out
-    if meta.has_residual and need[pos]:
-        grads[pos] = grad_out
-    for k in range(l - 1, -1, -1):
-        want_w = need[s + k] or need[s + l + k]
-        if k > 0:
-            if want_w:
-                dw, db = native.xty(dz, acts[k - 1])
-                grads[s + k] = dw if need[s + k] else None
-                grads[s + l + k] = db if need[s + l + k] else None
-            da = native.mlp_forward([(dz, None)], [weights[k].t().contiguous()], [None], activation="Identity")  # dz W_k
-            dz = native.activation_backward(zs[k - 1], da, act, ap)
-            continue
-        # first Linear: its input is the virtual concat of the segments (gathered ones materialised for the products)
-        off, parts, db0 = 0, [], None
-        for q, (t, idx) in enumerate(segments):
-            w = t.size(1)
-            if want_w:
-                c, cs = native.xty(dz, t if idx is None else native.gather_rows(t, idx))
-                parts.append(c)
-                db0 = cs if db0 is None else db0
-            if need[q]:
-                gq = native.mlp_forward([(dz, None)], [weights[0][:, off:off + w].t().contiguous()], [None], activation="Identity")
-                if idx is None:
-                    grads[q] = gq
-                else:
-                    from .topology import get_destination_csr
-                    csr = get_destination_csr(idx, t.size(0), t.device)
-                    grads[q] = native.scatter_sum_csr(gq, csr.rowptr, csr.perm, t.size(0))
-            off += w
-        if want_w:
-            grads[s] = (torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]) if need[s] else None
-            grads[s + l] = db0 if need[s + l] else None
-    return tuple(grads)
+    for k in range(l - 1, 0, -1):
+        if n.weights[k] or n.biases[k]:
+            dw[k], db[k] = native.xty(dz, acts[k - 1])
+        da = native.mlp_forward([(dz, None)], [weights[k].t().contiguous()], [None], activation="Identity")  # dz W_k
+        dz = native.activation_backward(zs[k - 1], da, act, ap)
+    # first Linear: its input is the virtual concat of the segments (gathered ones materialised for the products)
+    off, parts = 0, []
+    for (t, idx), wanted in zip(segments, n.tables):
+        w = t.size(1)
+        if n.weights[0] or n.biases[0]:
+            c, cs = native.xty(dz, t if idx is None else native.gather_rows(t, idx))
+            parts.append(c)
+            db[0] = cs if db[0] is None else db[0]
+        dtables.append(_gathered_table_grad(native.mlp_forward([(dz, None)], [weights[0][:, off:off + w].t().contiguous()], [None],
+                                                               activation="Identity"), t, idx) if wanted else None)
+        off += w
+    if n.weights[0]:
+        dw[0] = torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]
+    return call.grads(need, dtables, dw, db, dgamma, dbeta, grad_out)
 
 
 class _WideFirstMLP(torch.autograd.Function):
     """A fused-MLP call over ONE wide row-ordered table: the first Linear + activation on K16 (csrc/wide_linear.hip), the remaining
     Linears + LayerNorm as an ordinary fused-MLP launch over its output; the backward of that launch supplies the gradient of the
     first Linear's output (its ``need_dx``), from which K16 forms dW0 and db0.  The table itself gets no gradient (it is data: the
-    route is not taken when it wants one).  args = x, weights[L], biases[L], (gamma, beta if LN)."""
+    route is not taken when it wants one)."""
 
     @staticmethod
-    def forward(ctx, meta: _MlpMeta, x, *params):
-        l = meta.num_linear
-        weights, biases = list(params[:l]), list(params[l:2 * l])
-        ln = (params[2 * l], params[2 * l + 1], meta.ln_eps) if meta.has_ln else None
-        training = meta.training and any(ctx.needs_input_grad)
-        relu = meta.activation == "ReLU"
-        a0, z0 = native.wide_linear_forward(x, weights[0], biases[0], meta.activation, meta.act_param, want_z=training and not relu)
+    def forward(ctx, call: _MlpCall, *flat):
+        a = call.unpack(flat)
+        training = call.training and any(ctx.needs_input_grad)
+        relu = call.activation == "ReLU"
+        a0, z0 = native.wide_linear_forward(a.tables[0], a.weights[0], a.biases[0], call.activation, call.act_param,
+                                            want_z=training and not relu)
         acts = [] if training else None
-        out = native.mlp_forward([(a0, None)], weights[1:], biases[1:], ln=ln, activation=meta.activation, act_param=meta.act_param,
-                                 rows=meta.rows, save_act=acts, save_need_dx=True)
-        ctx.meta = meta
-        ctx.n_acts = len(acts) if acts else 0
+        out = native.mlp_forward([(a0, None)], a.weights[1:], a.biases[1:], ln=a.ln, activation=call.activation,
+                                 act_param=call.act_param, rows=call.rows, save_act=acts, save_need_dx=True)
+        ctx.call = call
         if training:
-            ctx.save_for_backward(x, *params, a0, a0 if relu else z0, *(acts or []))
+            ctx.save_for_backward(*flat, a0, a0 if relu else z0, *(acts or []))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        meta, saved = ctx.meta, ctx.saved_tensors
-        l = meta.num_linear
-        acts = list(saved[len(saved) - ctx.n_acts:]) if ctx.n_acts else None
-        x, params, a0, az = saved[0], saved[1:len(saved) - ctx.n_acts - 2], saved[-ctx.n_acts - 2], saved[-ctx.n_acts - 1]
-        need = ctx.needs_input_grad[2:]
-        # the rest of the chain, as the fused-MLP call over a0 that the forward made: argument order a0, W1.., b1.., (gamma, beta)
-        rest = _MlpMeta((None,), l - 1, meta.activation, meta.act_param, meta.ln_eps, meta.has_ln, False, meta.rows)
-        rest_args = (a0,) + tuple(params[1:l]) + tuple(params[l + 1:2 * l]) + tuple(params[2 * l:])
-        rest_need = (True,) + tuple(need[1:l]) + tuple(need[l + 1:2 * l]) + tuple(need[2 * l:])
-        g = _fused_mlp_backward_hip(rest, rest_args, rest_need, grad_out, acts)
+        call, need = ctx.call, ctx.needs_input_grad[1:]
+        flat, (a0, az, *acts) = call.split_saved(ctx.saved_tensors)
+        a, n = call.unpack(flat), call.unpack(need)
+        # the rest of the chain, as the fused-MLP call over a0 that the forward made
+        rest = _MlpCall((None,), call.num_linear - 1, call.activation, call.act_param, a.ln, None, call.rows)
+        rest_flat, rest_need = rest.pack([a0], a.weights[1:], a.biases[1:], a.ln), rest.pack([True], n.weights[1:], n.biases[1:], n.ln)
+        g = _fused_mlp_backward_hip(rest, rest_flat, rest_need, grad_out, acts or None)
         if g is None:  # an activation other than ReLU, or a single Linear behind the first: layer by layer, still on this library
-            g = _layerwise_mlp_backward_hip(rest, rest_args, rest_need, grad_out)
+            g = _layerwise_mlp_backward_hip(rest, rest_flat, rest_need, grad_out)
+        g = rest.unpack(g)
         dw0 = db0 = None
-        if need[0] or need[l]:
-            dw0, db0 = native.wide_linear_backward(g[0], az, x, meta.activation, meta.act_param)
-        return (None, None, dw0 if need[0] else None) + tuple(g[1:l]) + (db0 if need[l] else None,) + tuple(g[l:])
+        if n.weights[0] or n.biases[0]:
+            dw0, db0 = native.wide_linear_backward(g.tables[0], az, a.tables[0], call.activation, call.act_param)
+        dgamma, dbeta = g.ln[:2] if g.ln is not None else (None, None)
+        return (None,) + call.grads(need, None, [dw0] + g.weights, [db0] + g.biases, dgamma, dbeta)
 
 
 def wide_linear_route(segments, weights, biases, ln, activation, residual, rows) -> bool:
@@ -459,16 +484,9 @@ def fused_mlp(segments, weights, biases, ln=None, activation: str = "ReLU", act_
     indices = tuple(i for _, i in segments)
     if rows is None:
         rows = indices[0].numel() if indices[0] is not None else tables[0].size(0)
-    meta = _MlpMeta(indices, len(weights), activation, float(act_param), float(ln[2]) if ln is not None else 0.0,
-                    ln is not None, residual is not None, int(rows))
-    if wide_linear_route(segments, weights, biases, ln, activation, residual, rows):
-        return _WideFirstMLP.apply(meta, tables[0], *weights, *biases, *((ln[0], ln[1]) if ln is not None else ()))
-    args = list(tables) + list(weights) + list(biases)
-    if ln is not None:
-        args += [ln[0], ln[1]]
-    if residual is not None:
-        args.append(residual)
-    return _FusedMLP.apply(meta, *args)
+    call = _MlpCall(indices, len(weights), activation, act_param, ln, residual, rows)
+    fn = _WideFirstMLP if wide_linear_route(segments, weights, biases, ln, activation, residual, rows) else _FusedMLP
+    return fn.apply(call, *call.pack(tables, weights, biases, ln, residual))
 
 
 class _BatchNormRows(torch.autograd.Function):
@@ -515,34 +533,27 @@ class _EdgeProcessorWSplit(torch.autograd.Function):
     """EdgeProcessor (models/GNN.py:57-64) on destination-sorted edges with the first Linear
     split algebraically:  W0 [x_src | x_dst | e]^T = Ws x[src] + Wd x[dst] + We e.
     Two per-NODE projection launches (num_linear == 1, no bias) + one per-EDGE launch whose
-    first two segments are gathered and ADDED.  args = x, e, weights[L], biases[L], gamma, beta."""
+    first two segments are gathered and ADDED.  The record's tables are (x, e), its indices (src, dst)."""
 
     @staticmethod
-    def forward(ctx, meta, topo, x, e, *params):
-        ctx.topo = topo
-        src, dst, num_linear, activation, act_param, ln_eps, has_ln = meta[:7]
-        with_agg = len(meta) > 7 and meta[7]
-        weights, biases = list(params[:num_linear]), list(params[num_linear:2 * num_linear])
-        ln = (params[2 * num_linear], params[2 * num_linear + 1], ln_eps) if has_ln else None
+    def forward(ctx, call: _MlpCall, topo, *flat):
+        a = call.unpack(flat)
+        (x, e), (src, dst), w0 = a.tables, call.indices, a.weights[0]
         dn = x.size(1)
-        w0 = weights[0]
         ps, pd = _node_projections(x, w0, dn)                                 # [N, H] = x Ws^T, x Wd^T
-        training = len(meta) > 8 and meta[8] and any(ctx.needs_input_grad) and HIP_BACKWARD
+        training = call.training and any(ctx.needs_input_grad) and HIP_BACKWARD
         acts = [] if training else None   # the hidden layers' post-activations, kept for K8 where the kernel can
-        out = native.mlp_forward([(ps, src), (pd, dst), (e, None)], [w0[:, 2 * dn:]] + weights[1:], biases, ln=ln,
-                                 activation=activation, act_param=act_param, residual=e, rows=e.size(0),
+        out = native.mlp_forward([(ps, src), (pd, dst), (e, None)], [w0[:, 2 * dn:]] + a.weights[1:], a.biases, ln=a.ln,
+                                 activation=call.activation, act_param=call.act_param, residual=e, rows=call.rows,
                                  modes=[native.SEG_ADD, native.SEG_ADD, native.SEG_MATMUL],
-                                 aggregate=(topo.dst_sorted, topo.rowptr, topo.num_nodes) if with_agg else None,
-                                 save_act=acts, save_need_dx=bool(ctx.needs_input_grad[3]))
+                                 aggregate=(topo.dst_sorted, topo.rowptr, topo.num_nodes) if call.with_agg else None,
+                                 save_act=acts, save_need_dx=bool(call.tables(ctx.needs_input_grad[2:])[1]))
+        ctx.call, ctx.topo = call, topo
+        ctx.set_materialize_grads(False)  # an unused output (the last block's e') arrives as None, not as zeros
         # kept for the backward through save_for_backward (freed when this node's backward has run): the projections - its
         # gathered inputs again, [N, H] each - and the post-activations
-        extra = ([ps, pd] + acts) if training else []
-        ctx.n_extra = len(extra)
-        ctx.meta = meta[:7]
-        ctx.with_agg = with_agg
-        ctx.set_materialize_grads(False)  # an unused output (the last block's e') arrives as None, not as zeros
-        ctx.save_for_backward(x, e, *params, *extra)
-        if not with_agg:
+        ctx.save_for_backward(*flat, *(([ps, pd] + acts) if training else []))
+        if not call.with_agg:
             return out
         out, agg = out
         if agg is None:  # the launch shape cannot carry the epilogue: K1 as a separate launch
@@ -551,139 +562,76 @@ class _EdgeProcessorWSplit(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out, grad_agg=None):
-        src, dst, num_linear, activation, act_param, ln_eps, has_ln = ctx.meta
-        need = ctx.needs_input_grad[2:]
-        if not ctx.with_agg:
+        call, need = ctx.call, ctx.needs_input_grad[2:]
+        if not call.with_agg:
             grad_agg = None
         if grad_out is None and grad_agg is None:
             return (None, None) + tuple(None for _ in need)
-        if ctx.saved_tensors[1].size(0) == 0:  # an edge-less graph (superpixel.py:70-71): zeros of every argument's shape
-            saved0 = ctx.saved_tensors[:len(ctx.saved_tensors) - getattr(ctx, "n_extra", 0)]
-            return (None, None) + tuple(torch.zeros_like(a) if n else None for a, n in zip(saved0, need))
+        flat, extra = call.split_saved(ctx.saved_tensors)
+        if call.rows == 0:  # an edge-less graph (superpixel.py:70-71): zeros of every argument's shape
+            return (None, None) + tuple(torch.zeros_like(a) if n else None for a, n in zip(flat, need))
         # e' feeds the aggregation (its backward is a row gather by destination: grad_agg[dst]) AND whatever consumed e'
         # itself (grad_out): the K8 launch adds the gathered rows itself where its kernel can
         if HIP_BACKWARD:
-            hip = _edge_wsplit_backward_hip(ctx, grad_out, grad_agg)
+            hip = _edge_wsplit_backward_hip(call, ctx.topo, flat, extra, need, grad_out, grad_agg)
             if hip is None:  # (EdgeProcessor.forward_sorted only takes the W-split route for shapes K8 serves)
                 raise NotImplementedError("W-split edge processor: this shape has no HIP backward kernel (use the concat form)")
             return (None, None) + hip
-        # GNC_TORCH_BACKWARD=1 (A/B and parity runs only): PyTorch-ROCm recompute backward of the same ops on the GPU
+        src, dst = call.indices
         if grad_agg is not None and grad_out is not None:
             grad_out = native.gather_rows_add(grad_agg.contiguous(), dst, grad_out.contiguous())
         elif grad_agg is not None:
             grad_out = native.gather_rows(grad_agg.contiguous(), dst)
-        saved = ctx.saved_tensors
-        saved = saved[:len(saved) - getattr(ctx, "n_extra", 0)]
-        leaves = [a.detach().requires_grad_(bool(n)) for a, n in zip(saved, need)]
-        x, e, params = leaves[0], leaves[1], leaves[2:]
-        act = _torch_activation(activation, act_param)
-        with torch.enable_grad():
-            h = torch.cat([x[src.long()], x[dst.long()], e], dim=-1)
-            for k in range(num_linear):
-                h = F.linear(h, params[k], params[num_linear + k])
-                if k + 1 < num_linear:
-                    h = act(h)
-            if has_ln:
-                h = F.layer_norm(h, (h.size(-1),), params[2 * num_linear], params[2 * num_linear + 1], ln_eps)
-            h = h + e
-            wanted = [t for t, n in zip(leaves, need) if n]
-            grads = iter(torch.autograd.grad(h, wanted, grad_out.contiguous(), allow_unused=True))
-        return (None, None) + tuple(next(grads) if n else None for n in need)
+        return (None, None) + _torch_recompute_backward(
+            call, flat, need, grad_out, lambda t: torch.cat([t[0][src.long()], t[0][dst.long()], t[1]], dim=-1),
+            residual=lambda a: a.tables[1])
 
 
-def _edge_wsplit_backward_hip(ctx, grad_out, grad_agg=None):
+def _edge_wsplit_backward_hip(call: _MlpCall, topo, flat, extra, need, grad_out, grad_agg=None):
     """HIP backward of the W-split edge processor.  Per edge: the K8 data kernel (recompute + chain),
     then dz0 is (i) the gradient of both gathered projections - summed per node through the two CSRs
-    (destination-sorted: the forward's; source-sorted: topo.csc) - and (ii) the left operand of dWe."""
-    src, dst, num_linear, activation, act_param, ln_eps, has_ln = ctx.meta
-    topo = ctx.topo
-    need = ctx.needs_input_grad[2:]
-    saved = ctx.saved_tensors
-    n_extra = getattr(ctx, "n_extra", 0)
-    extra = list(saved[len(saved) - n_extra:]) if n_extra else []
-    saved = saved[:len(saved) - n_extra]
-    x, e = saved[0], saved[1]
-    params = list(saved[2:])
-    weights, biases = params[:num_linear], params[num_linear:2 * num_linear]
-    ln = (params[2 * num_linear], params[2 * num_linear + 1], ln_eps) if has_ln else None
-    if topo is None or activation != "ReLU" or not (grad_out if grad_out is not None else grad_agg).is_cuda:
+    (destination-sorted: the forward's; source-sorted: topo.csc) - and (ii) the left operand of dWe.
+    ``extra``: what the training forward kept behind the arguments (ps, pd, post-activations), or nothing."""
+    a, n = call.unpack(flat), call.unpack(need)
+    (x, e), (src, dst), w0 = a.tables, call.indices, a.weights[0]
+    if topo is None or call.activation != "ReLU" or not (grad_out if grad_out is not None else grad_agg).is_cuda:
         return None
     dn = x.size(1)
-    w0 = weights[0]
-    h = w0.size(0)
-    ws_, wd_, we_ = w0[:, :dn], w0[:, dn:2 * dn], w0[:, 2 * dn:]
     # the forward's projections are needed again as the gathered additive inputs (kept by the training forward)
-    if extra:
-        ps, pd = extra[0], extra[1]
-    else:
-        ps, pd = _node_projections(x, w0, dn)
+    ps, pd, *acts = extra or _node_projections(x, w0, dn)
     segments = [(ps, src), (pd, dst), (e, None)]
     modes = [native.SEG_ADD, native.SEG_ADD, native.SEG_MATMUL]
-    wl = [we_] + weights[1:]
-    if not native.mlp_backward_supported(segments, wl, biases, ln, activation, e, e.size(0), modes):
+    wl = [w0[:, 2 * dn:]] + a.weights[1:]
+    if not native.mlp_backward_supported(segments, wl, a.biases, a.ln, call.activation, e, call.rows, modes):
         return None
-    r = native.mlp_backward(segments, wl, biases, ln, grad_out.contiguous() if grad_out is not None else None, rows=e.size(0),
-                            modes=modes, need_dx=bool(need[1]), residual=e,
+    r = native.mlp_backward(segments, wl, a.biases, a.ln, grad_out.contiguous() if grad_out is not None else None, rows=call.rows,
+                            modes=modes, need_dx=bool(n.tables[1]), residual=e,
                             grad_gather=(grad_agg.contiguous(), dst) if grad_agg is not None else None,
-                            saved_act=extra[2:] or None, defer_ln_sums=True)
+                            saved_act=acts or None, defer_ln_sums=True)
     grad_out = r["grad_out"]  # effective row-ordered gradient (None when the launch gathered part of it itself)
     dz0 = r["dz"][0]
-    grads = [None] * (2 + len(params))
-    if need[1]:  # through We, plus the residual path (folded into the kernel's dx when it can)
-        grads[1] = r["dx"] if r["residual_folded"] else r["dx"] + grad_out
+    de = None
+    if n.tables[1]:  # through We, plus the residual path (folded into the kernel's dx when it can)
+        de = r["dx"] if r["residual_folded"] else r["dx"] + grad_out
     # node side: d(ps)[v] = sum of dz0 over edges with src == v, d(pd)[v] = ... dst == v
     csc_rowptr, csc_perm = topo.csc
     dps = native.scatter_sum_csr(dz0, csc_rowptr, csc_perm, topo.num_nodes)
     dpd = native.scatter_sum_csr(dz0, topo.rowptr, None, topo.num_nodes)
-    if need[0]:  # dx = dps Ws + dpd Wd: one projection launch over [dps | dpd] with the weight [Ws ; Wd]^T
-        grads[0] = native.projection_t2(dps, dpd, w0, dn)  # (a small batch reads W0 transposed, in one launch, without the copy)
-    # every weight-gradient product of this processor (and the row sums of its LayerNorm partials) in one xty_multi call:
-    # one launch for a small batch; dW_0 = [dps^T x | dpd^T x | dz0^T e] is written block by block in place
-    products, slots = [], []
-    if need[2] or need[2 + num_linear]:
-        dw0 = torch.empty(h, 2 * dn + e.size(1), dtype=torch.float32, device=e.device)
-        products += [(dps, x, dw0[:, :dn]), (dpd, x, dw0[:, dn:2 * dn])]
-        slots += [None, None]
-        if "dw" in r:
-            dw0[:, 2 * dn:] = r["dw"][0]
-            grads[2 + num_linear] = r["db"][0]
-        else:
-            products.append((dz0, e, dw0[:, 2 * dn:]))
-            slots.append(("b", 0))
-        grads[2] = dw0
-    for k in range(1, num_linear):
-        if "dw" in r:
-            grads[2 + k], grads[2 + num_linear + k] = r["dw"][k], r["db"][k]
-        else:
-            products.append((r["dz"][k], r["act"][k - 1], None))
-            slots.append(("wb", k))
-    ln_part = r.get("ln_part")
-    res, sums = native.xty_multi(products, [ln_part] if ln_part is not None else [])
-    for slot, (c, cs) in zip(slots, res):
-        if slot is None:
-            continue
-        kind, k = slot
-        if kind == "wb":
-            grads[2 + k] = c
-        grads[2 + num_linear + k] = cs
-    if has_ln:
-        if ln_part is not None:
-            od = ln_part.size(1) // 2
-            dbeta, dgamma = sums[0][:od], sums[0][od:]
-        else:
-            dbeta, dgamma = r["ln_sums"] if r["ln_sums"] is not None else native.colsum_pair(grad_out, r["yhat"])
-        grads[2 + 2 * num_linear] = dgamma
-        grads[2 + 2 * num_linear + 1] = dbeta
-    return tuple(g if n else None for g, n in zip(grads, need))
+    # dx = dps Ws + dpd Wd: one projection launch over [dps | dpd] with the weight [Ws ; Wd]^T
+    # (a small batch reads W0 transposed, in one launch, without the copy)
+    dx = native.projection_t2(dps, dpd, w0, dn) if n.tables[0] else None
+    # dW_0 = [dps^T x | dpd^T x | dz0^T e]; the layers behind the first are formed whether or not their parameters train
+    behind = [True] * (call.num_linear - 1)
+    dw, db, dgamma, dbeta = _parameter_grads(r, [(dps, x), (dpd, x), (dz0, e)], n.weights[:1] + behind, n.biases[:1] + behind,
+                                             n.ln, grad_out)
+    return call.grads(need, (dx, de), dw, db, dgamma, dbeta)
 
 
 def edge_processor_wsplit(x, e, topo, weights, biases, ln, activation="ReLU", act_param=0.0, with_agg=False):
     """``with_agg=True`` returns ``(e', agg)``: the per-destination sums come from the edge launch's epilogue (or
     from K1 when that launch cannot carry it) and both outputs are differentiable."""
-    meta = (topo.src_sorted, topo.dst_sorted, len(weights), activation, float(act_param),
-            float(ln[2]) if ln is not None else 0.0, ln is not None, bool(with_agg), torch.is_grad_enabled())
-    args = list(weights) + list(biases) + ([ln[0], ln[1]] if ln is not None else [])
-    return _EdgeProcessorWSplit.apply(meta, topo, x, e, *args)
+    call = _MlpCall((topo.src_sorted, topo.dst_sorted), len(weights), activation, act_param, ln, None, e.size(0), with_agg=with_agg)
+    return _EdgeProcessorWSplit.apply(call, topo, *call.pack((x, e), weights, biases, ln))
 
 
 def edge_processor_wsplit_aggregated(x, e, topo, weights, biases, ln, activation="ReLU", act_param=0.0, store_edges=True):
