@@ -7,6 +7,8 @@ by torchvision's ``ImageFolder`` rules and yields ``((x, pos, edge_index), label
 ``DataLoader(ds, batch_size=1, shuffle=True, collate_fn=lambda b: b[0])`` works unchanged.  Behind the reference's own
 parameters, ``edges="knn"`` (with ``knn_k`` and ``knn_pos_weight``) swaps a method's edge list for the k nearest neighbours of
 every node in (colour, position), ``image_to_graph.graphs_from_images``' option (DESIGN K24); ``edges=None`` is the reference.
+``node_features="descriptor"`` (superpixel only, DESIGN K26) widens ``x`` from the mean colour to 16 region descriptor columns;
+``num_node_features`` is the width to build the model with.
 
 ``GraphImageFolder.loader()`` is the fast way through an epoch: the same samples in the same order as that
 ``DataLoader`` (and the same draws from the global RNG), with decoding on a host thread pool and the resize and the
@@ -98,10 +100,11 @@ class GraphImageFolder(Dataset):
     out as ``torchvision.datasets.ImageFolder`` expects (``root/<class>/.../<image>``)."""
 
     def __init__(self, dataset_path='dataset', resize_value=128, diagonals=False, method='pixel', n_segments=100,
-                 patch_size=8, use_cache=True, edges=None, knn_k=8, knn_pos_weight=1.0, augment=None):
+                 patch_size=8, use_cache=True, edges=None, knn_k=8, knn_pos_weight=1.0, augment=None, node_features=None):
         if method not in I2G.METHODS:
             raise ValueError(f"Unknown method: {method}")
         I2G.check_edges(edges, knn_k)
+        I2G.check_node_features(node_features, method)
         self.dataset_path = dataset_path
         self.classes, self.class_to_idx = find_classes(dataset_path)
         self.samples = make_dataset(dataset_path, self.class_to_idx)
@@ -116,15 +119,22 @@ class GraphImageFolder(Dataset):
         self.knn_k = knn_k
         self.knn_pos_weight = knn_pos_weight
         self.augment = _check_augment(augment)  # an augment.Augmentation for the loaders (K25); None: the plain images
+        self.node_features = node_features  # None: the method's own x; "descriptor": 16 region descriptor columns (superpixel, K26)
 
     def __len__(self):
         return len(self.samples)
+
+    @property
+    def num_node_features(self) -> int:
+        """Columns of ``x``, for ``GraphNet(num_local_features=...)``: 3, or 16 under ``node_features="descriptor"``."""
+        return 3 if self.node_features is None else I2G.REGION_DESCRIPTOR_DIM
 
     def _graphs(self, images, augmentation=None):
         return I2G.graphs_from_images(images, self.method, resize_value=self.resize_value, diagonals=self.diagonals,
                                       use_cache=self.use_cache, n_segments=self.n_segments,
                                       patch_size=self.patch_size, edges=self.edges, knn_k=self.knn_k,
-                                      knn_pos_weight=self.knn_pos_weight, augmentation=augmentation)
+                                      knn_pos_weight=self.knn_pos_weight, augmentation=augmentation,
+                                      node_features=self.node_features)
 
     _build = _graphs  # what a loader calls per chunk
 

@@ -111,23 +111,104 @@ def image_to_graph_patch(image_or_path, resize_value: int = 128, patch_size: int
     return patch_graph_from_array(_load_resized(image_or_path, resize_value), patch_size)
 
 
-def superpixel_graph_from_labels(img_u8: np.ndarray, segments: np.ndarray):
+NODE_FEATURES = (None, "descriptor")
+# the columns of a region descriptor (csrc/region_descriptor.hip, DESIGN K26), GNC_REGION_DESCRIPTOR_DIM of them
+DESCRIPTOR_COLUMNS = ("mean_r", "mean_g", "mean_b", "std_r", "std_g", "std_b", "area", "bbox_height", "bbox_width",
+                      "spread_y", "spread_x", "box_fill", "boundary", "texture_r", "texture_g", "texture_b")
+REGION_DESCRIPTOR_DIM = len(DESCRIPTOR_COLUMNS)
+# what one launch of gnc_region_descriptors_rgb_u8 takes: the limits of the batched region-graph build
+REGION_DESCRIPTOR_MAX_PIXELS, REGION_DESCRIPTOR_MAX_NODES = 65536, 512
+
+
+def check_node_features(node_features, method: str = "superpixel") -> None:
+    """The ``node_features`` keyword of the superpixel builders, ``graphs_from_images`` and ``GraphImageFolder``."""
+    if node_features not in NODE_FEATURES:
+        raise ValueError(f"Unknown node_features: {node_features!r} (None: the method's own node features; 'descriptor': "
+                         f"the {REGION_DESCRIPTOR_DIM} region descriptor columns of a superpixel graph)")
+    if node_features is not None and method != "superpixel":
+        raise ValueError(f"node_features={node_features!r} needs method='superpixel', got method={method!r}: a pixel has no "
+                         "extent, and patch descriptors are not implemented")
+
+
+def _region_descriptors_launch(img: torch.Tensor, labels: torch.Tensor, node_capacity: int):
+    """ONE launch over a contiguous device batch ``[B, H, W, 3]`` uint8 / ``[B, H, W]`` int32: ``(desc [B, cap, 16], counts [B, 3])``."""
+    lib = native.load_library()
+    B, H, W, _ = img.shape
+    with torch.cuda.device(img.device):
+        nbytes = lib.gnc_region_descriptors_workspace_bytes(B, H, W, node_capacity)
+        if nbytes == 0:
+            raise NotImplementedError(f"region_descriptors: {B} images of {H} x {W} at {node_capacity} nodes is outside the "
+                                      f"supported set (H*W <= {REGION_DESCRIPTOR_MAX_PIXELS}, {REGION_DESCRIPTOR_MAX_NODES} nodes)")
+        desc = torch.empty(B, node_capacity, REGION_DESCRIPTOR_DIM, dtype=torch.float32, device=img.device)
+        counts = torch.empty(B, 3, dtype=torch.int32, device=img.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        native._check(lib.gnc_region_descriptors_rgb_u8(labels.data_ptr(), img.data_ptr(), B, H, W, node_capacity,
+                                                        desc.data_ptr(), counts.data_ptr(), ws.data_ptr(), nbytes,
+                                                        torch.cuda.current_stream(img.device).cuda_stream),
+                      "gnc_region_descriptors_rgb_u8")
+    return desc, counts
+
+
+def region_descriptors(images_u8, labels, node_capacity: int | None = None):
+    """Region descriptors of label images (csrc/region_descriptor.hip, K26): for every region of ``labels`` the 16 float32 columns
+    ``DESCRIPTOR_COLUMNS`` - mean colour (the plain superpixel ``x``, bit for bit), colour standard deviation, area share,
+    bounding-box extent, spatial spread, box fill, boundary share and texture - all in [0, 1], from exact integer sums.
+
+    ``images_u8`` ``[B, H, W, 3]`` uint8 with ``labels`` ``[B, H, W]`` (values in ``[0, H W)``, gaps allowed; row ``i`` is node ``i``
+    of the region graph of the same labels): ``desc [B, node_capacity, 16]`` and int32 ``counts [B, 3]`` = (regions, bad-label flag,
+    overflow flag) on the device, ONE launch and no host synchronisation; rows behind an image's region count are zeros, and an
+    image with a flag set holds zeros only.  ``node_capacity`` defaults to 512, the most one launch takes.
+
+    One image ``[H, W, 3]`` with ``[H, W]`` labels: ``desc [regions, 16]`` (this form reads the count; a label outside
+    ``[0, H W)`` raises ``ValueError``, more regions than the capacity ``NotImplementedError``) and ``counts [3]``."""
+    img = images_u8 if isinstance(images_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images_u8))
+    if img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError("region_descriptors: expected a uint8 RGB image [H, W, 3] or batch [B, H, W, 3]")
+    single = img.dim() == 3
+    img = (img.unsqueeze(0) if single else img).to(_device()).contiguous()
+    lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels))
+    lab = lab.unsqueeze(0) if single and lab.dim() == 2 else lab
+    if tuple(lab.shape) != tuple(img.shape[:3]):
+        raise ValueError("region_descriptors: expected label images of the images' size")
+    lab = lab.to(device=img.device, dtype=torch.int32).contiguous()
+    cap = REGION_DESCRIPTOR_MAX_NODES if node_capacity is None else int(node_capacity)
+    desc, counts = _region_descriptors_launch(img, lab, cap)
+    if not single:
+        return desc, counts
+    regions, bad, overflow = (int(v) for v in counts[0].tolist())
+    if bad:
+        raise ValueError("label image has values outside [0, H*W)")
+    if overflow:
+        raise NotImplementedError(f"region_descriptors: {regions} regions do not fit node_capacity = {cap} (at most "
+                                  f"{REGION_DESCRIPTOR_MAX_NODES} regions and H*W <= {REGION_DESCRIPTOR_MAX_PIXELS})")
+    return desc[0, :regions], counts[0]
+
+
+def superpixel_graph_from_labels(img_u8: np.ndarray, segments: np.ndarray, node_features=None):
     """Everything of superpixel.py after the SLIC call (:33-71) for a given label image: per-segment mean
-    colour (of img/255) and centroid, region adjacency, edges [i,j],[j,i] in lexicographic order."""
+    colour (of img/255) and centroid, region adjacency, edges [i,j],[j,i] in lexicographic order.
+    ``node_features="descriptor"``: ``x`` is the region descriptor ``[nodes, 16]`` (``region_descriptors``), whose first three
+    columns are the plain ``x``."""
+    check_node_features(node_features)
     img = _to_device_u8(img_u8)
     H, W, C = img.shape
     if C != 3 or segments.shape != (H, W):
         raise ValueError("expected an RGB image and a label image of the same size")
     labels = torch.from_numpy(np.ascontiguousarray(segments.astype(np.int32))).to(img.device)
-    return _superpixel_graph_from_device_labels(img, labels)
+    return _superpixel_graph_from_device_labels(img, labels, node_features)
 
 
-def _superpixel_graph_from_device_labels(img_u8, labels: torch.Tensor):
+def _superpixel_graph_from_device_labels(img_u8, labels: torch.Tensor, node_features=None):
     lib = native.load_library()
     img = img_u8 if isinstance(img_u8, torch.Tensor) else _to_device_u8(img_u8)
     H, W, C = img.shape
     labels = labels.to(device=img.device, dtype=torch.int32).contiguous()
     n = H * W
+    desc = None
+    if node_features is not None:  # one more launch off the same labels, in front of the one host read
+        if n > REGION_DESCRIPTOR_MAX_PIXELS:
+            raise NotImplementedError(_descriptor_limits(f"an image of {H} x {W}"))
+        desc, _ = _region_descriptors_launch(img.contiguous().unsqueeze(0), labels.unsqueeze(0), REGION_DESCRIPTOR_MAX_NODES)
     x = torch.empty(n, 3, dtype=torch.float32, device=img.device)
     pos = torch.empty(n, 2, dtype=torch.float32, device=img.device)
     ei = torch.empty(2, 4 * n, dtype=torch.int64, device=img.device)
@@ -143,7 +224,16 @@ def _superpixel_graph_from_device_labels(img_u8, labels: torch.Tensor):
     s, e, bad = (int(v) for v in counts.tolist())  # one host sync: the sizes are data dependent
     if bad:
         raise ValueError("label image has values outside [0, H*W)")
+    if desc is not None:
+        if s > REGION_DESCRIPTOR_MAX_NODES:
+            raise NotImplementedError(_descriptor_limits(f"a graph of {s} regions"))
+        return desc[0, :s], pos[:s], ei[:, :e]
     return x[:s], pos[:s], ei[:, :e]
+
+
+def _descriptor_limits(what: str) -> str:
+    return (f"node_features='descriptor': {what} is outside what the descriptor kernel takes (at most "
+            f"{REGION_DESCRIPTOR_MAX_NODES} regions and H*W <= {REGION_DESCRIPTOR_MAX_PIXELS})")
 
 
 def slic(image_u8, n_segments: int = 100, compactness: float = 10, max_iter: int = 10,
@@ -198,7 +288,7 @@ def superpixel_capacities(n_segments: int) -> tuple[int, int]:
 
 
 def superpixel_graphs_batched(images_u8, labels=None, *, n_segments: int = 100, compactness: float = 10,
-                              node_capacity: int, edge_capacity: int) -> SuperpixelGraphBatch:
+                              node_capacity: int, edge_capacity: int, node_features=None) -> SuperpixelGraphBatch:
     """Region graphs of a batch of resized uint8 RGB images ``[B, H, W, 3]`` in ONE launch (csrc/rag_batched.hip), with
     no host synchronisation: ``x [B, node_capacity, 3]``, ``pos [B, node_capacity, 2]``, ``edge_index [B, 2,
     edge_capacity]`` and int32 ``counts [B, 4]`` = (nodes, directed edges, bad-label flag, overflow flag) on the device.
@@ -206,7 +296,13 @@ def superpixel_graphs_batched(images_u8, labels=None, *, n_segments: int = 100, 
 
     Image ``b``'s graph is ``x[b, :nodes]``, ``pos[b, :nodes]``, ``edge_index[b, :, :edges]`` and equals
     ``superpixel_graph_from_labels`` of that image bit for bit; rows behind it are 0, edge slots -1.  An image whose
-    overflow flag is set reports its true sizes (edges = -1 above 512 nodes) and holds padding only."""
+    overflow flag is set reports its true sizes (edges = -1 above 512 nodes) and holds padding only.
+
+    ``node_features="descriptor"`` (K26): ``x`` is ``[B, node_capacity, 16]``, the region descriptors of the same labels
+    (``region_descriptors``: one more launch, still no host synchronisation), so ``x[..., :3]`` is the plain ``x``; ``pos``,
+    ``edge_index`` and ``counts`` are those of the plain build.  The descriptor kernel knows no edge capacity: an image that
+    overflows on its edges alone keeps its descriptor rows, one with more nodes than ``node_capacity`` holds zeros."""
+    check_node_features(node_features)
     lib = native.load_library()
     img = images_u8 if isinstance(images_u8, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images_u8))
     if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[-1] != 3:
@@ -236,26 +332,31 @@ def superpixel_graphs_batched(images_u8, labels=None, *, n_segments: int = 100, 
                                                 x.data_ptr(), pos.data_ptr(), ei.data_ptr(), counts.data_ptr(),
                                                 ws.data_ptr(), nbytes, torch.cuda.current_stream(img.device).cuda_stream),
                       "gnc_rag_build_batched")
+    if node_features is not None:
+        x, _ = _region_descriptors_launch(img, labels, node_capacity)
     return SuperpixelGraphBatch(x, pos, ei, counts)
 
 
-def _superpixel_graphs_from_device_batch(imgs: torch.Tensor, labels: torch.Tensor, node_capacity: int, edge_capacity: int, knn=None):
+def _superpixel_graphs_from_device_batch(imgs: torch.Tensor, labels: torch.Tensor, node_capacity: int, edge_capacity: int, knn=None,
+                                         node_features=None):
     """The loader's list of ``(x, pos, edge_index)`` for a device batch: one batched build, ONE host read of the sizes;
     an image that does not fit the capacities (or a batch outside the kernel's supported set) takes the per-image path.
     ``knn = (k, pos_weight)``: the edges are the k nearest neighbours instead (K24), one more launch over the padded batch, off
-    its device node counts and in front of the same single host read."""
+    its device node counts and in front of the same single host read.  ``node_features="descriptor"`` (K26): one more launch
+    off the same labels and capacities, in front of that read too; the kNN space stays (colour, position) = ``x[..., :3]``."""
     B, H, W, _ = imgs.shape
 
     def per_image(im, lab):
-        x, pos, ei = _superpixel_graph_from_device_labels(im, lab)
-        return (x, pos, ei) if knn is None else (x, pos, _knn_edges_of_graph(x, pos, "superpixel", H, *knn))
+        x, pos, ei = _superpixel_graph_from_device_labels(im, lab, node_features)
+        return (x, pos, ei) if knn is None else (x, pos, _knn_edges_of_graph(x[:, :3], pos, "superpixel", H, *knn))
 
     if native.load_library().gnc_rag_batched_workspace_bytes(B, H, W, node_capacity, edge_capacity) == 0:
         return [per_image(im, lab) for im, lab in zip(imgs, labels)]
-    batch = superpixel_graphs_batched(imgs, labels, node_capacity=node_capacity, edge_capacity=edge_capacity)
+    batch = superpixel_graphs_batched(imgs, labels, node_capacity=node_capacity, edge_capacity=edge_capacity,
+                                      node_features=node_features)
     if knn is not None:
         k = knn[0]
-        knn_ei, _, _ = native.knn_graph_padded(knn_features(batch.x, batch.pos, "superpixel", H, knn[1]), batch.counts, k)
+        knn_ei, _, _ = native.knn_graph_padded(knn_features(batch.x[..., :3], batch.pos, "superpixel", H, knn[1]), batch.counts, k)
     graphs = []
     for b, (s, e, bad, overflow) in enumerate(batch.counts.tolist()):  # the chunk's one host sync
         if bad:
@@ -270,20 +371,24 @@ def _superpixel_graphs_from_device_batch(imgs: torch.Tensor, labels: torch.Tenso
     return graphs
 
 
-def superpixel_graph_from_array(img_u8: np.ndarray, n_segments: int = 100, compactness: float = 10):
-    """superpixel.py:29-71 for an already resized uint8 RGB array: device SLIC, then the region graph."""
+def superpixel_graph_from_array(img_u8: np.ndarray, n_segments: int = 100, compactness: float = 10, node_features=None):
+    """superpixel.py:29-71 for an already resized uint8 RGB array: device SLIC, then the region graph
+    (``node_features="descriptor"``: with the region descriptors as ``x``, K26)."""
+    check_node_features(node_features)
     labels = slic(img_u8, n_segments=n_segments, compactness=compactness, start_label=0)
-    return _superpixel_graph_from_device_labels(img_u8, labels)
+    return _superpixel_graph_from_device_labels(img_u8, labels, node_features)
 
 
 def image_to_graph_superpixel(image_or_path, resize_value: int = 128, n_segments: int = 100, compactness: int = 10,
-                              **slic_options):
+                              node_features=None, **slic_options):
     """superpixel.py:8-73, SLIC included, on the device.  Options of scikit-image's ``slic`` that the reference never
-    passes (mask, sigma, spacing, slic_zero, ...) are not implemented and raise."""
+    passes (mask, sigma, spacing, slic_zero, ...) are not implemented and raise.  ``node_features="descriptor"`` (K26): ``x`` is
+    the ``[nodes, 16]`` region descriptor instead of the mean colour, which stays its first three columns."""
+    check_node_features(node_features)
     if slic_options:
         raise NotImplementedError(f"image_to_graph_superpixel: SLIC options {sorted(slic_options)} are not implemented "
                                   "(the reference passes only n_segments and compactness)")
-    return superpixel_graph_from_array(_load_resized(image_or_path, resize_value), n_segments, compactness)
+    return superpixel_graph_from_array(_load_resized(image_or_path, resize_value), n_segments, compactness, node_features)
 
 
 # PIL.Image.Resampling values; the device resize implements the three whose weights need no sin / cos
@@ -574,7 +679,7 @@ METHODS = ("pixel", "patch", "superpixel")
 def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128, diagonals: bool = False,
                        use_cache: bool = True, n_segments: int = 100, patch_size: int = 8, compactness: float = 10, *,
                        node_capacity: int | None = None, edge_capacity: int | None = None, edges=None, knn_k: int = 8,
-                       knn_pos_weight: float = 1.0, augmentation=None):
+                       knn_pos_weight: float = 1.0, augmentation=None, node_features=None):
     """Graphs of a batch of decoded uint8 RGB images ``[H_i, W_i, 3]`` (any sizes): a list of ``(x, pos, edge_index)``
     equal to ``image_to_graph_pixel_optimized`` / ``image_to_graph_patch`` / ``image_to_graph_superpixel`` of each
     image, with arguments named as ``utils/dataloader.py``'s ``OptimizedDatasetLoader``.  The resize of the whole
@@ -592,10 +697,17 @@ def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128
 
     ``augmentation`` (K25): the parameters ``augment.Augmentation.sample`` drew for these images.  The one ``resize`` call then is
     ``crop_resize`` (random resized crop and horizontal flip) followed by ``color_jitter``: the graphs are those of the images
-    Pillow produces with the same parameters, and everything behind the resize is unchanged.  None: no new launch."""
+    Pillow produces with the same parameters, and everything behind the resize is unchanged.  None: no new launch.
+
+    ``node_features="descriptor"`` (K26, ``method="superpixel"`` only; another method raises ``ValueError``): ``x`` is the
+    ``[nodes, 16]`` region descriptor (``region_descriptors``; ``x[:, :3]`` is the plain ``x``), ``pos`` and ``edge_index`` are
+    unchanged - ``edges="knn"`` still looks for neighbours in (colour, position).  One more launch per chunk in front of the same
+    single host read; an image on the per-image path runs the kernel alone, and one with more than 512 regions or
+    ``H W > 65536`` raises ``NotImplementedError``."""
     if method not in METHODS:
         raise ValueError(f"Unknown method: {method}")
     check_edges(edges, knn_k)
+    check_node_features(node_features, method)
     if len(images_u8) == 0:
         return []
     if augmentation is not None:
@@ -618,7 +730,8 @@ def graphs_from_images(images_u8, method: str = "pixel", resize_value: int = 128
     nodes, cap_edges = superpixel_capacities(n_segments)
     return _superpixel_graphs_from_device_batch(imgs, labels, nodes if node_capacity is None else int(node_capacity),
                                                 cap_edges if edge_capacity is None else int(edge_capacity),
-                                                knn=None if edges is None else (knn_k, knn_pos_weight))
+                                                knn=None if edges is None else (knn_k, knn_pos_weight),
+                                                node_features=node_features)
 
 
 EDGES = (None, "knn")

@@ -110,6 +110,9 @@ _SIGNATURES = {
     "gnc_rag_batched_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "gnc_rag_build_batched": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gnc_region_descriptors_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "gnc_region_descriptors_rgb_u8": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                                c_void_p, c_size_t, c_void_p]),
     "gnc_slic_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "gnc_slic_rgb_u8": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_int32, c_int32, c_double, c_double,
                                   c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

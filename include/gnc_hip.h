@@ -846,6 +846,32 @@ int gnc_rag_build_batched(const int32_t* labels, const uint8_t* img, int32_t B, 
                           int32_t node_capacity, int32_t edge_capacity, float* x, float* pos, int64_t* edge_index,
                           int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K26: region descriptors for superpixel nodes (csrc/region_descriptor.hip) ----
+ * gnc_region_descriptors_rgb_u8  `labels` [B, H, W] int32 in [0, H*W) (gaps allowed; regions are numbered as gnc_rag_build
+ *                      numbers them), `img` [B, H, W, 3] uint8 -> out [B, node_capacity, GNC_REGION_DESCRIPTOR_DIM] float32
+ *                      (16-byte aligned) and counts [B, 3] = (regions, 1 if a label was outside [0, H*W), 1 if there are
+ *                      more regions than node_capacity), in ONE launch.  Columns of a region with n pixels, from exact
+ *                      integer sums, every expression evaluated in double and cast to float:
+ *                        0-2   mean colour (S_c / 255) / n          = the x of gnc_rag_build, bit for bit
+ *                        3-5   colour std  sqrt(n Q_c - S_c^2) / (255 n)
+ *                        6     area share  n / (H W)
+ *                        7, 8  bounding-box extent  (ymax - ymin + 1) / H, (xmax - xmin + 1) / W
+ *                        9, 10 spatial spread  sqrt(n Syy - Sy^2) / (n H), sqrt(n Sxx - Sx^2) / (n W)
+ *                        11    box fill  n / ((ymax - ymin + 1)(xmax - xmin + 1))
+ *                        12    boundary share: pixels with a 4-neighbour of another label / n
+ *                        13-15 texture: mean |v_c(p) - v_c(q)| / 255 over the horizontally and vertically adjacent pixel
+ *                              pairs inside the region (0 without such a pair)
+ *                      Rows behind the region count are zeros; a flagged image's slice is all zeros.  Supported:
+ *                      H*W <= 65536, node_capacity <= 512, B <= 2^20; gnc_region_descriptors_workspace_bytes returns 0
+ *                      outside that set.  Integer atomics only (deterministic), stream-ordered, no host synchronisation,
+ *                      safe under stream capture.  Added without an ABI bump.
+ */
+#define GNC_REGION_DESCRIPTOR_DIM 16
+size_t gnc_region_descriptors_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t node_capacity);
+int gnc_region_descriptors_rgb_u8(const int32_t* labels, const uint8_t* img, int32_t B, int32_t H, int32_t W,
+                                  int32_t node_capacity, float* out, int32_t* counts, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* ---- SLIC superpixels on the device (ABI 20; image_to_graph_superpixel.py:31) ------------------
  * gnc_slic_rgb_u8      scikit-image 0.18.3 `slic(img_as_float(img), n_segments, compactness, max_iter,
  *                      enforce_connectivity, min_size_factor, max_size_factor, start_label)` with sigma = 0, no
